@@ -7,13 +7,18 @@ cell integration, constrained scatter) on a synthetic uniformly refined 3-D Sned
 CSR).  Inputs are resident in HBM when the timed region starts; outputs stay on the device.
 
   python bench.py                       # N=1, 216^3 cells
+  python bench.py --full                # + every other line of SURVEY.md 8(d) and the CPU baseline
+  python bench.py --dump-outputs DIR    # + what the last timed step computed, as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N   # strong scaling: the same mesh cut into N sub-boxes,
                                              # ghost values exchanged over RCCL (cracks_amd/halo.py)
 
-Prints ONE JSON line on rank 0 (contract in the task description) with the extra objects
-"roofline" (dominant kernel, HIP-event timed, algorithmic bytes of SURVEY.md §8(d)) and
-"cpu_baseline" (the CPU oracle = loop-for-loop port of the reference, timed on this host).
+Prints ONE JSON line on rank 0 (contract in the task description) with the extra object
+"roofline" (dominant kernel, HIP-event timed in the timed steps, algorithmic bytes of SURVEY.md §8(d)).  A plain
+run sets up, warms up, times the steps and prints; everything measured besides the headline is behind --full:
+"cpu_baseline" (the CPU oracle = loop-for-loop port of the reference, timed on this host), "extra" (residual-only,
+2-D, general-family, overlay and config-5 lines), "host_pointer_call", the context rebuild and, for N > 1, the
+near-cubic second partition.
 """
 from __future__ import annotations
 
@@ -29,9 +34,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL peer-to-peer between the ranks of a node
 
-HBM_PEAK_GBS = 8000.0  # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X spec sheet
 N_SIMD = 1024  # 256 CUs x 4 SIMDs
 CLOCK_GHZ = 2.4  # max clock (the chip sustains ~1.6-2.1 GHz under FP64 load: profiles/r02/microbench_mfma_f64_lds.txt)
+DUMP_VALUES = 1 << 20  # --dump-outputs: values per array at most (8 MiB of float64; at most 5 arrays)
 
 
 def kernel_source_hash() -> str:
@@ -631,6 +637,26 @@ def host_pointer_call(asm, dev, n_dofs: int):
     return rec
 
 
+def dump_outputs(asm, residual_only: bool, out_dir: str):
+    """What the last assembly handed its caller, as <out_dir>/<name>.npy in float64: the residual(s) and, for the Jacobian,
+    the CSR value array of every block.  An array longer than DUMP_VALUES is cut to the sorted distinct positions of
+    DUMP_VALUES draws from a generator seeded with its length: the same entries in every run with the same arguments, so
+    two builds of the project compare entry for entry."""
+    import torch
+
+    outs = {"system_pde_residual": asm.system_pde_residual}
+    if residual_only:
+        outs["system_total_residual"] = asm.system_total_residual
+    else:  # residual_total is not written by a Jacobian assembly (include/pfm_assemble.h)
+        outs.update({f"system_pde_matrix_block{b}": m for b, m in enumerate(asm.system_pde_matrix)})
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outs.items():
+        if t.numel() > DUMP_VALUES:
+            idx = np.unique(np.random.default_rng(t.numel()).integers(0, t.numel(), DUMP_VALUES))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def self_launch_command(n_gpus: int, argv):
     """argv of `python -m torch.distributed.run ... bench.py <argv>` for a single-node run with one rank per GPU."""
     import socket
@@ -654,8 +680,15 @@ def main():
                     help="cells per direction (default 216 in 3-D, 1000 in 2-D); --cells under torch.distributed.run, whose parser trips over --n")
     ap.add_argument("--residual-only", action="store_true")
     ap.add_argument("--path", choices=["auto", "general", "cart", "overlay"], default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra lines (residual-only, 2-D configurations, PCIe-inclusive value)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline, extra lines, context rebuild, "
+                         "near-cubic second partition (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the extra lines (residual-only, 2-D configurations, PCIe-inclusive value) "
+                         "and the near-cubic second partition")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (single rank)")
     ap.add_argument("--checksum", action="store_true",
                     help="add partition-independent sums of the assembled values (outside the timed region): the "
                          "N-rank run must reproduce the 1-rank numbers up to round-off")
@@ -677,6 +710,8 @@ def main():
         os.execv(sys.executable, self_launch_command(args.gpus, sys.argv[1:]))
     if world != args.gpus:
         sys.exit(f"--gpus {args.gpus} does not match WORLD_SIZE={world} of the launcher")
+    if args.dump_outputs and world > 1:
+        sys.exit("--dump-outputs needs --gpus 1")
     # PFM_BENCH_SMOKE_GLOO=1: all ranks on cuda:0, ghost import staged through the host over gloo -- exercises the
     # multi-process flow on a single-GPU box; never a measurement
     smoke_gloo = os.environ.get("PFM_BENCH_SMOKE_GLOO") == "1"
@@ -723,7 +758,7 @@ def main():
     # a second context on the same mesh: pfm_ctx_create without the process's one-time costs (first large host->device
     # copy, pinned staging buffers) = what the rebuild after a refine_mesh costs in a running program
     ctx_rebuild_s = None
-    if world == 1 and not smoke_gloo:
+    if args.full and world == 1 and not smoke_gloo:
         again = Assembler(lp.mesh, blocked=True, device=local_rank, n_owned_nodes=lp.n_owned)
         ctx_rebuild_s = round(again.ctx.create_seconds, 3)
         again.ctx.close()
@@ -759,6 +794,8 @@ def main():
     k_med = float(np.median(k_all)) if k_all.size else 0.0
     k_ms, k_n = asm.ctx.kernel_time_ms()
     asm.ctx.timing_enable(False)
+    if args.dump_outputs:
+        dump_outputs(asm, residual_only, args.dump_outputs)
 
     # the ghost import alone (cracks.cc:2147-2154 as pack -> RCCL group -> unpack): events around halo.exchange, median of 20
     exchange_ms = 0.0
@@ -815,10 +852,11 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
 
     # The headline cut is z-slabs (2 peers, whole x-y tiles); a deal.II host hands over p4est's Morton sub-cubes (up to 7
-    # peers, partial tiles).  The same steps on the near-cubic grid, in the same run, so that the SCALE record shows both.
+    # peers, partial tiles).  With --full, the same steps on the near-cubic grid in the same run, so that the SCALE record
+    # shows both.
     cubic = None
     p_cubic = P.factor_ranks(world, dim)
-    if world > 1 and dim == 3 and tuple(p_cubic) != tuple(p) and not args.no_extras and not residual_only:
+    if args.full and world > 1 and dim == 3 and tuple(p_cubic) != tuple(p) and not args.no_extras and not residual_only:
         asm.ctx.close()
         del asm
         if halo is not None:
@@ -924,7 +962,7 @@ def main():
             out["cubic_partition"] = cubic
         if checksum is not None:
             out["checksum"] = checksum
-        if world == 1 and not smoke_gloo and not args.no_extras and dim == 3 and not residual_only and args.path == "auto":
+        if args.full and world == 1 and not smoke_gloo and not args.no_extras and dim == 3 and not residual_only and args.path == "auto":
             try:
                 out["extra"] = extra_lines(asm, dev, local_rank, n, max(5, args.steps // 2))
                 # PCIe-inclusive figure of SURVEY 8(d), MEASURED: pfm_assemble into the host's own (page-locked) arrays
@@ -933,7 +971,7 @@ def main():
                 out["value_incl_d2h"] = hp.get("DoFs_per_s")  # never the headline value
             except Exception as e:  # the headline line must not depend on the extras
                 out["extra_error"] = f"{type(e).__name__}: {e}"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dim, residual_only)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -249,7 +249,7 @@ def test_bench_multiprocess_flow_reproduces_single_rank_sums(world, cells, extra
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--cells", str(cells), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--checksum"] + extra
+    common = ["--cells", str(cells), "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--checksum"] + extra
     env = dict(os.environ, PFM_BENCH_SMOKE_GLOO="1")
 
     def run(cmd):

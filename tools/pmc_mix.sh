@@ -7,7 +7,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/pmc_mix_raw
 env "$@" timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_SALU SQ_INSTS_LDS \
-   --output-format csv -d $O/pmc_mix_raw -o p -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_mix.log 2>&1
+   --output-format csv -d $O/pmc_mix_raw -o p -- python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $O/pmc_mix.log 2>&1
 cp $O/pmc_mix_raw/p_counter_collection.csv $O/pmc_mix.csv 2>/dev/null
 rm -rf $O/pmc_mix_raw
 python - <<PY
