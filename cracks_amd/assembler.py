@@ -316,6 +316,40 @@ class Context:
                                                           capi.np_ptr(mu, np.float64), out), "pfm_functionals_material")
         return float(out[0]), float(out[1]), float(out[2])
 
+    def face_load(self, cells, faces) -> np.ndarray:
+        """Raw ``int_face sigma(u) n dA`` summed over the (cell, face) pairs (compute_load, cracks.cc:3726-3790), global Lame
+        coefficients, no sign flips; this rank's part.  Returns a vector of ``dim`` entries."""
+        c = np.ascontiguousarray(cells, np.int32)
+        f = np.ascontiguousarray(faces, np.uint8)
+        if c.shape != f.shape:
+            raise ValueError("cells and faces differ in length")
+        out = (C.c_double * 3)()
+        self._check(self.lib.pfm_face_load(self._h, c.size, capi.np_ptr(c, np.int32), capi.np_ptr(f, np.uint8), out),
+                    "pfm_face_load")
+        return np.array(out[:self.dim])
+
+    def cod_lines(self, lines, cell_owned: Optional[np.ndarray] = None, eps: float = 1e-8):
+        """compute_cod of every line at once (cracks.cc:3453-3550): ``(cod, n_faces)``, the raw sums of this rank BEFORE
+        the reference's ``/2`` and MPI sum.  The (line, cell, face) list is cached in the context for the same lines, eps
+        and mask."""
+        ln = np.ascontiguousarray(lines, np.float64)
+        cod = np.zeros(ln.size)
+        nf = np.zeros(ln.size, np.int64)
+        mask = None if cell_owned is None else np.ascontiguousarray(cell_owned, np.uint8)
+        mp = None if mask is None else capi.np_ptr(mask, np.uint8)
+        self._check(self.lib.pfm_cod_lines(self._h, mp, ln.size, capi.np_ptr(ln, np.float64), float(eps),
+                                           capi.np_ptr(cod, np.float64), capi.np_ptr(nf, np.int64)), "pfm_cod_lines")
+        return cod, nf
+
+    def sneddon_phi_error_sq(self, cell_owned: Optional[np.ndarray] = None) -> float:
+        """``int (phi_h - phi_exact)^2`` of ExactPhiSneddon(alpha_eps) over this rank's cells (cracks.cc:4495-4516), before the
+        MPI sum and the root."""
+        out = (C.c_double * 1)()
+        mask = None if cell_owned is None else np.ascontiguousarray(cell_owned, np.uint8)
+        mp = None if mask is None else capi.np_ptr(mask, np.uint8)
+        self._check(self.lib.pfm_sneddon_phi_error(self._h, mp, out), "pfm_sneddon_phi_error")
+        return float(out[0])
+
 
 class Assembler:
     """Device-resident counterpart of the reference's assembly members.

@@ -31,7 +31,7 @@ EXPORTS = [
     "pfm_ctx_device_bytes", "pfm_timing_enable", "pfm_kernel_time_ms", "pfm_kernel_times_ms",
     # include/pfm_newton.h
     "pfm_diag_mass_device", "pfm_active_set_device", "pfm_get_constraints", "pfm_functionals",
-    "pfm_functionals_material", "pfm_residual_norms",
+    "pfm_functionals_material", "pfm_residual_norms", "pfm_face_load", "pfm_cod_lines", "pfm_sneddon_phi_error",
 ]
 
 
@@ -138,6 +138,9 @@ def load():
     lib.pfm_get_constraints.argtypes = [vp, vp]
     lib.pfm_functionals.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.pfm_residual_norms.argtypes = [vp, vp, C.POINTER(C.c_double)]
+    lib.pfm_face_load.argtypes = [vp, i64, vp, vp, C.POINTER(C.c_double)]
+    lib.pfm_cod_lines.argtypes = [vp, vp, i32, vp, C.c_double, vp, vp]
+    lib.pfm_sneddon_phi_error.argtypes = [vp, vp, C.POINTER(C.c_double)]
     _LIB = lib
     return lib
 

@@ -370,6 +370,22 @@ struct pfm_ctx
   int64_t n_partial = 0;
   uint8_t *d_cell_owned = nullptr;
   double *d_func_mat = nullptr; // per-cell Lame override of pfm_functionals_material
+  // post-processing functionals (pfm_postproc.hip): the (line, cell, face) list of pfm_cod_lines, kept for the lines, eps
+  // and cell mask it was built for (the mesh geometry of a context never changes).  Device buffers are in `allocs`.
+  struct CodCache
+  {
+    bool valid = false;
+    std::vector<double> lines;
+    double eps = 0.0;
+    bool masked = false;
+    std::vector<uint8_t> mask;
+    long long *d_line_ptr = nullptr; // [n_lines + 1] entry ranges per line
+    long long *d_entry = nullptr;    // [n_entries] cell * 2 dim + face, ordered by line, cell, face
+    int64_t n_entries = 0;
+  } cod;
+  int32_t *d_face_cells = nullptr; // pfm_face_load input staging (in allocs)
+  uint8_t *d_face_ids = nullptr;
+  int64_t n_face_cap = 0;
   // measurement (pfm_timing_enable)
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

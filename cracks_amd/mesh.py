@@ -35,6 +35,9 @@ __all__ = [
     "update_constraints",
     "node_graph",
     "dof_sparsity",
+    "face_vertices",
+    "boundary_faces",
+    "boundary_faces_at",
 ]
 
 
@@ -604,3 +607,50 @@ def dof_sparsity(mesh: Mesh, layout: DofLayout):
                       shape=(layout.n_dofs, layout.n_dofs))
     A.sort_indices()
     return A.indptr.astype(np.int64), A.indices.astype(np.int32)
+
+
+# ---- boundary faces (compute_load's face list, cracks.cc:3762-3764) --------------------------------------------------
+
+def face_vertices(dim: int) -> List[List[int]]:
+    """deal.II face numbering on lexicographic vertices: face ``f`` is the side ``f % 2`` of reference axis ``f // 2``;
+    its vertices are those with bit ``f // 2`` equal to ``f % 2`` (2-D: 0 = (v0, v2), 1 = (v1, v3), 2 = (v0, v1),
+    3 = (v2, v3))."""
+    return [[v for v in range(1 << dim) if ((v >> (f >> 1)) & 1) == (f & 1)] for f in range(2 * dim)]
+
+
+def _one_cell_faces(mesh: Mesh) -> np.ndarray:
+    """[n_cells, 2 dim] bool: the face's vertex set belongs to no other cell (``at_boundary()`` on a conforming mesh,
+    and on the fine side of a refinement interface the test the harness has used since compute_load_2d)."""
+    fv = face_vertices(mesh.dim)
+    keys = np.sort(np.stack([mesh.cells[:, vs] for vs in fv], axis=1), axis=2)  # [cells, faces, 2^(dim-1)]
+    flat = keys.reshape(-1, keys.shape[2])
+    _, inv, cnt = np.unique(flat, axis=0, return_inverse=True, return_counts=True)
+    return (cnt[inv.ravel()] == 1).reshape(mesh.n_cells, 2 * mesh.dim)
+
+
+def _as_pairs(sel: np.ndarray):
+    c, f = np.nonzero(sel)  # row-major: ordered by cell, then face
+    return c.astype(np.int32), f.astype(np.uint8)
+
+
+def boundary_faces(mesh: Mesh, boundary_id: int, cells: Optional[np.ndarray] = None):
+    """(cells int32, faces uint8) of the boundary faces with id ``boundary_id``: every vertex of the face carries the id
+    (``boundary_nodes``) and no other cell has the face.  ``cells``: optional mask (e.g. ``cell_owned``) of the cells to
+    take the faces of."""
+    on_b = np.zeros(mesh.n_nodes, bool)
+    on_b[mesh.boundary_nodes[boundary_id]] = True
+    sel = np.stack([on_b[mesh.cells[:, vs]].all(axis=1) for vs in face_vertices(mesh.dim)], axis=1) & _one_cell_faces(mesh)
+    if cells is not None:
+        sel &= np.asarray(cells, bool)[:, None]
+    return _as_pairs(sel)
+
+
+def boundary_faces_at(mesh: Mesh, axis: int, value: float, tol: float = 1e-10, cells: Optional[np.ndarray] = None):
+    """(cells, faces) of the boundary faces whose centre has coordinate ``axis`` within ``tol`` of ``value`` (strictly) --
+    how the reference sets boundary id 3 on the three-point mesh (face centre y == 2.0, cracks.cc:1283-1293)."""
+    fv = face_vertices(mesh.dim)
+    centre = np.stack([mesh.coords[mesh.cells[:, vs], axis].mean(axis=1) for vs in fv], axis=1)
+    sel = (centre < value + tol) & (centre > value - tol) & _one_cell_faces(mesh)
+    if cells is not None:
+        sel &= np.asarray(cells, bool)[:, None]
+    return _as_pairs(sel)

@@ -304,7 +304,10 @@ class ActiveSetDriver:
         return new_newton_residual / old_newton_residual if old_newton_residual else 0.0
 
     # ---- time loop (active-set branch) ---------------------------------------------------
-    def run(self, n_steps: Optional[int] = None) -> List[StepRecord]:
+    def run(self, n_steps: Optional[int] = None,
+            step_hook: Optional[Callable[["ActiveSetDriver", StepRecord], None]] = None) -> List[StepRecord]:
+        """``step_hook(driver, record)``: called after every converged time step where the reference computes its
+        statistics (cracks.cc:4436-4460), with the projected and distributed solution in ``driver.solution``."""
         s = self.s
         limit = s.max_no_timesteps if n_steps is None else n_steps - 1
         self.project_back_phase_field()  # cracks.cc:4267
@@ -347,6 +350,8 @@ class ActiveSetDriver:
             self.log(f"No {self.timestep_number} time {self.time:g} bulk energy: {rec.bulk_energy:g} "
                      f"crack energy: {rec.crack_energy:g}" + (f"  Load x: {rec.load:g}" if rec.load is not None else ""))
             self.records.append(rec)
+            if step_hook is not None:
+                step_hook(self, rec)
             self.timestep_number += 1
         return self.records
 

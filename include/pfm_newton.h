@@ -75,6 +75,41 @@ int pfm_functionals(pfm_ctx *ctx, const uint8_t *cell_owned, double out[3]);
 int pfm_functionals_material(pfm_ctx *ctx, const uint8_t *cell_owned, const double *cell_lambda, const double *cell_mu,
                              double out[3]);
 
+/* The remaining functionals of the reference's statistics (pfm_postproc.hip).  Same contract as pfm_functionals: they
+ * read the node state last given to pfm_state_set / pfm_state_set_solution (after the ghost import), return THIS RANK's
+ * part (the caller does Utilities::MPI::sum and the scaling the reference applies after it), are ordered behind earlier
+ * work on the context's stream and synchronous with host outputs.  Deterministic fixed-order reductions: repeated calls
+ * are bitwise identical.  PFM_ERR_BAD_ARG, with nothing launched, before pfm_set_params and on bad input (a cell out of
+ * range, a face >= 2 dim, lines not finite and strictly ascending, a negative count or eps, a NULL output). */
+
+/* compute_load (cracks.cc:3726-3790): out[d] = sum over the given (cell, face) pairs of
+ *   int_face (lambda tr(E) I + 2 mu E) n dA,   E = sym grad u,  QGauss<dim-1>(3),  MappingQ1,  outward normal,
+ * with lambda, mu = the GLOBAL coefficients of pfm_set_params even when per-cell ones are set (as the reference,
+ * cracks.cc:3776-3777).  Faces in deal.II numbering: 2 d = lower, 2 d + 1 = upper face of reference axis d.  out has dim
+ * entries, the raw vector: the sign flips of cracks.cc:3793-3815 are the caller's.  A deal.II host passes the faces of its
+ * owned cells with cell->face(f)->at_boundary() && boundary_id() == 3. */
+int pfm_face_load(pfm_ctx *ctx, int64_t n_faces, const int32_t *cells, const uint8_t *faces, double *out);
+
+/* compute_cod(lines[i]) for all lines at once (cracks.cc:3453-3550) over the cells with cell_owned[cell] != 0 (NULL =
+ * every local cell): a face of such a cell matches line x when
+ *   not (center_x - diameter > x), not (center_x + diameter < x), |n(q0) . e_x| >= 0.5, x - eps < q0_x < x + eps
+ * (q0 = face quadrature point 0), and
+ *   cod[i]     = sum over the faces matching lines[i] of int_face 0.5 u . grad(phi) dA   (BEFORE the /2 and the MPI sum of
+ *                cracks.cc:3538-3539: interior faces are counted from both cells, as in the reference)
+ *   n_faces[i] = number of those faces (the caller returns -1e300 when the global count is 0).
+ * A face may match several lines.  lines: strictly ascending (the reference's x_i = -1.5 + i / 256, cracks.cc:3716-3720,
+ * with eps = 1e-8).  The (line, cell, face) list of the first call is cached in the context for the same lines, eps and
+ * mask: later calls only evaluate the faces. */
+int pfm_cod_lines(pfm_ctx *ctx, const uint8_t *cell_owned, int n_lines, const double *lines, double eps, double *cod,
+                  int64_t *n_faces);
+
+/* VectorTools::integrate_difference(..., ExactPhiSneddon(alpha_eps), QGauss<dim>(3), L2_norm, phi only) (cracks.cc:4495-4516,
+ * 418-450; exact phi = 1 - exp(-dist / alpha_eps), dist = distance to the segment [-1, 1] x {0}, alpha_eps of pfm_set_params):
+ * *sum_sq = sum over the cells with cell_owned[cell] != 0 (NULL = all) of int_cell (phi_h - phi_exact)^2 dx, in double.
+ * The caller takes the root of the MPI sum.  The reference keeps every cell's error in a Vector<float>: its printed
+ * phi_L2_error carries a float rounding (about 1e-7 relative) that this sum does not. */
+int pfm_sneddon_phi_error(pfm_ctx *ctx, const uint8_t *cell_owned, double *sum_sq);
+
 #ifdef __cplusplus
 }
 #endif
