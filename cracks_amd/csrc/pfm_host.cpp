@@ -3760,10 +3760,10 @@ extern "C"
         if (hipMemsetAsync(c->cv.patch_count, 0, sizeof(int), c->stream) != hipSuccess)
           return fail(c, PFM_ERR_HIP, "patch list reset");
       }
-    // 2-D boxes: the two launches of k_cart2d_cells (displacement rows | phase-field rows) next to each other
-    // (measured: 0.262 -> 0.259 ms of kernel time at 1000^2, nothing for the caller after the fork and the join: off by default)
-    static const bool cart2d_forked = getenv("PFM_CART2D_FORKED") != nullptr && getenv("PFM_CART2D_ONE_LAUNCH") == nullptr;
-    const bool fork = cart && !residual_only && phase == 0 && (pair || (c->v.dim == 2 && cart2d_forked) || getenv("PFM_SIDE_STREAM"));
+    // 2-D boxes never fork: the second launch of k_cart2d_cells (phase-field rows) reads the mean |diagonal| the first one
+    // leaves in CartView::cell_avg, so it must follow it on the same stream.  (The fork was measured at 0.262 -> 0.259 ms of
+    // kernel time at 1000^2 and was off by default; with an event between the launches nothing of that overlap is left.)
+    const bool fork = cart && !residual_only && phase == 0 && (pair || (c->v.dim != 2 && getenv("PFM_SIDE_STREAM")));
     if (fork)
       {
         if (!c->side_stream)

@@ -35,3 +35,27 @@ def linf_scaled(a, b) -> float:
     a = np.asarray(a)
     b = np.asarray(b)
     return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
+
+
+def exchange_ghosts(lps, ctxs, dim: int):
+    """Ghost import of a partition whose contexts all live on one device, without a communicator: every rank packs what
+    its peers need with one launch (pfm_halo_pack_all) and the messages are copied into the receivers' buffers, laid out
+    as pfm_halo_unpack_all reads them (per peer, field-major, ``dim + 3`` doubles per node).  Returns the receive buffers;
+    unpacking them is the caller's."""
+    import torch
+
+    rec = dim + 3
+    recv = [torch.zeros(int(lp.recv_ptr[-1]) * rec, dtype=torch.float64, device="cuda") for lp in lps]
+    for r, lp in enumerate(lps):
+        send = torch.empty(int(lp.send_ptr[-1]) * rec, dtype=torch.float64, device="cuda")
+        if send.numel():
+            ctxs[r].halo_pack_all(send.data_ptr())
+        torch.cuda.synchronize()
+        for k, s in enumerate(lp.peers):
+            ko = lps[s].peers.index(r)
+            o0, o1 = int(lp.send_ptr[k]) * rec, int(lp.send_ptr[k + 1]) * rec
+            assert int(lps[s].recv_ptr[ko + 1] - lps[s].recv_ptr[ko]) * rec == o1 - o0
+            q0 = int(lps[s].recv_ptr[ko]) * rec
+            recv[s][q0:q0 + (o1 - o0)] = send[o0:o1]
+    torch.cuda.synchronize()
+    return recv

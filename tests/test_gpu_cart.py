@@ -546,22 +546,28 @@ def test_residual_kernels_with_planes_by_transfer_agree(n, het, monkeypatch):
     assert linf_scaled(rx, r.residual_pde) < TOL and linf_scaled(tx, r.residual_total) < TOL
 
 
-@pytest.mark.parametrize("blocked", [True, False])
-def test_cart2d_launch_variants_agree(blocked, monkeypatch):
-    """k_cart2d_cells: one launch per row group (default; the mean |diagonal| of a block with constrained rows goes from
-    the first launch to the second through CartView::cell_avg, the structurally zero (u,phi) block is cleared by a fill
-    in front of them), the same without the fill, and the single launch of round 5 write the same bits -- on a box with
-    Dirichlet lines, an active set and dead zones where diagonal entries vanish (the placeholder needs the mean)."""
-    c = box_case(2, (45, 31), -10.0, 10.0, blocked, monolithic=True)
+def dead_zone(c):
+    """kappa = 0 and both old phase fields zero on x < 0: element diagonals vanish in whole cells, and the constrained rows
+    there (Dirichlet lines, every fifth phase-field dof in the active set) take deal.II's mean-|diagonal| placeholder."""
     c.params.constant_k = 0.0
     node, comp = c.layout.node_comp_of_dof()
-    is_phi = comp == 2
+    is_phi = comp == c.mesh.dim
     dead = c.mesh.coords[node[is_phi]][:, 0] < 0.0
     o = c.old.copy()
     o[np.nonzero(is_phi)[0][dead]] = 0.0
     c.old, c.oldold = o, o.copy()
     phi_dofs = np.nonzero(is_phi)[0]
     c.cu = M.update_constraints(c.mesh, c.layout, M.sneddon_dirichlet_dofs(c.mesh, c.layout), phi_dofs[::5])
+    return c
+
+
+@pytest.mark.parametrize("blocked", [True, False])
+def test_cart2d_launch_variants_agree(blocked, monkeypatch):
+    """k_cart2d_cells: one launch per row group (default; the mean |diagonal| of a block with constrained rows goes from
+    the first launch to the second through CartView::cell_avg, the structurally zero (u,phi) block is cleared by a fill
+    in front of them), the same without the fill, and the single launch of round 5 write the same bits -- on a box with
+    Dirichlet lines, an active set and dead zones where diagonal entries vanish (the placeholder needs the mean)."""
+    c = dead_zone(box_case(2, (45, 31), -10.0, 10.0, blocked, monolithic=True))
     ctx = make_context(c)
     assert ctx.kernel_path == 1
 
@@ -577,6 +583,47 @@ def test_cart2d_launch_variants_agree(blocked, monkeypatch):
     monkeypatch.delenv("PFM_CART2D_NO_FILL")
     monkeypatch.delenv("PFM_CART2D_ONE_LAUNCH")
     _full(c, path=1)
+
+
+def test_cart2d_forked_environment_keeps_one_stream(tmp_path):
+    """PFM_CART2D_FORKED=1 and PFM_SIDE_STREAM=1 once put the second launch of k_cart2d_cells (phase-field rows) on a side
+    stream next to the first, which writes the mean |diagonal| the second reads (CartView::cell_avg), with no event between
+    them.  Both switches are read once per process: under each, the dead-zone box of test_cart2d_launch_variants_agree
+    must give the default's bits, in both layouts, as it is and with G_c = 0 and no displacement on y > 0 -- there the
+    (phi,phi) element diagonal vanishes as well and the phase-field rows take their placeholder from cell_avg."""
+    import os
+    import subprocess
+    import sys
+
+    script = tmp_path / "run.py"
+    script.write_text(
+        "import sys, numpy as np\n"
+        f"sys.path[:0] = [{os.path.dirname(os.path.dirname(os.path.abspath(__file__)))!r}, {os.path.dirname(os.path.abspath(__file__))!r}]\n"
+        "import test_gpu_cart as T\n"
+        "from gpu_util import make_context\n"
+        "out = []\n"
+        "for blocked, flat in ((True, False), (False, False), (True, True), (False, True)):\n"
+        "    c = T.dead_zone(T.box_case(2, (45, 31), -10.0, 10.0, blocked, monolithic=True))\n"
+        "    if flat:\n"
+        "        c.params.G_c, c.params.gamma_penal = 0.0, 0.0\n"
+        "        node, comp = c.layout.node_comp_of_dof()\n"
+        "        c.sol[(comp < 2) & (c.mesh.coords[node][:, 1] > 0.0)] = 0.0\n"
+        "    ctx = make_context(c)\n"
+        "    assert ctx.kernel_path == 1\n"
+        "    values, res, _ = ctx.assemble_host(c.sol, c.old, c.oldold, False)\n"
+        "    out += [np.asarray(v) for v in values] + [res]\n"
+        "np.save(sys.argv[1], np.concatenate(out))\n")
+    keys = ("PFM_CART2D_FORKED", "PFM_SIDE_STREAM", "PFM_CART2D_ONE_LAUNCH", "PFM_CART2D_NO_FILL")
+    got = {}
+    for tag, env in (("default", {}), ("forked", {"PFM_CART2D_FORKED": "1"}), ("side", {"PFM_SIDE_STREAM": "1"})):
+        f = tmp_path / f"{tag}.npy"
+        e = {k: v for k, v in os.environ.items() if k not in keys}
+        e.update(env)
+        subprocess.run([sys.executable, str(script), str(f)], check=True, env=e, timeout=600)
+        got[tag] = np.load(f)
+    for tag in ("forked", "side"):
+        assert got[tag].shape == got["default"].shape
+        assert np.array_equal(got[tag].view(np.int64), got["default"].view(np.int64)), tag
 
 
 def test_bench_reports_the_config5_standin():
