@@ -272,6 +272,19 @@ class Context:
         """measurement: 1 / 2 = only the first / second half of the overlapped assembly, 0 = all."""
         self._check(self.lib.pfm_ctx_force_phase(self._h, phase), "pfm_ctx_force_phase")
 
+    # marching kernels of pfm_ctx_force_zchunk / pfm_ctx_zchunk
+    ZC_UU3, ZC_PHI4, ZC_RES3, ZC_RES2 = 0, 1, 2, 3
+
+    def force_zchunk(self, kernel: int, planes: int):
+        """tests and tuning: z-chunk length of a marching kernel (ZC_*), clamped to the plane count; 0 = the default."""
+        self._check(self.lib.pfm_ctx_force_zchunk(self._h, kernel, planes), "pfm_ctx_force_zchunk")
+
+    def zchunk(self, kernel: int) -> int:
+        """the chunk length the next launch of the marching kernel over the context's box uses."""
+        p = C.c_int(0)
+        self._check(self.lib.pfm_ctx_zchunk(self._h, kernel, C.byref(p)), "pfm_ctx_zchunk")
+        return int(p.value)
+
     @property
     def device_bytes(self) -> int:
         return int(self.lib.pfm_ctx_device_bytes(self._h))

@@ -28,7 +28,7 @@ EXPORTS = [
     "pfm_halo_register", "pfm_halo_pack", "pfm_halo_unpack", "pfm_halo_pack_all", "pfm_halo_unpack_all",
     "pfm_assemble_device", "pfm_assemble_nl_residual_device",
     "pfm_sync_status", "pfm_assemble", "pfm_host_register", "pfm_host_unregister", "pfm_values_to_host", "pfm_ctx_kernel_path", "pfm_ctx_force_path", "pfm_ctx_overlay_info", "pfm_ctx_force_phase",
-    "pfm_ctx_device_bytes", "pfm_timing_enable", "pfm_kernel_time_ms", "pfm_kernel_times_ms",
+    "pfm_ctx_force_zchunk", "pfm_ctx_zchunk", "pfm_ctx_device_bytes", "pfm_timing_enable", "pfm_kernel_time_ms", "pfm_kernel_times_ms",
     # include/pfm_newton.h
     "pfm_diag_mass_device", "pfm_active_set_device", "pfm_get_constraints", "pfm_functionals",
     "pfm_functionals_material", "pfm_residual_norms", "pfm_face_load", "pfm_cod_lines", "pfm_sneddon_phi_error",
@@ -128,6 +128,8 @@ def load():
     lib.pfm_ctx_kernel_path.argtypes = [vp]
     lib.pfm_ctx_force_path.argtypes = [vp, i32]
     lib.pfm_ctx_overlay_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    lib.pfm_ctx_force_zchunk.argtypes = [vp, i32, i32]
+    lib.pfm_ctx_zchunk.argtypes = [vp, i32, C.POINTER(i32)]
     lib.pfm_timing_enable.argtypes = [vp, i32]
     lib.pfm_kernel_time_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.pfm_kernel_times_ms.argtypes = [vp, vp, i32, C.POINTER(C.c_int)]

@@ -1660,6 +1660,41 @@ namespace pfm
     return best;
   }
 
+  namespace
+  {
+    int env_planes(const char *name)
+    {
+      const char *s = getenv(name);
+      return s ? atoi(s) : 0;
+    }
+  } // namespace
+
+  int zchunk_of(const CartView &cv, int kernel, long long tiles, int planes)
+  {
+    // the tuning variables, once per process: nothing is read from the environment per launch
+    static const int env[PFM_ZC_KERNELS] = {env_planes("PFM_UU_ZC"), env_planes("PFM_PHI_ZC"), env_planes("PFM_RES_ZC"),
+                                            env_planes("PFM_RES2_ZC")};
+    // the model's range and resident workgroups per CU of each kernel (k_cart_residual2m: one wave per workgroup)
+    static constexpr int zmin[PFM_ZC_KERNELS] = {8, 6, 4, 4}, zmax[PFM_ZC_KERNELS] = {48, 48, 24, 64}, per_cu[PFM_ZC_KERNELS] = {2, 2, 2, 8};
+    const int forced = cv.zc_force[kernel] > 0 ? cv.zc_force[kernel] : env[kernel];
+    if (forced > 0)
+      return std::max(1, std::min(forced, planes));
+    return choose_zchunk(tiles, planes, zmin[kernel], zmax[kernel], per_cu[kernel]);
+  }
+
+  int cart_res3_zchunk(const CartView &cv)
+  {
+    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
+    const int ntx = (OWX + RNX - 1) / RNX, nty = (OWY + RNY - 1) / RNY;
+    return zchunk_of(cv, PFM_ZC_RES3, (long long)ntx * nty, OWZ);
+  }
+
+  int cart_res2_zchunk(const CartView &cv) // chunks of node rows, one wave per R2N nodes of a row
+  {
+    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1;
+    return zchunk_of(cv, PFM_ZC_RES2, (OWX + R2N - 1) / R2N, OWY);
+  }
+
   // the conditions of `rows_residual` in launch_assemble_cart + what the pair needs: the default (u,u) kernel
   bool cart_jacobian_pair(const DevView &v, const CartView &cv, const pfm_params &p, int residual_only, int phase)
   {
@@ -1706,8 +1741,7 @@ namespace pfm
     if (v.dim == 2)
       {
         const int ntx = (int)((OWX + R2N - 1) / R2N);
-        static const int zc_force = getenv("PFM_RES2_ZC") ? atoi(getenv("PFM_RES2_ZC")) : 0; // tuning only
-        const int zc = zc_force > 0 ? zc_force : choose_zchunk(ntx, (int)OWY, 4, 64, 8);
+        const int zc = cart_res2_zchunk(cv);
         const unsigned nw = (unsigned)(ntx * ((OWY + zc - 1) / zc));
         if (nw == 0)
           ;
@@ -1720,8 +1754,7 @@ namespace pfm
       {
         const int ntx = (int)((OWX + RNX - 1) / RNX), nty = (int)((OWY + RNY - 1) / RNY);
         // chunks of z-planes: fill the dispatch rounds of the chip (2 workgroups per CU) at few redundant layers
-        static const int zc_force = getenv("PFM_RES_ZC") ? atoi(getenv("PFM_RES_ZC")) : 0; // tuning only
-        const int zc = zc_force > 0 ? zc_force : choose_zchunk((long long)ntx * nty, (int)OWZ, 4, 24, 2);
+        const int zc = cart_res3_zchunk(cv);
         const int nch = (int)((OWZ + zc - 1) / zc);
         const bool listed = cv.tile_sel == 2 && cv.bnd_res3 != nullptr && cv.zc_res3 == zc;
         const unsigned nt = listed ? (unsigned)cv.n_bnd_res3 : (unsigned)(ntx * nty * nch);
@@ -1771,8 +1804,7 @@ namespace pfm
     out.clear();
     const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
     const int ntx = (OWX + RNX - 1) / RNX, nty = (OWY + RNY - 1) / RNY;
-    static const int zc_force = getenv("PFM_RES_ZC") ? atoi(getenv("PFM_RES_ZC")) : 0; // as launch_assemble_cart
-    zc = zc_force > 0 ? zc_force : choose_zchunk((long long)ntx * nty, OWZ, 4, 24, 2);
+    zc = cart_res3_zchunk(cv); // as launch_assemble_cart
     const int nch = (OWZ + zc - 1) / zc;
     for (int ch = 0; ch < nch; ++ch)
       for (int tiy = 0; tiy < nty; ++tiy)

@@ -1716,6 +1716,13 @@ namespace pfm
     return hipMemcpyAsync(d_scal, &Sh, sizeof(MatScal), hipMemcpyHostToDevice, s) == hipSuccess ? PFM_OK : PFM_ERR_HIP;
   }
 
+  int cart_phi4_zchunk(const CartView &cv)
+  {
+    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
+    const int ntx = (OWX + PN - 1) / PN, nty = (OWY + PN - 1) / PN;
+    return zchunk_of(cv, PFM_ZC_PHI4, (long long)ntx * nty, OWZ);
+  }
+
   int launch_cart_phi4(const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values, hipStream_t s,
                        const void *d_scal, double *res_pde)
   {
@@ -1728,10 +1735,9 @@ namespace pfm
     const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
     const int ntx = (OWX + PN - 1) / PN, nty = (OWY + PN - 1) / PN;
     // z-chunks: one extra cell layer per chunk is recomputed; keep that below ~4 % while filling the chip
-    static const int zc_force = getenv("PFM_PHI_ZC") ? atoi(getenv("PFM_PHI_ZC")) : 0; // tuning only
     // (round 6: chunks of up to 48 planes as in k_cart_uu3 -- at 216^3 the model picks 31 = 217 / 7, seven equal chunks per
     // column instead of ten of 22 with a short last one: 10.7 -> 10.4 ms per assembly, profiles/r06/zc_scan.txt)
-    const int zc_abs = zc_force > 0 ? zc_force : choose_zchunk((long long)ntx * nty, OWZ, 6, 48, 2);
+    const int zc_abs = cart_phi4_zchunk(cv);
     const int nch = (OWZ + zc_abs - 1) / zc_abs;
     static const bool no_prio = getenv("PFM_NO_PRIO") != nullptr; // A/B runs only
     const int zc = no_prio ? -zc_abs : zc_abs;

@@ -1145,8 +1145,7 @@ namespace pfm
     const bool listed = cv.tile_sel == 2 && cv.bnd_uu3 != nullptr;
     // planes per workgroup: the interior / boundary launches of an overlapped assembly select tiles plane by plane (zc = 1:
     // every plane through the prologue's register loads, as in rounds 1-4); otherwise chunks that fill the dispatch rounds
-    static const int zc_force = getenv("PFM_UU_ZC") ? atoi(getenv("PFM_UU_ZC")) : 0; // tuning only
-    const int zc = cv.tile_sel != 0 ? 1 : (zc_force > 0 ? std::min(zc_force, OWZ) : choose_zchunk((long long)ntx * nty, OWZ, 8, 48, 2));
+    const int zc = cv.tile_sel != 0 ? 1 : cart_uu3_zchunk(cv);
     const int nch = (OWZ + zc - 1) / zc;
     const unsigned nb = listed ? (unsigned)cv.n_bnd_uu3 : (unsigned)(ntx * nty * nch);
     if (nb == 0)
@@ -1227,6 +1226,13 @@ namespace pfm
 #undef PFM_UU3
     return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
   }
+  int cart_uu3_zchunk(const CartView &cv)
+  {
+    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
+    const int ntx = (OWX + T3X - 1) / T3X, nty = (OWY + T3Y - 1) / T3Y;
+    return zchunk_of(cv, PFM_ZC_UU3, (long long)ntx * nty, OWZ);
+  }
+
   void cart_uu3_boundary_tiles(const CartView &cv, std::vector<int32_t> &out)
   {
     out.clear();

@@ -3642,6 +3642,27 @@ extern "C"
     return PFM_OK;
   }
 
+  // pfm_ctx_force_zchunk of the residual kernel: its list holds tiles of chunks of the old length.  Freed here, made again
+  // for the new length by the next assembly that runs a half (assemble_impl)
+  static void drop_overlap_lists(pfm_ctx *c)
+  {
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize(); // a queued launch of phase 2 may still read them
+    const std::pair<const int32_t *, int> lists[2] = {{c->cv.bnd_uu3, c->cv.n_bnd_uu3}, {c->cv.bnd_res3, c->cv.n_bnd_res3}};
+    for (const auto &l : lists)
+      {
+        auto it = std::find(c->allocs.begin(), c->allocs.end(), (void *)l.first);
+        if (!l.first || it == c->allocs.end())
+          continue;
+        c->allocs.erase(it);
+        c->device_bytes -= (int64_t)sizeof(int32_t) * std::max(l.second, 1); // (an empty list was uploaded as one entry)
+        (void)hipFree((void *)l.first);
+      }
+    c->cv.bnd_uu3 = c->cv.bnd_res3 = nullptr;
+    c->cv.n_bnd_uu3 = c->cv.n_bnd_res3 = c->cv.zc_res3 = 0;
+    c->overlap_lists_ready = false;
+  }
+
   // phase 0: the whole assembly (pfm_assemble_device).  phases 1, 2: the two halves of pfm_assemble_overlapped -- 1 = what
   // reads no ghost node, 2 = the rest; timing events bracket 1..2 together.
   static int assemble_impl(pfm_ctx *c, int residual_only, double *const *d_values, double *d_res_pde, double *d_res_tot, int phase)
@@ -3656,6 +3677,12 @@ extern "C"
     hipError_t e = hipSuccess;
     const bool split = c->prm.decompose_stress_matrix > 0 && c->prm.timestep_number > 0; // cracks.cc:2294
     const bool cart = c->kernel_path == 1 && !split && (residual_only || cart_matrix_supported(c->v.dim));
+    if (cart && phase != 0 && !c->overlap_lists_ready)
+      {
+        const int rcl = ensure_overlap_lists(c); // dropped by pfm_ctx_force_zchunk: the lists of the new residual length
+        if (rcl)
+          return rcl;
+      }
     if (!cart && !c->general_ready)
       {
         try
@@ -4046,6 +4073,30 @@ extern "C"
       return PFM_ERR_BAD_ARG;
     c->force_phase = phase;
     return phase ? ensure_overlap_lists(c) : PFM_OK;
+  }
+
+  int pfm_ctx_force_zchunk(pfm_ctx *c, int kernel, int planes)
+  {
+    if (!c || kernel < 0 || kernel >= PFM_ZC_KERNELS || planes < 0)
+      return PFM_ERR_BAD_ARG;
+    c->cv.zc_force[kernel] = planes;
+    for (auto &lv : c->levels3)
+      lv.cv.zc_force[kernel] = planes;
+    if (kernel == PFM_ZC_RES3 && c->overlap_lists_ready)
+      drop_overlap_lists(c); // the residual's boundary list is one of chunks of its length (the (u,u) list goes with it)
+    return PFM_OK;
+  }
+
+  int pfm_ctx_zchunk(const pfm_ctx *c, int kernel, int *planes)
+  {
+    if (!c || kernel < 0 || kernel >= PFM_ZC_KERNELS || !planes)
+      return PFM_ERR_BAD_ARG;
+    if (!c->cart_ok || (kernel == PFM_ZC_RES2) != (c->v.dim == 2))
+      return PFM_ERR_UNSUPPORTED;
+    // the launchers' own helpers, on the context's box
+    *planes = kernel == PFM_ZC_UU3 ? cart_uu3_zchunk(c->cv) : kernel == PFM_ZC_PHI4 ? cart_phi4_zchunk(c->cv)
+            : kernel == PFM_ZC_RES3 ? cart_res3_zchunk(c->cv) : cart_res2_zchunk(c->cv);
+    return PFM_OK;
   }
 
   // Ghost import NEXT TO the cell work instead of in front of it (cracks.cc:2147-2154 against 2200-2437): after the

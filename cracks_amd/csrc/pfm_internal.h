@@ -118,6 +118,17 @@ namespace pfm
     int tile_sel;                     // 0: every tile; 1: only tiles that read no ghost node ("interior"); 2: only the
                                       // others -- the two launches of pfm_assemble_overlapped, between which the ghost
                                       // import lands (cracks.cc:2147-2154 next to the cell loop instead of in front of it)
+    int zc_force[4];                  // pfm_ctx_force_zchunk, per marching kernel (PFM_ZC_*): 0 = the default length
+                                      // (tuning variable, else the dispatch model), > 0 = that many planes (host side only)
+  };
+  // the marching kernels of the cartesian family, indices of CartView::zc_force (pfm_ctx_force_zchunk)
+  enum
+  {
+    PFM_ZC_UU3 = 0,  // k_cart_uu3
+    PFM_ZC_PHI4 = 1, // k_cart_phi4
+    PFM_ZC_RES3 = 2, // k_cart_residual3x / 3d / 3
+    PFM_ZC_RES2 = 3, // k_cart_residual2m
+    PFM_ZC_KERNELS = 4
   };
 
   // does the node range [lo, hi] (tile + one-node halo, lattice indices along `axis`) contain a ghost node?  Ghost nodes
@@ -206,6 +217,16 @@ namespace pfm
   // z-chunk length of a marching kernel: `tiles` columns, `planes` node planes, one redundant cell layer per chunk,
   // `per_cu` resident workgroups per CU.  Maximises (fill of the last dispatch round) x (useful layers per chunk).
   int choose_zchunk(long long tiles, int planes, int zc_min, int zc_max, int per_cu);
+  // the chunk length of marching kernel `kernel` (PFM_ZC_*) over `tiles` columns of `planes` planes, as every launcher of
+  // it computes it: cv.zc_force, else the tuning variable (PFM_UU_ZC, PFM_PHI_ZC, PFM_RES_ZC, PFM_RES2_ZC; read once),
+  // else choose_zchunk in the kernel's range.  Forced lengths are clamped to [1, max(planes, 1)].
+  int zchunk_of(const CartView &cv, int kernel, long long tiles, int planes);
+  // ... over the owned box of cv, each with its kernel's tile count; k_cart_uu3 marches single planes instead in the two
+  // halves of an overlapped assembly (launch_cart_uu3)
+  int cart_uu3_zchunk(const CartView &cv);
+  int cart_phi4_zchunk(const CartView &cv);
+  int cart_res3_zchunk(const CartView &cv);
+  int cart_res2_zchunk(const CartView &cv);
   // XCD-aware launch: workgroup i runs on XCD i % 8.  The kernels are launched with a grid rounded up to a multiple
   // of 8 and map blockIdx to (blockIdx % 8) * (grid / 8) + blockIdx / 8, so that every XCD works on one contiguous
   // range of tiles (neighbouring tiles share their halo in that XCD's L2) and the slow boundary tiles are spread over

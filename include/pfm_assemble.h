@@ -262,6 +262,17 @@ int pfm_ctx_overlay_info(const pfm_ctx *ctx, int64_t *n_patch_rows, int64_t *n_g
 /* measurement only: 1 / 2 make pfm_assemble_device run only the first / second half of pfm_assemble_overlapped (the work
  * that reads no ghost node / the rest), 0 restores the whole assembly: how much work hides the ghost import */
 int pfm_ctx_force_phase(pfm_ctx *ctx, int phase);
+/* tests and tuning: the z-chunk length of a marching kernel of the cartesian family, whose workgroups each march through
+ * one chunk of node planes (2-D: node rows) -- kernel 0 = k_cart_uu3, 1 = k_cart_phi4, 2 = the 3-D residual kernels
+ * (k_cart_residual3x / 3d / 3), 3 = k_cart_residual2m.  planes = 0 restores the default (PFM_UU_ZC, PFM_PHI_ZC, PFM_RES_ZC,
+ * PFM_RES2_ZC if set, else the launch-time model); planes > 0 forces that length, clamped to the plane count of every
+ * lattice the kernel runs on (the level lattices of a 3-D overlay included).  A null context, a kernel outside 0..3 or
+ * planes < 0: PFM_ERR_BAD_ARG. */
+int pfm_ctx_force_zchunk(pfm_ctx *ctx, int kernel, int planes);
+/* the length the next launch of `kernel` over the context's own box uses, from the launchers' own helper (not in the
+ * two halves of pfm_assemble_overlapped, where k_cart_uu3 marches single planes).  PFM_ERR_UNSUPPORTED: the context has
+ * no box, or the kernel does not run in its dimension. */
+int pfm_ctx_zchunk(const pfm_ctx *ctx, int kernel, int *planes);
 int64_t pfm_ctx_device_bytes(const pfm_ctx *ctx);
 
 #ifdef __cplusplus

@@ -69,6 +69,8 @@ def test_bad_arguments_are_rejected_without_a_gpu(lib):
     assert lib.pfm_ctx_create(C.byref(h), C.byref(d), 0) == 1
     assert lib.pfm_set_params(None, None) == 1
     assert lib.pfm_assemble_device(None, 0, None, None, None) == 1
+    assert lib.pfm_ctx_force_zchunk(None, 0, 8) == 1
+    assert lib.pfm_ctx_zchunk(None, 0, C.byref(C.c_int())) == 1
     assert lib.pfm_ctx_destroy(None) == 0
     assert lib.pfm_last_error(None) == b"null context"
 

@@ -2,8 +2,10 @@
 
 The oracle cannot assemble 10^7 cells in test time, but a row only depends on the 8 cells around its node: a few hundred
 rows -- at the mesh faces, at the seams of the (u,u) tiles (8 x 4 nodes), the phase-field tiles (7 x 7), the residual
-tiles (15 x 15), around the z-chunk boundaries of the marching kernels, plus random interior nodes -- are compared with the
-oracle run on the sub-mesh of exactly those cells.  The CSR offsets of the rows are recomputed here from the lattice
+tiles (15 x 15), on both sides of every z-chunk seam of the lengths the context reports for its marching kernels
+(pfm_ctx_zchunk: 31 planes for k_cart_uu3 / k_cart_phi4 and 22 for the residual at 216^3 on 256 CUs), each seam plane at
+columns on tile seams, plus random interior nodes -- are compared with the oracle run on the sub-mesh of exactly those
+cells.  The CSR offsets of the rows are recomputed here from the lattice
 (ascending columns), so the test also pins the pattern the library reports at this size.
 
 PFM_FULLSIZE_N overrides the edge length (default 216)."""
@@ -54,14 +56,23 @@ def test_rows_of_the_bench_mesh_match_the_oracle():
     rng = np.random.default_rng(216)
     ax = _axis_samples(n)
     zc = set(ax)
-    for c in (12, 18, 24, 25):  # chunk seams of the marching kernels whatever length the dispatch model chose
+    for c in (12, 18, 24, 25):  # chunk seams of lengths earlier dispatch models chose
         zc |= {k for k in (c - 1, c, c + 1, 2 * c, 2 * c + 1) if k <= n}
+    # the seams of the lengths these launches use (k_cart_uu3, k_cart_phi4, the residual kernels): the last plane of a
+    # chunk, the first of the next one and the one behind it
+    lens = {asm.ctx.zchunk(k) for k in (asm.ctx.ZC_UU3, asm.ctx.ZC_PHI4, asm.ctx.ZC_RES3)}
+    seams = {k for L in lens for m in range(1, n // L + 1) for k in (m * L - 1, m * L, m * L + 1) if k <= n}
+    zc |= seams
     pts = set()
     for _ in range(260):
         pts.add((int(rng.choice(ax)), int(rng.choice(ax)), int(rng.choice(sorted(zc)))))
     for _ in range(120):
         pts.add(tuple(int(x) for x in rng.integers(0, NP, 3)))
+    for k in seams:  # every seam plane at columns on tile seams in x and y (uu3: 8 x 4 nodes, phi4: 7 x 7, residual: 15 x 15)
+        for i, j in ((7, 3), (8, 4), (15, 7)):
+            pts.add((i, j, k))
     pts = sorted(pts)
+    assert seams <= {k for _, _, k in pts}
     S = np.array([i + NP * (j + NP * k) for i, j, k in pts], np.int64)
 
     # ---- sub-mesh of the cells around the sampled nodes
@@ -136,7 +147,8 @@ def test_rows_of_the_bench_mesh_match_the_oracle():
         worst = max(worst, np.abs(fetch(res_d, gd) - r_res.residual_pde[ld]).max())
         worst = max(worst, np.abs(fetch(tot_d, gd) - r_res.residual_total[ld]).max())
     scale = max(1.0, float(np.abs(r.values).max()))
-    print(f"full size {n}^3: {len(pts)} rows, {cell_ids.size} oracle cells, max |GPU - oracle| = {worst:.3e} (scale {scale:.2e})")
+    print(f"full size {n}^3: {len(pts)} rows, {len(seams)} seam planes of chunk lengths {sorted(lens)}, {cell_ids.size} oracle cells, "
+          f"max |GPU - oracle| = {worst:.3e} (scale {scale:.2e})")
     assert worst < 1e-12 * scale
 
 
