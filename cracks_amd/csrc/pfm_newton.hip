@@ -115,7 +115,16 @@ namespace pfm
               const double old_value = old_solution[idx], new_value = solution[idx];
               const double gap = new_value - old_value;
               const int cyc = cycle_counter[P];
-              const bool inactive = (residual_total[idx] / mass[P] + cconst * gap <= 0.0) && cyc < 5; // cracks.cc:2868-2872
+              bool crit_le_0;
+              {
+                // the criterion is rounded as written (quotient, product, sum; no fma): at a tie a contracted
+                // fma(c, gap, r / m) decides differently from the reference and from newton.py's numpy statement
+#pragma clang fp contract(off)
+                const double q = residual_total[idx] / mass[P];
+                const double cg = cconst * gap;
+                crit_le_0 = q + cg <= 0.0;
+              }
+              const bool inactive = crit_le_0 && cyc < 5; // cracks.cc:2868-2872
               if (!inactive)
                 {
                   cycling = cyc >= 5;

@@ -30,6 +30,9 @@ int pfm_diag_mass_device(pfm_ctx *ctx, double *d_mass);
  * hanging nodes (cracks.cc:2888-2890), for the owned nodes of this rank:
  *   a phase-field dof that is not hanging becomes ACTIVE unless
  *        residual_total/diag_mass + c (phi - phi_old) <= 0  and  cycle_counter < 5;
+ *   rounding: the criterion is fl(fl(residual_total / diag_mass) + fl(c fl(phi - phi_old))) in double, every operation
+ *   rounded on its own (no fused multiply-add), as the reference and an unfused host statement evaluate it, so that
+ *   the decisions agree at ties, -0.0 and NaN (NaN: active) included;
  *   an active dof gets phi := phi_old and a homogeneous constraint line (bit `dim` of the node's flag byte in
  *   the context, i.e. exactly what pfm_set_constraints would have been given); a dof that leaves the set
  *   increments its cycle counter.

@@ -1248,6 +1248,9 @@ extern "C"
   // written over dofs (the reference's cell loop visits every phase-field dof once: "already processed").
   //   is_phi / hanging: per dof flags;  active: in = active_set_old, out = active_set
   //   counts[0] = active dofs, counts[1] = cycling dofs, counts[2] = 1 if the set changed
+  // fp-contract off for this function only: the criterion is rounded as the reference writes it (quotient, product,
+  // sum), which is also newton.py's numpy statement; -march=native would otherwise fuse c * gap into the add
+  __attribute__((optimize("fp-contract=off")))
   int oracle_active_set(int32_t n_dofs, const uint8_t *is_phi, const uint8_t *hanging, const double *residual_relevant,
                         const double *diag_mass_relevant, double c, double *solution, const double *old_solution_relevant,
                         int32_t *cycle_counter, uint8_t *active, int64_t *counts)

@@ -78,6 +78,104 @@ def test_oracle_active_set_matches_harness_logic():
     assert np.array_equal(sol, sol_ref) and np.array_equal(cyc, cyc_ref)
 
 
+# ---- the criterion at its edges: newton.py's unfused numpy statement is the contract (it reproduces the goldens)
+def numpy_active_set(is_phi, hanging, res, mass, c, sol, old, cyc, active):
+    """newton.py's loop body over dofs, every operation rounded on its own.  Returns (active, solution, cycle counter,
+    counts) without touching the inputs."""
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        crit = res / mass + c * (sol - old)
+    cand = is_phi.astype(bool) & ~hanging.astype(bool)
+    act = cand & ~((crit <= 0.0) & (cyc < 5))
+    sol_ref = sol.copy()
+    sol_ref[act] = old[act]
+    cyc_ref = cyc.copy()
+    cyc_ref[active.astype(bool) & ~act] += 1
+    counts = (int(act.sum()), int(np.sum(act & (cyc >= 5))), int(bool(np.any(active.astype(bool) != act))))
+    return act, sol_ref, cyc_ref, counts
+
+
+def _product_error_sign(c, gap):
+    """sign of c * gap - fl(c * gap), exactly"""
+    from fractions import Fraction
+
+    e = Fraction(float(c)) * Fraction(float(gap)) - Fraction(float(c) * float(gap))
+    return (e > 0) - (e < 0)
+
+
+def criterion_edges(c, n_ties=24, seed=3):
+    """Phase-field dof inputs (res, mass, sol, old, cyc, was) at the edges of the criterion, each value crossed with
+    cycle counters 0, 4, 5, 6 and with both previous states.  Among them, exact ties fl(r / m) = -fl(c gap) with m a
+    power of two (the quotient is exact) and a nonzero rounding error of c gap of either sign: unfused, crit is 0
+    (inactive below the cycling threshold); fused, fma(c, gap, r / m) is that error, and only the positive one turns
+    the decision.  Also crit = +0 and -0, NaN and +-Inf residuals, and clear cases on both sides.  Returns the arrays and
+    the mask of the entries where a fused criterion decides differently."""
+    rng = np.random.default_rng(seed)
+    res, mass, sol, old, fused_flips = [], [], [], [], []
+    want = {1: n_ties // 2, -1: n_ties // 2}
+    while want[1] or want[-1]:
+        o = rng.uniform(0.0, 1.0)
+        s = rng.uniform(0.0, 1.0)
+        gap = s - o
+        sg = _product_error_sign(c, gap) if c != 0.0 else 0
+        if sg == 0 or want[sg] == 0:
+            continue
+        want[sg] -= 1
+        m = 2.0 ** int(rng.integers(-12, 3))
+        res.append(-(c * gap) * m)
+        assert res[-1] / m == -(c * gap)
+        mass.append(m)
+        sol.append(s)
+        old.append(o)
+        fused_flips.append(sg > 0)
+    m = 0.125
+    for r, s, o in [(0.0, 0.5, 0.5),            # crit = +0
+                    (-0.0, -0.0, 0.0),          # crit = -0 (-0 / m + c (-0 - 0))
+                    (np.nan, 0.5, 0.25), (np.inf, 0.5, 0.25), (-np.inf, 0.5, 0.25),
+                    (1.0, 0.25, 0.5), (-1.0, 0.5, 0.25),  # r / m = 8 against c gap
+                    (1e-3, 0.5, 0.5), (-1e-3, 0.5, 0.5)]:
+        res.append(r)
+        mass.append(m)
+        sol.append(s)
+        old.append(o)
+        fused_flips.append(False)
+    k = len(res)
+    rep = lambda a: np.tile(np.asarray(a, np.float64), 8)
+    cyc = np.repeat(np.array([0, 4, 5, 6] * 2, np.int32), k)
+    was = np.repeat(np.array([0, 0, 0, 0, 1, 1, 1, 1], np.uint8), k)
+    flips = np.tile(np.asarray(fused_flips), 8) & (cyc < 5)
+    return rep(res), rep(mass), rep(sol), rep(old), cyc, was, flips
+
+
+@pytest.mark.parametrize("c", [10.0, 3.7, 0.0])
+def test_oracle_active_set_criterion_edges_match_unfused_numpy(c):
+    """Ties where a fused multiply-add decides differently, +-0, NaN, +-Inf, c = 0, the cycling threshold from both sides,
+    dofs that leave the set, hanging dofs: the oracle makes numpy's decisions bit for bit."""
+    res, mass, sol, old, cyc, was, flips = criterion_edges(c) if c != 0.0 else criterion_edges(10.0)
+    n = res.size
+    is_phi = np.ones(n, np.uint8)
+    is_phi[::7] = 0  # displacement dofs in between: never touched
+    hanging = np.zeros(n, np.uint8)
+    hanging[3::11] = 1
+    was = was * is_phi * (1 - hanging)  # a constraint line is never on a hanging dof
+    act_ref, sol_ref, cyc_ref, counts_ref = numpy_active_set(is_phi, hanging, res, mass, c, sol, old, cyc, was)
+    if c != 0.0:
+        # the data discriminate: numpy's decision differs from a fused one on entries that stay candidates
+        assert np.any(flips & (is_phi == 1) & (hanging == 0) & ~act_ref)
+    assert np.any((was == 1) & ~act_ref)  # some leave the set
+    assert np.any(act_ref & (cyc >= 5)) and np.any(~act_ref & (is_phi == 1) & (hanging == 0) & (cyc == 4))
+    s, k, a = sol.copy(), cyc.copy(), was.copy()
+    counts = O.active_set(is_phi, hanging, res, mass, c, s, old, k, a)
+    assert counts == counts_ref
+    assert np.array_equal(a.astype(bool), act_ref)
+    assert s.tobytes() == sol_ref.tobytes() and np.array_equal(k, cyc_ref)
+    assert not np.any(a[hanging == 1]) and np.array_equal(k[hanging == 1], cyc[hanging == 1])
+    # the same inputs with the resulting set as the previous one: nothing changes, no counter moves
+    s2, k2, a2 = sol.copy(), cyc.copy(), act_ref.astype(np.uint8)
+    counts = O.active_set(is_phi, hanging, res, mass, c, s2, old, k2, a2)
+    assert counts == counts_ref[:2] + (0,)
+    assert np.array_equal(k2, cyc) and s2.tobytes() == sol_ref.tobytes()
+
+
 # ---------------------------------------------------------------------------------------------- GPU
 def _gpu_assembler(case):
     from cracks_amd.assembler import Assembler, node_flags_from_dof_flags
