@@ -45,7 +45,8 @@ class Context:
         self.dim = mesh.dim
         self.blocked = bool(blocked)
         self.n_nodes = mesh.n_nodes
-        self.n_owned = mesh.n_nodes if n_owned_nodes is None else int(n_owned_nodes)
+        self.n_cells = mesh.n_cells
+        self.n_owned =mesh.n_nodes if n_owned_nodes is None else int(n_owned_nodes)
         self.n_blocks = 4 if blocked else 1
         d = capi.PfmMeshDesc()
         d.dim = mesh.dim
@@ -362,6 +363,57 @@ class Context:
         mp = None if mask is None else capi.np_ptr(mask, np.uint8)
         self._check(self.lib.pfm_sneddon_phi_error(self._h, mp, out), "pfm_sneddon_phi_error")
         return float(out[0])
+
+    # ---- include/pfm_newton.h, mesh adaptation
+    def refine_flags(self, phi_threshold: float = float("nan"), box_lo=None, box_hi=None, max_level: int = -1,
+                     cell_owned: Optional[np.ndarray] = None, cell_level: Optional[np.ndarray] = None):
+        """The refinement indicator of refine_mesh() (cracks.cc:3902-4116) on the node state in the context:
+        ``(flags uint8 [n_cells], n_flagged)`` of this rank.  ``box_lo`` / ``box_hi``: the closed box of the fixed
+        pre-refinement strategies (``dim`` entries, +-inf for open sides; None = no box)."""
+        crit = capi.PfmRefineCriteria()
+        crit.phi_threshold = float(phi_threshold)
+        crit.use_box = 0 if box_lo is None else 1
+        if box_lo is not None:
+            for d in range(self.dim):
+                crit.box_lo[d], crit.box_hi[d] = float(box_lo[d]), float(box_hi[d])
+        crit.max_level = int(max_level)
+        n_cells = self.n_cells
+        mask = None if cell_owned is None else np.ascontiguousarray(cell_owned, np.uint8)
+        level = None if cell_level is None else np.ascontiguousarray(cell_level, np.uint8)
+        for a in (mask, level):
+            if a is not None and a.size != n_cells:
+                raise ValueError("one entry per cell expected")
+        flags = np.zeros(n_cells, np.uint8)
+        n = C.c_int64(0)
+        self._check(self.lib.pfm_refine_flags(self._h, C.byref(crit), None if mask is None else capi.np_ptr(mask, np.uint8),
+                                              None if level is None else capi.np_ptr(level, np.uint8),
+                                              capi.np_ptr(flags, np.uint8), C.byref(n)), "pfm_refine_flags")
+        return flags, int(n.value)
+
+    def min_cell_diameter(self, cell_owned: Optional[np.ndarray] = None) -> float:
+        """``min_cell_diameter`` over this rank's cells (cracks.cc:3824-3835); +inf where no cell is masked."""
+        out = C.c_double(0.0)
+        mask = None if cell_owned is None else np.ascontiguousarray(cell_owned, np.uint8)
+        if mask is not None and mask.size != self.n_cells:
+            raise ValueError("one entry per cell expected")
+        self._check(self.lib.pfm_min_cell_diameter(self._h, None if mask is None else capi.np_ptr(mask, np.uint8), C.byref(out)),
+                    "pfm_min_cell_diameter")
+        return float(out.value)
+
+    def transfer_state(self, dst: "Context", parent_cell, child, src_ptrs: Sequence[int], dst_ptrs: Sequence[int]):
+        """``pfm_state_transfer``: SolutionTransfer::interpolate for refinement (cracks.cc:4137-4159) of the device dof vectors
+        ``src_ptrs`` of this context into ``dst_ptrs`` of ``dst``.  ``parent_cell`` / ``child``: one entry per cell of
+        ``dst`` (child 255 = identical cell, else the deal.II child number)."""
+        pc = np.ascontiguousarray(parent_cell, np.int32)
+        ch = np.ascontiguousarray(child, np.uint8)
+        if pc.size != dst.n_cells or ch.size != dst.n_cells or len(src_ptrs) != len(dst_ptrs):
+            raise ValueError("one (parent, child) entry per cell of dst and as many destination as source vectors expected")
+        n = len(src_ptrs)
+        sp = (C.c_void_p * max(n, 1))(*[C.c_void_p(p) for p in src_ptrs])
+        dp = (C.c_void_p * max(n, 1))(*[C.c_void_p(p) for p in dst_ptrs])
+        rc = self.lib.pfm_state_transfer(self._h, dst._h, capi.np_ptr(pc, np.int32), capi.np_ptr(ch, np.uint8), n, sp, dp)
+        if rc != capi.PFM_OK:
+            raise PfmError(rc, "pfm_state_transfer", self.lib.pfm_last_error(dst._h).decode())
 
 
 class Assembler:

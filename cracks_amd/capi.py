@@ -32,6 +32,7 @@ EXPORTS = [
     # include/pfm_newton.h
     "pfm_diag_mass_device", "pfm_active_set_device", "pfm_get_constraints", "pfm_functionals",
     "pfm_functionals_material", "pfm_residual_norms", "pfm_face_load", "pfm_cod_lines", "pfm_sneddon_phi_error",
+    "pfm_refine_flags", "pfm_min_cell_diameter", "pfm_state_transfer",
 ]
 
 
@@ -51,6 +52,14 @@ class PfmParams(C.Structure):
     def from_any(cls, other) -> "PfmParams":
         """Copy from any ctypes structure with the same field names (e.g. the test mirror)."""
         return cls(**{name: getattr(other, name) for name, _ in cls._fields_})
+
+
+class PfmRefineCriteria(C.Structure):
+    """include/pfm_newton.h, pfm_refine_criteria"""
+    _fields_ = [
+        ("phi_threshold", C.c_double), ("use_box", C.c_int), ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3),
+        ("max_level", C.c_int),
+    ]
 
 
 class PfmMeshDesc(C.Structure):
@@ -143,6 +152,9 @@ def load():
     lib.pfm_face_load.argtypes = [vp, i64, vp, vp, C.POINTER(C.c_double)]
     lib.pfm_cod_lines.argtypes = [vp, vp, i32, vp, C.c_double, vp, vp]
     lib.pfm_sneddon_phi_error.argtypes = [vp, vp, C.POINTER(C.c_double)]
+    lib.pfm_refine_flags.argtypes = [vp, C.POINTER(PfmRefineCriteria), vp, vp, vp, C.POINTER(i64)]
+    lib.pfm_min_cell_diameter.argtypes = [vp, vp, C.POINTER(C.c_double)]
+    lib.pfm_state_transfer.argtypes = [vp, vp, vp, vp, i32, vp, vp]
     _LIB = lib
     return lib
 

@@ -407,6 +407,9 @@ struct pfm_ctx
   int32_t *d_face_cells = nullptr; // pfm_face_load input staging (in allocs)
   uint8_t *d_face_ids = nullptr;
   int64_t n_face_cap = 0;
+  // mesh adaptation (pfm_adapt.hip): one grow-only scratch buffer (in allocs)
+  void *d_adapt = nullptr;
+  size_t adapt_bytes = 0;
   // measurement (pfm_timing_enable)
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

@@ -9,6 +9,9 @@
  *   compute_energy(), compute_tcv()                   cracks.cc:3615-3701, 3553-3611 -> pfm_functionals
  *   constraints_update.set_zero(residual); residual.l2_norm() / linfty_norm()
  *                                                     cracks.cc:2791-2794, 2918-2919, 2947-2949 -> pfm_residual_norms
+ *   refinement indicator + level limit of refine_mesh() cracks.cc:3902-4116 -> pfm_refine_flags
+ *   SolutionTransfer::interpolate                     cracks.cc:4137-4159   -> pfm_state_transfer
+ *   min_cell_diameter                                 cracks.cc:3824-3835   -> pfm_min_cell_diameter
  */
 #ifndef PFM_NEWTON_H
 #define PFM_NEWTON_H
@@ -112,6 +115,56 @@ int pfm_cod_lines(pfm_ctx *ctx, const uint8_t *cell_owned, int n_lines, const do
  * The caller takes the root of the MPI sum.  The reference keeps every cell's error in a Vector<float>: its printed
  * phi_L2_error carries a float rounding (about 1e-7 relative) that this sum does not. */
 int pfm_sneddon_phi_error(pfm_ctx *ctx, const uint8_t *cell_owned, double *sum_sq);
+
+/* ---- mesh adaptation (pfm_adapt.hip): the two sweeps around the context rebuild of refine_mesh() (cracks.cc:3895-4163)
+ * and the other half of determine_mesh_dependent_parameters() (cracks.cc:3820-3836).  Conventions of the functionals above:
+ * PFM_ERR_BAD_ARG with nothing launched on bad input, ordered behind earlier work on the context's stream, synchronous
+ * where outputs are host pointers, deterministic (repeated calls are bitwise identical). */
+
+typedef struct
+{
+  double phi_threshold; /* flag a cell when phi < threshold at one of its vertices (strict <; NaN never flags),
+                           cracks.cc:3987-3992, 4026-4031, 4060-4065; NaN = criterion off */
+  int use_box;          /* also flag a cell with a vertex in the closed box [box_lo, box_hi] (first `dim` entries; +-inf for
+                           open sides): fixed_preref_* 3911-3921, 3934-3944, 3957-3967 and the y >= 1.75 rule of 4007-4017 */
+  double box_lo[3], box_hi[3];
+  int max_level;        /* flags of cells with cell_level[cell] == max_level are cleared afterwards (4107-4116);
+                           < 0: no limit (Sneddon) */
+} pfm_refine_criteria;
+
+/* The refinement indicator of refine_mesh() on the node state last given to pfm_state_set / pfm_state_set_solution (after
+ * the ghost import; the contract of pfm_functionals: an owned cell may have ghost vertices), on every kernel path.
+ *   cell_owned  host [n_cells] or NULL = every local cell; cells that are not owned are never flagged
+ *   cell_level  host [n_cells]; may be NULL iff max_level < 0
+ *   flags       host out [n_cells], 0 / 1 -- what the host passes to cell->set_refine_flag()
+ *   n_flagged   host out, flagged cells of THIS rank (the caller does the MPI sum of cracks.cc:4133)
+ * One byte per cell and eight bytes travel to the host, not the solution. */
+int pfm_refine_flags(pfm_ctx *ctx, const pfm_refine_criteria *crit, const uint8_t *cell_owned, const uint8_t *cell_level,
+                     uint8_t *flags, int64_t *n_flagged);
+
+/* min over the cells with cell_owned[cell] != 0 (NULL = all) of cell->diameter(), the largest vertex distance of the
+ * cell (cracks.cc:3824-3835) -- what the h-dependent kappa and eps need after every rebuild.  +inf where no cell is
+ * masked; the caller takes the minimum over the ranks. */
+int pfm_min_cell_diameter(pfm_ctx *ctx, const uint8_t *cell_owned, double *h_min);
+
+/* SolutionTransfer::interpolate for refinement (cracks.cc:4137-4159) between two contexts: n_vectors dof vectors of `src`
+ * (device, src's layout) are interpolated to dof vectors of `dst` (device, dst's layout).
+ *   parent_cell[c]  the cell of src that dst cell c is identical to (child[c] == 255) or an isotropic child of
+ *   child[c]        255, or the child number 0 .. 2^dim - 1 in deal.II order: bit d = offset along reference axis d
+ * (host arrays [dst n_cells]).  The value at vertex v of dst cell c is the parent's Q1 function at the reference point
+ * xi_d = (child bit d + vertex bit d) / 2: the weights 1, 1/2, 1/4, 1/8 are exact, the terms with a non-zero weight are
+ * added in ascending parent-vertex order, and every dst node takes its value from the lowest-numbered dst cell that has
+ * it.  src vectors are expected distributed at hanging nodes (as cracks.cc:4417 leaves them).
+ * Before anything is written the relation is checked on the device against the coordinates: every dst vertex must lie at
+ * the Q1 image of its xi within 1e-10 of the parent's diameter.  A mismatch, an index out of range or a bad child number
+ * is PFM_ERR_BAD_ARG and d_dst is untouched.
+ * Both contexts must be unpartitioned (n_owned_nodes == n_nodes), on the same device, of the same dimension and layout,
+ * 1 <= n_vectors <= 8: anything else is PFM_ERR_UNSUPPORTED (p4est repartitions at a refinement; that transfer stays the
+ * host's).  Coarsening is NOT supported: the reference's phase-field strategies never set a coarsen flag.
+ * Ordered behind earlier work on both contexts' streams; the values are written on dst's stream (asynchronous after the
+ * check).  src must stay alive until the call has returned. */
+int pfm_state_transfer(pfm_ctx *src, pfm_ctx *dst, const int32_t *parent_cell, const uint8_t *child, int n_vectors,
+                       const double *const *d_src, double *const *d_dst);
 
 #ifdef __cplusplus
 }
