@@ -3,9 +3,10 @@
 
 Three things live here:
 
-* the numpy statement of the three device sweeps of ``include/pfm_newton.h`` ("mesh adaptation") --
-  ``refine_flags_numpy``, ``min_cell_diameter_numpy``, ``transfer_numpy``.  It is what the tests compare the kernels
-  with, bit for bit, and the CPU backend of the driver below;
+* the numpy statement of the device sweeps of ``include/pfm_newton.h`` ("mesh adaptation") -- ``refine_flags_numpy``,
+  ``min_cell_diameter_numpy``, ``transfer_numpy``, and for RefinementStrategy::mix ``face_neighbours_numpy``,
+  ``kelly_numpy``, ``indicator_select_numpy``, ``refine_flags_mix_numpy``.  It is what the tests compare the kernels
+  with (bit for bit, the Kelly indicator to round-off), and the CPU backend of the driver below;
 * ``two_level_mesh``: the stand-in for ``execute_coarsening_and_refinement`` on top of ``mesh.refine_cells``, with the
   ``(parent_cell, child)`` relation ``pfm_state_transfer`` takes;
 * ``AdaptiveDriver``: the time loop of ``newton.ActiveSetDriver`` with the predictor-corrector refinement.
@@ -55,6 +56,276 @@ def min_cell_diameter_numpy(mesh: M.Mesh, cell_owned: Optional[np.ndarray] = Non
     if cell_owned is not None:
         d = d[np.asarray(cell_owned).astype(bool)]
     return float(d.min()) if d.size else float("inf")
+
+
+# ---- RefinementStrategy::mix: face neighbours, Kelly indicator, fixed-number marking ------------------------------------
+
+REL_NONE, REL_SAME, REL_FINE, REL_COARSE = 0, 1, 2, 3
+
+
+@dataclass
+class FaceNeighbours:
+    """The face-neighbour table of ``pfm_kelly_indicator``.  ``rel[c, f]``: 0 = no neighbour among the cells of the mesh,
+    1 = ``nbr[c, f]`` is the cell of the same level across face f, 2 = ``nbr[c, f]`` is the coarser cell (the face is one
+    subface of its face), 3 = ``nbr[c, f]`` is the row of ``sub`` with the fine faces ``cell * 2 dim + face`` in ascending
+    order (-1: not a cell of the mesh)."""
+    nbr: np.ndarray  # [n_cells, 2 dim] int64
+    rel: np.ndarray  # [n_cells, 2 dim] uint8
+    sub: np.ndarray  # [n_coarse_faces, 2^(dim-1)] int64
+
+
+def _hanging_tables(mesh: M.Mesh):
+    """(hn_index [n_nodes] -> k or -1, parents [n_hanging, p] padded with -1, weights padded with 0)"""
+    index = np.full(mesh.n_nodes, -1, np.int64)
+    index[mesh.hn_nodes] = np.arange(mesh.hn_nodes.size)
+    cnt = np.diff(mesh.hn_ptr).astype(np.int64)
+    p = int(cnt.max()) if cnt.size else 1
+    par = np.full((cnt.size + 1, p), -1, np.int64)  # (one spare row: a conforming mesh has none)
+    w = np.zeros((cnt.size + 1, p))
+    slot = np.arange(p)[None, :] < cnt[:, None]
+    par[:-1][slot] = mesh.hn_parents
+    w[:-1][slot] = mesh.hn_weights
+    return index, par, w
+
+
+def face_neighbours_numpy(mesh: M.Mesh) -> FaceNeighbours:
+    """A face matches the other cell with the same vertex set.  An unmatched face with a hanging vertex takes the union of
+    its other vertices and the parents of the hanging ones; if that is the vertex set of another cell's (unmatched) face,
+    that cell is the coarser neighbour.  Everything else is a boundary face."""
+    dim, NC, nf, nfv = mesh.dim, mesh.n_cells, 2 * mesh.dim, 1 << (mesh.dim - 1)
+    BIG = np.iinfo(np.int64).max
+    cells = mesh.cells.astype(np.int64)
+    keys = np.sort(np.stack([cells[:, vs] for vs in M.face_vertices(dim)], axis=1), axis=2).reshape(-1, nfv)
+    index, par, _ = _hanging_tables(mesh)
+    # candidate faces: one of the vertices hangs
+    cand = np.nonzero((index[keys] >= 0).any(axis=1))[0]
+    uni = np.empty((0, nfv), np.int64)
+    uni_ok = np.zeros(0, bool)
+    if cand.size:
+        kc = keys[cand]  # [m, nfv]
+        hk = index[kc]
+        ex = np.where((hk >= 0)[:, :, None], par[np.maximum(hk, 0)], BIG)  # parents of the hanging vertices
+        ex[:, :, 0] = np.where(hk >= 0, ex[:, :, 0], kc)                     # the others themselves
+        ex = np.where(ex < 0, BIG, ex).reshape(cand.size, -1)
+        ex.sort(axis=1)
+        ex[:, 1:][ex[:, 1:] == ex[:, :-1]] = BIG
+        ex.sort(axis=1)
+        uni_ok = (ex < BIG).sum(axis=1) == nfv
+        uni = np.where(uni_ok[:, None], ex[:, :nfv], 0)
+    both = np.concatenate([keys, uni])
+    N = max(mesh.n_nodes, 2)
+    if float(N) ** nfv < 2.0 ** 62:
+        code = np.zeros(both.shape[0], np.int64)
+        for j in range(nfv):
+            code = code * N + both[:, j]
+        _, inv = np.unique(code, return_inverse=True)
+    else:
+        _, inv = np.unique(both, axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    kid, uid = inv[:keys.shape[0]], inv[keys.shape[0]:]
+    cnt = np.bincount(kid, minlength=int(inv.max()) + 1 if inv.size else 0)
+    order = np.argsort(kid, kind="stable")
+    first = np.zeros(cnt.size + 1, np.int64)
+    np.cumsum(cnt, out=first[1:])
+    nbr = np.full(NC * nf, -1, np.int64)
+    rel = np.zeros(NC * nf, np.uint8)
+    two = np.nonzero(cnt == 2)[0]
+    a, b = order[first[two]], order[first[two] + 1]
+    nbr[a], nbr[b] = b // nf, a // nf
+    rel[a] = rel[b] = REL_SAME
+    sub = np.zeros((0, nfv), np.int64)
+    if cand.size:
+        ok = uni_ok & (cnt[kid[cand]] == 1) & (uid != kid[cand]) & (cnt[uid] == 1)
+        fine = cand[ok]
+        coarse = order[first[uid[ok]]]
+        nbr[fine] = coarse // nf
+        rel[fine] = REL_FINE
+        cf, row = np.unique(coarse, return_inverse=True)
+        row = row.reshape(-1)
+        rel[cf] = REL_COARSE
+        nbr[cf] = np.arange(cf.size)
+        sub = np.full((cf.size, nfv), -1, np.int64)
+        o = np.lexsort((fine, row))
+        pos = np.arange(o.size) - np.searchsorted(row[o], row[o], side="left")
+        keep = pos < nfv
+        sub[row[o][keep], pos[keep]] = fine[o][keep]
+    return FaceNeighbours(nbr.reshape(NC, nf), rel.reshape(NC, nf), sub)
+
+
+def _q1_dweights(dim: int, xi: np.ndarray) -> np.ndarray:
+    """[..., nv, dim]: d N_b / d xi_d at the points xi [..., dim]"""
+    nv = 1 << dim
+    out = np.empty(xi.shape[:-1] + (nv, dim))
+    for b in range(nv):
+        for d in range(dim):
+            w = np.full(xi.shape[:-1], 1.0 if (b >> d) & 1 else -1.0)
+            for e in range(dim):
+                if e != d:
+                    w = w * (xi[..., e] if (b >> e) & 1 else 1.0 - xi[..., e])
+            out[..., b, d] = w
+    return out
+
+
+def _face_jump_integrals(mesh: M.Mesh, U: np.ndarray, hang, cA: np.ndarray, f: int, cB: np.ndarray) -> np.ndarray:
+    """int over face f of the cells cA of sum_c (n . grad u_c|_A - n . grad u_c|_B)^2 dA with QGauss<dim-1>(3).  The point of
+    B under a face point is the (bi)linear image of the reference corners A's face vertices have in B, through the hanging
+    weights where a vertex hangs on B's face."""
+    dim, nv = mesh.dim, mesh.nv
+    index, par, wts = hang
+    ax, side = f >> 1, f & 1
+    others = [d for d in range(dim) if d != ax]
+    cells = mesh.cells.astype(np.int64)
+    nA, nB = cells[cA], cells[cB]
+    XA, XB, UA, UB = mesh.coords[nA], mesh.coords[nB], U[nA], U[nB]
+    m = cA.size
+    bit = lambda corner: ((corner[:, None] >> np.arange(dim)[None, :]) & 1).astype(float)
+    xiB = np.zeros((m, nv, dim))
+    ok = np.ones(m, bool)
+    for b in M.face_vertices(dim)[f]:
+        eq = nB == nA[:, b][:, None]
+        found = eq.any(axis=1)
+        hk = index[nA[:, b]]
+        hangs = ~found & (hk >= 0)
+        ok &= found | hangs
+        val = np.where(found[:, None], bit(eq.argmax(axis=1)), 0.0)
+        for p in range(par.shape[1]):
+            pn, pw = par[np.maximum(hk, 0), p], np.where(hangs, wts[np.maximum(hk, 0), p], 0.0)
+            eqp = nB == pn[:, None]
+            ok &= ~(hangs & (pn >= 0)) | eqp.any(axis=1)
+            val = val + pw[:, None] * bit(eqp.argmax(axis=1))
+        xiB[:, b] = val
+    g = 0.5 * np.sqrt(0.6)
+    gp, gw = np.array([0.5 - g, 0.5, 0.5 + g]), np.array([5.0, 8.0, 5.0]) / 18.0
+    total = np.zeros(m)
+    for q in np.ndindex(*([3] * (dim - 1))):
+        xi = np.zeros(dim)
+        xi[ax] = side
+        w = 1.0
+        for o, i in zip(others, q):
+            xi[o] = gp[i]
+            w *= gw[i]
+        dNA = _q1_dweights(dim, xi)  # [nv, dim]
+        JA = np.einsum("mbi,bd->mid", XA, dNA)
+        if dim == 2:
+            t = JA[:, :, others[0]]
+            nrm = np.stack([t[:, 1], -t[:, 0]], axis=1)
+        else:
+            nrm = np.cross(JA[:, :, others[0]], JA[:, :, others[1]])
+        length = np.linalg.norm(nrm, axis=1)
+        nrm = nrm / length[:, None]
+        mA = np.linalg.solve(JA, nrm[:, :, None])[:, :, 0]
+        xb = np.einsum("b,mbd->md", _weights(dim, xi[None, :])[0], xiB)
+        dNB = _q1_dweights(dim, xb)  # [m, nv, dim]
+        JB = np.einsum("mbi,mbd->mid", XB, dNB)
+        mB = np.linalg.solve(JB, nrm[:, :, None])[:, :, 0]
+        jump = np.einsum("md,bd,mbc->mc", mA, dNA, UA) - np.einsum("md,mbd,mbc->mc", mB, dNB, UB)
+        total += (jump ** 2).sum(axis=1) * (w * length)
+    return np.where(ok, total, 0.0)
+
+
+def _nodal_components(mesh: M.Mesh, nodal: np.ndarray, component_mask: Optional[int]) -> np.ndarray:
+    dim = mesh.dim
+    mask = (1 << dim) - 1 if component_mask is None else int(component_mask)
+    if mask <= 0 or mask >> (dim + 1):
+        raise ValueError("component mask empty or with a bit above dim")
+    nodal = np.asarray(nodal, np.float64)
+    if nodal.ndim != 2 or nodal.shape[0] != mesh.n_nodes or nodal.shape[1] > dim + 1:
+        raise ValueError("nodal values [n_nodes, <= dim + 1] expected")
+    comps = [c for c in range(dim + 1) if (mask >> c) & 1 and c < nodal.shape[1]]
+    return np.ascontiguousarray(nodal[:, comps]) if comps else np.zeros((mesh.n_nodes, 1))
+
+
+def kelly_numpy(mesh: M.Mesh, nodal: np.ndarray, component_mask: Optional[int] = None, cell_owned: Optional[np.ndarray] = None,
+                neighbours: Optional[FaceNeighbours] = None) -> np.ndarray:
+    """``pfm_kelly_indicator``: ``eta_K = sqrt(h_K / 24 * sum_F int_F sum_c [n . grad u_c]^2 dA)`` (KellyErrorEstimator with
+    cell_diameter_over_24, no Neumann terms, coefficient 1) of the nodal values ``nodal`` [n_nodes, dim + 1] (displacements,
+    then phi; missing columns count as 0; hanging nodes distributed).  Bit c of ``component_mask`` selects column c; None =
+    the displacements."""
+    U = _nodal_components(mesh, nodal, component_mask)
+    fn = neighbours if neighbours is not None else face_neighbours_numpy(mesh)
+    hang = _hanging_tables(mesh)
+    nf = 2 * mesh.dim
+    I = np.zeros((mesh.n_cells, nf))
+    for f in range(nf):
+        cA = np.nonzero((fn.rel[:, f] == REL_SAME) | (fn.rel[:, f] == REL_FINE))[0]
+        if cA.size:
+            I[cA, f] = _face_jump_integrals(mesh, U, hang, cA, f, fn.nbr[cA, f])
+    cc, cf = np.nonzero(fn.rel == REL_COARSE)
+    if cc.size:
+        rows = fn.sub[fn.nbr[cc, cf]]
+        acc = np.zeros(cc.size)
+        for j in range(rows.shape[1]):  # the fine cells' own values, ascending fine cell
+            acc = acc + np.where(rows[:, j] >= 0, I.reshape(-1)[np.maximum(rows[:, j], 0)], 0.0)
+        I[cc, cf] = acc
+    s = np.zeros(mesh.n_cells)
+    for f in range(nf):
+        s = s + I[:, f]
+    eta = np.sqrt(mesh.cell_diameters() / 24.0 * s)
+    if cell_owned is not None:
+        eta = np.where(np.asarray(cell_owned).astype(bool), eta, 0.0)
+    return eta
+
+
+def indicator_select_numpy(ind: np.ndarray, k: int, cell_owned: Optional[np.ndarray] = None) -> Tuple[float, int, int]:
+    """``pfm_indicator_select``: ``(t, n_above, n_equal)`` with t the k-th largest (1-based) masked value; -0.0 counts and
+    is returned as 0.0, a NaN ranks below every number."""
+    x = np.asarray(ind, np.float64)
+    if cell_owned is not None:
+        x = x[np.asarray(cell_owned).astype(bool)]
+    if k < 1 or k > x.size:
+        raise ValueError("k outside [1, number of masked values]")
+    x = np.where(x == 0.0, 0.0, x)
+    numbers = x[~np.isnan(x)]
+    if k > numbers.size:
+        return float("nan"), int(numbers.size), int(x.size - numbers.size)
+    t = float(np.partition(numbers, numbers.size - k)[numbers.size - k])
+    return t, int((numbers > t).sum()), int((numbers == t).sum())
+
+
+def indicator_count_numpy(ind: np.ndarray, t: float, cell_owned: Optional[np.ndarray] = None) -> Tuple[int, int]:
+    """``pfm_indicator_count``: the masked values above ``t`` and equal to it, in the order of ``indicator_select_numpy``."""
+    x = np.asarray(ind, np.float64)
+    if cell_owned is not None:
+        x = x[np.asarray(cell_owned).astype(bool)]
+    nan = np.isnan(x)
+    if np.isnan(t):
+        return int((~nan).sum()), int(nan.sum())
+    with np.errstate(invalid="ignore"):
+        return int((x > t).sum()), int((x == t).sum())
+
+
+def refine_flags_mix_numpy(mesh: M.Mesh, nodal: np.ndarray, top_fraction: float = 0.3, component_mask: Optional[int] = None,
+                           phi_threshold: float = float("nan"), box_lo=None, box_hi=None, max_level: int = -1,
+                           cell_owned: Optional[np.ndarray] = None, cell_level: Optional[np.ndarray] = None,
+                           neighbours: Optional[FaceNeighbours] = None) -> Tuple[np.ndarray, int, float]:
+    """``pfm_refine_flags_mix`` (cracks.cc:4043-4116): the phase-field flags without the level limit, the Kelly indicator
+    zeroed on them, the ``(int)(top_fraction * n_cells)`` largest indicators flagged (ties all flag, a zero threshold becomes
+    the smallest positive indicator, zero indicators never flag), then the level limit.  ``(flags, n_flagged, threshold)``."""
+    if not 0.0 <= top_fraction <= 1.0:
+        raise ValueError("top_fraction outside [0, 1]")
+    nodal = np.asarray(nodal, np.float64)
+    f, _ = refine_flags_numpy(mesh, nodal[:, mesh.dim], phi_threshold, box_lo, box_hi, -1, cell_owned)
+    f = f.astype(bool)
+    k = int(top_fraction * mesh.n_cells)
+    t = float("inf")
+    if k >= 1:
+        eta = kelly_numpy(mesh, nodal, component_mask, cell_owned, neighbours)
+        eta[f] = 0.0
+        t = indicator_select_numpy(eta, k)[0]
+        if not t > 0.0:
+            pos = eta[eta > 0.0]
+            t = float(pos.min()) if pos.size else float("inf")
+        with np.errstate(invalid="ignore"):
+            f |= eta >= t
+    if max_level >= 0:
+        f &= np.asarray(cell_level) != max_level
+    return f.astype(np.uint8), int(f.sum()), t
+
+
+def nodal_values(mesh: M.Mesh, layout, vec: np.ndarray) -> np.ndarray:
+    """[n_nodes, dim + 1] nodal displacements and phase field of a dof vector"""
+    n = np.arange(mesh.n_nodes)
+    return np.stack([np.asarray(vec)[layout.dof(n, c)] for c in range(mesh.dim + 1)], axis=1)
 
 
 def _xi(dim: int, child: np.ndarray, vtx: np.ndarray) -> np.ndarray:
@@ -192,6 +463,9 @@ class NumpyAdaptor:
         phi = vectors[0][layout.dof(np.arange(mesh.n_nodes), mesh.dim)]
         return refine_flags_numpy(mesh, phi, **crit)
 
+    def flags_mix(self, asm, mesh, layout, vectors, params, crit: dict, top_fraction: float):
+        return refine_flags_mix_numpy(mesh, nodal_values(mesh, layout, vectors[0]), top_fraction, **crit)[:2]
+
     def transfer(self, asm_src, mesh_src, asm_dst, mesh_dst, blocked, parent_cell, child, vectors):
         return transfer_numpy(mesh_src, mesh_dst, blocked, parent_cell, child, vectors)
 
@@ -205,6 +479,11 @@ class DeviceAdaptor:
         asm.ctx.set_params(params)
         asm.ctx.state_set_host(*vectors)
         return asm.ctx.refine_flags(**crit)
+
+    def flags_mix(self, asm, mesh, layout, vectors, params, crit: dict, top_fraction: float):
+        asm.ctx.set_params(params)
+        asm.ctx.state_set_host(*vectors)
+        return asm.ctx.refine_flags_mix(top_fraction, **crit)[:2]
 
     def transfer(self, asm_src, mesh_src, asm_dst, mesh_dst, blocked, parent_cell, child, vectors):
         import torch
@@ -238,13 +517,19 @@ class AdaptiveDriver:
     ``setup_of(mesh) -> ProblemSetup`` builds the problem on a mesh (its ``solution0`` is only used on the base mesh);
     ``assembler_of(mesh, layout)`` is the assembler factory; ``adaptor`` evaluates the indicator and moves the vectors
     (``NumpyAdaptor`` / ``DeviceAdaptor``).  ``phi_threshold`` is the reference's ``value_phase_field_for_refinement``;
-    cells one level above the base are never flagged (its level limit).  The mesh-dependent parameters stay those of
+    cells one level above the base are never flagged (its level limit).  ``strategy``: "phase_field" (that criterion alone)
+    or "mix" (cracks.cc:4043-4103: also the ``top_fraction`` of the cells with the largest Kelly indicator of the
+    displacements).  The mesh-dependent parameters stay those of
     ``setup_of``: the reference's Miehe and three-point tests fix h to the finest level in advance (cracks.cc:3839-3854).
 
     ``records`` holds one ``AdaptiveRecord`` per "Timestep" block of the reference's output, redone ones included."""
 
     def __init__(self, base: M.Mesh, setup_of: Callable, assembler_of: Callable, adaptor, phi_threshold: float,
-                 box_lo=None, box_hi=None, log: Optional[Callable[[str], None]] = None):
+                 box_lo=None, box_hi=None, log: Optional[Callable[[str], None]] = None, strategy: str = "phase_field",
+                 top_fraction: float = 0.3):
+        if strategy not in ("phase_field", "mix"):
+            raise ValueError(strategy)
+        self.strategy, self.top_fraction = strategy, float(top_fraction)
         self.base = base
         self.setup_of, self.assembler_of, self.adaptor = setup_of, assembler_of, adaptor
         self.crit = dict(phi_threshold=phi_threshold, box_lo=box_lo, box_hi=box_hi, max_level=1)
@@ -262,7 +547,10 @@ class AdaptiveDriver:
         mesh, lay = d.s.mesh, d.s.layout
         vectors = [d.solution, d.old_solution, d.old_old_solution]
         crit = dict(self.crit, cell_level=self.tl.cell_level)
-        flags, n = self.adaptor.flags(self.asm, mesh, lay, vectors, d._params(), crit)
+        if self.strategy == "mix":
+            flags, n = self.adaptor.flags_mix(self.asm, mesh, lay, vectors, d._params(), crit, self.top_fraction)
+        else:
+            flags, n = self.adaptor.flags(self.asm, mesh, lay, vectors, d._params(), crit)
         if n == 0:
             return False, 0
         new_mask = self.mask.copy()

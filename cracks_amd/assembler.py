@@ -390,6 +390,67 @@ class Context:
                                               capi.np_ptr(flags, np.uint8), C.byref(n)), "pfm_refine_flags")
         return flags, int(n.value)
 
+    def _criteria(self, phi_threshold, box_lo, box_hi, max_level):
+        crit = capi.PfmRefineCriteria()
+        crit.phi_threshold = float(phi_threshold)
+        crit.use_box = 0 if box_lo is None else 1
+        if box_lo is not None:
+            for d in range(self.dim):
+                crit.box_lo[d], crit.box_hi[d] = float(box_lo[d]), float(box_hi[d])
+        crit.max_level = int(max_level)
+        return crit
+
+    def _cell_bytes(self, a):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, np.uint8)
+        if a.size != self.n_cells:
+            raise ValueError("one entry per cell expected")
+        return a, capi.np_ptr(a, np.uint8)
+
+    def kelly_indicator(self, eta_ptr: int, component_mask: Optional[int] = None, cell_owned: Optional[np.ndarray] = None):
+        """``pfm_kelly_indicator``: the Kelly indicator (cracks.cc:4074-4083) of the node state in the context into the device
+        array ``eta_ptr`` [n_cells] of doubles, asynchronously.  ``component_mask``: bit c < dim = displacement c, bit dim =
+        phi; None = the displacements, as the reference."""
+        mask = (1 << self.dim) - 1 if component_mask is None else int(component_mask)
+        if mask < 0 or mask >= 1 << 32:
+            raise ValueError("component_mask does not fit an unsigned int")
+        owned, mp = self._cell_bytes(cell_owned)  # (the array stays referenced across the call)
+        self._check(self.lib.pfm_kelly_indicator(self._h, mp, mask, C.c_void_p(eta_ptr)), "pfm_kelly_indicator")
+
+    def indicator_select(self, ind_ptr: int, k: int, cell_owned: Optional[np.ndarray] = None):
+        """``pfm_indicator_select``: ``(threshold, n_above, n_equal)``, the k-th largest (1-based) of the device array
+        ``ind_ptr`` [n_cells] over the masked cells, exactly."""
+        t, counts = C.c_double(0.0), (C.c_int64 * 2)()
+        owned, mp = self._cell_bytes(cell_owned)  # (the array stays referenced across the call)
+        self._check(self.lib.pfm_indicator_select(self._h, C.c_void_p(ind_ptr), mp, int(k), C.byref(t), counts), "pfm_indicator_select")
+        return float(t.value), int(counts[0]), int(counts[1])
+
+    def indicator_count(self, ind_ptr: int, t: float, cell_owned: Optional[np.ndarray] = None):
+        """``pfm_indicator_count``: ``(n_above, n_equal)`` of the masked entries of the device array against ``t`` -- what a
+        distributed host sums over the ranks while it bisects for the global threshold."""
+        counts = (C.c_int64 * 2)()
+        owned, mp = self._cell_bytes(cell_owned)  # (the array stays referenced across the call)
+        self._check(self.lib.pfm_indicator_count(self._h, C.c_void_p(ind_ptr), mp, float(t), counts), "pfm_indicator_count")
+        return int(counts[0]), int(counts[1])
+
+    def refine_flags_mix(self, top_fraction: float = 0.3, component_mask: Optional[int] = None, phi_threshold: float = float("nan"),
+                         box_lo=None, box_hi=None, max_level: int = -1, cell_owned: Optional[np.ndarray] = None,
+                         cell_level: Optional[np.ndarray] = None):
+        """``pfm_refine_flags_mix``: RefinementStrategy::mix (cracks.cc:4043-4116) on the node state in the context:
+        ``(flags uint8 [n_cells], n_flagged, threshold)``."""
+        crit = self._criteria(phi_threshold, box_lo, box_hi, max_level)
+        mask = (1 << self.dim) - 1 if component_mask is None else int(component_mask)
+        if mask < 0 or mask >= 1 << 32:
+            raise ValueError("component_mask does not fit an unsigned int")
+        owned, op = self._cell_bytes(cell_owned)  # (the arrays stay referenced across the call)
+        level, lp = self._cell_bytes(cell_level)
+        flags = np.zeros(self.n_cells, np.uint8)
+        n, t = C.c_int64(0), C.c_double(0.0)
+        self._check(self.lib.pfm_refine_flags_mix(self._h, C.byref(crit), float(top_fraction), mask, op, lp,
+                                                  capi.np_ptr(flags, np.uint8), C.byref(n), C.byref(t)), "pfm_refine_flags_mix")
+        return flags, int(n.value), float(t.value)
+
     def min_cell_diameter(self, cell_owned: Optional[np.ndarray] = None) -> float:
         """``min_cell_diameter`` over this rank's cells (cracks.cc:3824-3835); +inf where no cell is masked."""
         out = C.c_double(0.0)

@@ -33,6 +33,7 @@ EXPORTS = [
     "pfm_diag_mass_device", "pfm_active_set_device", "pfm_get_constraints", "pfm_functionals",
     "pfm_functionals_material", "pfm_residual_norms", "pfm_face_load", "pfm_cod_lines", "pfm_sneddon_phi_error",
     "pfm_refine_flags", "pfm_min_cell_diameter", "pfm_state_transfer",
+    "pfm_kelly_indicator", "pfm_indicator_select", "pfm_indicator_count", "pfm_refine_flags_mix",
 ]
 
 
@@ -155,6 +156,11 @@ def load():
     lib.pfm_refine_flags.argtypes = [vp, C.POINTER(PfmRefineCriteria), vp, vp, vp, C.POINTER(i64)]
     lib.pfm_min_cell_diameter.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.pfm_state_transfer.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+    lib.pfm_kelly_indicator.argtypes = [vp, vp, C.c_uint, vp]
+    lib.pfm_indicator_select.argtypes = [vp, vp, vp, i64, C.POINTER(C.c_double), C.POINTER(i64)]
+    lib.pfm_indicator_count.argtypes = [vp, vp, vp, C.c_double, C.POINTER(i64)]
+    lib.pfm_refine_flags_mix.argtypes = [vp, C.POINTER(PfmRefineCriteria), C.c_double, C.c_uint, vp, vp, vp, C.POINTER(i64),
+                                         C.POINTER(C.c_double)]
     _LIB = lib
     return lib
 

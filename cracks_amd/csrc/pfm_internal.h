@@ -410,6 +410,12 @@ struct pfm_ctx
   // mesh adaptation (pfm_adapt.hip): one grow-only scratch buffer (in allocs)
   void *d_adapt = nullptr;
   size_t adapt_bytes = 0;
+  // face-neighbour table of pfm_kelly_indicator, built on first use (in allocs): neighbour cell or side-list entry and the
+  // relation byte per (face, cell), and the fine faces of every face against finer cells
+  int32_t *d_face_nbr = nullptr;
+  uint8_t *d_face_rel = nullptr;
+  uint32_t *d_face_sub = nullptr;
+  bool face_table_ready = false;
   // measurement (pfm_timing_enable)
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

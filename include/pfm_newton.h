@@ -166,6 +166,60 @@ int pfm_min_cell_diameter(pfm_ctx *ctx, const uint8_t *cell_owned, double *h_min
 int pfm_state_transfer(pfm_ctx *src, pfm_ctx *dst, const int32_t *parent_cell, const uint8_t *child, int n_vectors,
                        const double *const *d_src, double *const *d_dst);
 
+/* ---- RefinementStrategy::mix (cracks.cc:4043-4116): the Kelly indicator of the displacements, zeroed where the phase
+ * field has flagged, and refine_and_coarsen_fixed_number(..., top_fraction, 0.0).  All four read the node state last given
+ * to pfm_state_set / pfm_state_set_solution (hanging nodes distributed) and work on every kernel path.
+ *
+ * KellyErrorEstimator<dim>::estimate as the reference calls it (deal.II >= 9: strategy cell_diameter_over_24, empty
+ * Neumann map, coefficient 1):
+ *   eta[K] = sqrt( h_K / 24 * sum over the faces F of K of I_F ),   h_K = cell->diameter() as in pfm_min_cell_diameter,
+ *   I_F    = int_F sum_{c in mask} ( n . grad u_c |_K - n . grad u_c |_K' )^2 dA,   QGauss<dim-1>(3), MappingQ1 on both sides.
+ * A face whose neighbour is refined once more contributes the sum of its 2^(dim-1) subface integrals (each evaluated from
+ * the fine cell's side, added in ascending fine-cell order), a fine cell's face against a coarser neighbour that one
+ * subface; a face without a neighbour among the local cells -- domain boundary, slit lips with duplicated nodes, a cell of
+ * another rank that is not in the ghost layer -- contributes 0.
+ *   cell_owned      host [n_cells] or NULL = every local cell; eta = 0 for the others
+ *   component_mask  bit c < dim: displacement component c, bit dim: phi.  The reference uses (1 << dim) - 1.  0 or a bit
+ *                   above dim: PFM_ERR_BAD_ARG
+ *   d_eta           device out [n_cells], double.  Asynchronous on the context's stream, like pfm_diag_mass_device.
+ * The indicator is computed and returned in double; the reference accumulates into a Vector<float>, so its values (and a
+ * threshold derived from them) carry a float rounding that these do not (see pfm_sneddon_phi_error).
+ * The face-neighbour table is built from the cell and hanging-node tables of pfm_ctx_create at the first call, kept in
+ * the context and counted in pfm_ctx_device_bytes (PFM_ERR_NOMEM if it does not fit; the context stays usable).  A face
+ * matches the cell with the same vertex set; an unmatched face with a hanging vertex matches the face made of its other
+ * vertices and the parents (as listed in hn_parents) of the hanging ones.
+ * Partitioned contexts: the caller's contract is that every face neighbour of an owned cell is a local cell (p4est's
+ * ghost layer holds them) and that the ghost values have been imported; eta is then right for every owned cell.
+ * No floating-point atomics: repeated calls are bitwise identical. */
+int pfm_kelly_indicator(pfm_ctx *ctx, const uint8_t *cell_owned, unsigned component_mask, double *d_eta);
+
+/* The k-th largest value (1-based) of the device array d_ind [n_cells] over the cells with cell_owned[cell] != 0 (NULL =
+ * all): exact (radix select on the order-preserving 64-bit key with integer histograms).  -0.0 and 0.0 compare equal (0.0
+ * is returned), a NaN ranks below every number (a NaN is returned when rank k falls on one).
+ *   counts[0] = masked values above *threshold, counts[1] = masked values equal to it.
+ * k < 1 or k above the number of masked cells: PFM_ERR_BAD_ARG.  Synchronous. */
+int pfm_indicator_select(pfm_ctx *ctx, const double *d_ind, const uint8_t *cell_owned, int64_t k, double *threshold,
+                         int64_t counts[2]);
+
+/* The same two counts for a given t.  A distributed host bisects on this with its own MPI sum, as
+ * parallel::distributed::GridRefinement does; the library does not do the bisection.  Synchronous. */
+int pfm_indicator_count(pfm_ctx *ctx, const double *d_ind, const uint8_t *cell_owned, double t, int64_t counts[2]);
+
+/* cracks.cc:4043-4116 on one rank:
+ *   (a) the flags of `crit` without its level limit (pfm_refine_flags),
+ *   (b) eta = pfm_kelly_indicator(component_mask), set to 0 on the flagged cells (4085-4095),
+ *   (c) k = (int64) (top_fraction * n_cells), truncated as the reference's static_cast.  k >= 1: t = the k-th largest eta
+ *       over all local cells; t == 0 becomes the smallest positive eta; every cell with eta >= t is flagged -- ties at t
+ *       all flag, a zero indicator never does (serial refine_and_coarsen_fixed_number + refine),
+ *   (d) flags at crit->max_level are cleared (4107-4116).
+ * Outputs as pfm_refine_flags, plus *threshold = the t used (+inf when (c) flags nothing: k == 0 or no positive eta).
+ * top_fraction outside [0, 1] or a bad mask: PFM_ERR_BAD_ARG.  A partitioned context (n_owned_nodes != n_nodes) is
+ * PFM_ERR_UNSUPPORTED with the outputs untouched: the fraction is of the global cell count, so that host composes the three
+ * calls above itself.  Synchronous. */
+int pfm_refine_flags_mix(pfm_ctx *ctx, const pfm_refine_criteria *crit, double top_fraction, unsigned component_mask,
+                         const uint8_t *cell_owned, const uint8_t *cell_level, uint8_t *flags, int64_t *n_flagged,
+                         double *threshold);
+
 #ifdef __cplusplus
 }
 #endif
