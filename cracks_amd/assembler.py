@@ -364,6 +364,30 @@ class Context:
         self._check(self.lib.pfm_sneddon_phi_error(self._h, mp, out), "pfm_sneddon_phi_error")
         return float(out[0])
 
+    def cod_buckets(self, n_buckets: int = 75, x_lo: float = -1.5, x_hi: float = 1.5, n_sub: int = 100,
+                    cell_owned: Optional[np.ndarray] = None):
+        """compute_cod_array (cracks.cc:3337-3449) before its MPI sum: ``(values, volume)``, this rank's raw bucket sums of
+        ``u . grad(phi) JxW`` and ``JxW`` over the ``n_sub^dim`` midpoints of every masked cell (``pfm_cod_buckets``)."""
+        values, volume = np.zeros(max(int(n_buckets), 0)), np.zeros(max(int(n_buckets), 0))
+        owned, mp = self._cell_bytes(cell_owned)  # (the array stays referenced across the call)
+        self._check(self.lib.pfm_cod_buckets(self._h, mp, int(n_buckets), float(x_lo), float(x_hi), int(n_sub),
+                                             capi.np_ptr(values, np.float64), capi.np_ptr(volume, np.float64)), "pfm_cod_buckets")
+        return values, volume
+
+    def point_eval(self, points, cell_owned: Optional[np.ndarray] = None):
+        """``pfm_point_eval``: ``(cell [P], values [P, dim+1], grads [P, dim+1, dim])`` of the node state at the points
+        ``[P, dim]``: the lowest-numbered masked cell that contains each point (-1: none, values and gradients 0), the Q1
+        interpolant of (u, phi) and ``grads[p, c, d] = d(component c)/dx_d`` (cracks.cc:3264-3320)."""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, self.dim)
+        n, nc = pts.shape[0], self.dim + 1
+        cell = np.full(max(n, 1), -1, np.int32)  # (at least one entry: the pointers of an empty call are still valid)
+        values, grads = np.zeros((max(n, 1), nc)), np.zeros((max(n, 1), nc, self.dim))
+        buf = pts if n else np.zeros((1, self.dim))
+        owned, mp = self._cell_bytes(cell_owned)
+        self._check(self.lib.pfm_point_eval(self._h, mp, n, capi.np_ptr(buf, np.float64), capi.np_ptr(cell, np.int32),
+                                            capi.np_ptr(values, np.float64), capi.np_ptr(grads, np.float64)), "pfm_point_eval")
+        return cell[:n], values[:n], grads[:n]
+
     # ---- include/pfm_newton.h, mesh adaptation
     def refine_flags(self, phi_threshold: float = float("nan"), box_lo=None, box_hi=None, max_level: int = -1,
                      cell_owned: Optional[np.ndarray] = None, cell_level: Optional[np.ndarray] = None):

@@ -32,6 +32,7 @@ EXPORTS = [
     # include/pfm_newton.h
     "pfm_diag_mass_device", "pfm_active_set_device", "pfm_get_constraints", "pfm_functionals",
     "pfm_functionals_material", "pfm_residual_norms", "pfm_face_load", "pfm_cod_lines", "pfm_sneddon_phi_error",
+    "pfm_cod_buckets", "pfm_point_eval",
     "pfm_refine_flags", "pfm_min_cell_diameter", "pfm_state_transfer",
     "pfm_kelly_indicator", "pfm_indicator_select", "pfm_indicator_count", "pfm_refine_flags_mix",
 ]
@@ -153,6 +154,8 @@ def load():
     lib.pfm_face_load.argtypes = [vp, i64, vp, vp, C.POINTER(C.c_double)]
     lib.pfm_cod_lines.argtypes = [vp, vp, i32, vp, C.c_double, vp, vp]
     lib.pfm_sneddon_phi_error.argtypes = [vp, vp, C.POINTER(C.c_double)]
+    lib.pfm_cod_buckets.argtypes = [vp, vp, i32, C.c_double, C.c_double, i32, vp, vp]
+    lib.pfm_point_eval.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.pfm_refine_flags.argtypes = [vp, C.POINTER(PfmRefineCriteria), vp, vp, vp, C.POINTER(i64)]
     lib.pfm_min_cell_diameter.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.pfm_state_transfer.argtypes = [vp, vp, vp, vp, i32, vp, vp]

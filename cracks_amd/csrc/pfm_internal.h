@@ -410,6 +410,9 @@ struct pfm_ctx
   // mesh adaptation (pfm_adapt.hip): one grow-only scratch buffer (in allocs)
   void *d_adapt = nullptr;
   size_t adapt_bytes = 0;
+  // pfm_cod_buckets / pfm_point_eval (pfm_pointstat.hip): one grow-only scratch buffer (in allocs, counted in device_bytes)
+  void *d_stat = nullptr;
+  size_t stat_bytes = 0;
   // face-neighbour table of pfm_kelly_indicator, built on first use (in allocs): neighbour cell or side-list entry and the
   // relation byte per (face, cell), and the fine faces of every face against finer cells
   int32_t *d_face_nbr = nullptr;

@@ -9,6 +9,7 @@
 // atomics): repeated calls are bitwise identical.  Each entry returns this rank's part; the MPI sums, the reference's
 // sign flips and its "/2" are the caller's.
 #include "pfm_internal.h"
+#include "pfm_q1_point.h"
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -31,110 +32,6 @@ namespace pfm
       return i == 0 ? 0.5 - 0.5 * 0.7745966692414834 : (i == 1 ? 0.5 : 0.5 + 0.5 * 0.7745966692414834);
     }
     __device__ __forceinline__ double gauss_w(int i) { return i == 1 ? 8.0 / 18.0 : 5.0 / 18.0; }
-
-    template <int dim>
-    __device__ __forceinline__ void load_geometry(const DevView &v, long long cell, double x[1 << dim][dim])
-    {
-#pragma unroll
-      for (int b = 0; b < (1 << dim); ++b)
-        {
-          const int n = v.conn[(long long)b * v.n_cells + cell];
-#pragma unroll
-          for (int d = 0; d < dim; ++d)
-            x[b][d] = v.coords[(long long)d * v.n_nodes + n];
-        }
-    }
-
-    template <int dim>
-    __device__ __forceinline__ void load_state(const DevView &v, long long cell, double U[1 << dim][dim], double PH[1 << dim])
-    {
-#pragma unroll
-      for (int b = 0; b < (1 << dim); ++b)
-        {
-          const int n = v.conn[(long long)b * v.n_cells + cell];
-#pragma unroll
-          for (int d = 0; d < dim; ++d)
-            U[b][d] = v.u[d][n];
-          PH[b] = v.phi[n];
-        }
-    }
-
-    // Q1 shape values, physical gradients and det J at the reference point xi (MappingQ1)
-    template <int dim>
-    __device__ __forceinline__ double eval_point(const double x[1 << dim][dim], const double xi[dim], double N[1 << dim],
-                                                 double g[1 << dim][dim], double inv[dim][dim])
-    {
-      constexpr int nv = 1 << dim;
-      double dNr[nv][dim];
-#pragma unroll
-      for (int b = 0; b < nv; ++b)
-        {
-          double val = 1.0;
-#pragma unroll
-          for (int d = 0; d < dim; ++d)
-            val *= ((b >> d) & 1) ? xi[d] : (1.0 - xi[d]);
-          N[b] = val;
-#pragma unroll
-          for (int e = 0; e < dim; ++e)
-            {
-              double s = 1.0;
-#pragma unroll
-              for (int d = 0; d < dim; ++d)
-                s *= (d == e) ? (((b >> d) & 1) ? 1.0 : -1.0) : (((b >> d) & 1) ? xi[d] : (1.0 - xi[d]));
-              dNr[b][e] = s;
-            }
-        }
-      double J[dim][dim], det;
-#pragma unroll
-      for (int i = 0; i < dim; ++i)
-#pragma unroll
-        for (int j = 0; j < dim; ++j)
-          {
-            double s = 0.0;
-#pragma unroll
-            for (int b = 0; b < nv; ++b)
-              s += x[b][i] * dNr[b][j];
-            J[i][j] = s;
-          }
-      if constexpr (dim == 2)
-        {
-          det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-          const double id = 1.0 / det;
-          inv[0][0] = J[1][1] * id;
-          inv[0][1] = -J[0][1] * id;
-          inv[1][0] = -J[1][0] * id;
-          inv[1][1] = J[0][0] * id;
-        }
-      else
-        {
-          const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-          const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-          const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-          det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-          const double id = 1.0 / det;
-          inv[0][0] = c00 * id;
-          inv[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-          inv[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-          inv[1][0] = c01 * id;
-          inv[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-          inv[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-          inv[2][0] = c02 * id;
-          inv[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-          inv[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-        }
-#pragma unroll
-      for (int b = 0; b < nv; ++b)
-#pragma unroll
-        for (int d = 0; d < dim; ++d)
-          {
-            double s = 0.0;
-#pragma unroll
-            for (int e = 0; e < dim; ++e)
-              s += inv[e][d] * dNr[b][e];
-            g[b][d] = s;
-          }
-      return det;
-    }
 
     // Point q of QGauss<dim-1>(3) on face f (deal.II numbering: axis f/2, side f%2) in cell reference coordinates,
     // QProjector's axis order: 2-D (s,t) / (t,s); 3-D faces 0/1 (s,q0,q1), 2/3 (q1,s,q0), 4/5 (q0,q1,s).
@@ -531,13 +428,6 @@ namespace pfm
         cod[l] = acc;
     }
 
-    int fail(pfm_ctx *c, int code, const std::string &msg)
-    {
-      if (c)
-        c->err = msg;
-      return code;
-    }
-
     // device buffer in the context's allocation list (freed by pfm_ctx_destroy); `old` is released first
     template <class T>
     int realloc_owned(pfm_ctx *c, T *&p, size_t n)
@@ -569,24 +459,6 @@ namespace pfm
       c->allocs.push_back(p);
       c->d_partial = p;
       c->n_partial = nb;
-      return PFM_OK;
-    }
-
-    int upload_mask(pfm_ctx *c, const uint8_t *cell_owned, uint8_t **d_owned)
-    {
-      *d_owned = nullptr;
-      if (!cell_owned)
-        return PFM_OK;
-      if (!c->d_cell_owned)
-        {
-          if (hipMalloc((void **)&c->d_cell_owned, (size_t)std::max<long long>(c->v.n_cells, 1)) != hipSuccess)
-            return fail(c, PFM_ERR_NOMEM, "hipMalloc cell mask");
-          c->allocs.push_back(c->d_cell_owned);
-        }
-      if (c->v.n_cells > 0 &&
-          hipMemcpyAsync(c->d_cell_owned, cell_owned, (size_t)c->v.n_cells, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return fail(c, PFM_ERR_HIP, "cell mask upload");
-      *d_owned = c->d_cell_owned;
       return PFM_OK;
     }
 

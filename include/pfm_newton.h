@@ -12,6 +12,8 @@
  *   refinement indicator + level limit of refine_mesh() cracks.cc:3902-4116 -> pfm_refine_flags
  *   SolutionTransfer::interpolate                     cracks.cc:4137-4159   -> pfm_state_transfer
  *   min_cell_diameter                                 cracks.cc:3824-3835   -> pfm_min_cell_diameter
+ *   compute_cod_array()                               cracks.cc:3337-3449   -> pfm_cod_buckets
+ *   compute_point_stress(), compute_point_value()     cracks.cc:3285-3320, 3264-3283 -> pfm_point_eval
  */
 #ifndef PFM_NEWTON_H
 #define PFM_NEWTON_H
@@ -108,6 +110,49 @@ int pfm_face_load(pfm_ctx *ctx, int64_t n_faces, const int32_t *cells, const uin
  * mask: later calls only evaluate the faces. */
 int pfm_cod_lines(pfm_ctx *ctx, const uint8_t *cell_owned, int n_lines, const double *lines, double eps, double *cod,
                   int64_t *n_faces);
+
+/* compute_cod_array (cracks.cc:3337-3449; the reference has its call switched off at cracks.cc:4491, "very expensive"): the
+ * Sneddon COD profile, the integral of u . grad(phi) binned into n_buckets slices along x with QIterated(QMidpoint, n_sub).
+ * Every cell with cell_owned[cell] != 0 (NULL = every local cell) is sampled at the n_sub^dim points xi_d = (k_d + 0.5) / n_sub
+ * (k_0 fastest), weight n_sub^-dim each; at each point, with MappingQ1, x = x(xi)[0], JxW = det J(xi) * weight and
+ *   idx = floor((x - x_lo) / (x_hi - x_lo) * n_buckets + 0.5)      (value_to_bucket, cracks.cc:3323-3328, with its constants
+ *                                                                   made arguments; in double, in this order, unfused)
+ * points with idx < 0 or idx >= n_buckets are dropped (cracks.cc:3393-3394), otherwise
+ *   values[idx] += (u . grad phi) JxW,   volume[idx] += JxW         (cracks.cc:3404-3409).
+ * values, volume: host out [n_buckets], THIS rank's raw sums; the MPI sum, the "/ width / 2.0" of cracks.cc:3419 and the
+ * error norm of 3432-3438 are the caller's.  The reference's call is (75, -1.5, 1.5, 100).
+ * Limits: 1 <= n_buckets <= 128, 1 <= n_sub <= 128, x_lo < x_hi and both finite, non-NULL outputs; anything else is
+ * PFM_ERR_BAD_ARG with nothing launched and the outputs untouched.
+ * No floating-point atomics: a wave walks the rows of a fixed slab of a cell's points (256 rows along xi_0), a fixed number of
+ * waves takes the (cell, slab) items in contiguous ranges, and the per-wave partial sums are added in wave order; the order of
+ * every sum depends on the mesh size and the arguments only, so repeated calls are bitwise identical.  One launch covers at
+ * most 2^32 sample points (the bound and what is known about its kernel time: DESIGN.md 4.4): the host side splits the cell range, launch after
+ * launch on the context's stream, and the launches' sums are added in launch order.  The scratch (at most 12 MiB + 4 KiB) is kept in the
+ * context and counted in pfm_ctx_device_bytes. */
+int pfm_cod_buckets(pfm_ctx *ctx, const uint8_t *cell_owned, int n_buckets, double x_lo, double x_hi, int n_sub,
+                    double *values /* host out [n_buckets] */, double *volume /* host out [n_buckets] */);
+
+/* The point evaluation behind compute_point_stress (cracks.cc:3285-3320: GridTools::find_active_cell_around_point, then
+ * values / gradients of the solution at the point) and compute_point_value (cracks.cc:3264-3283).
+ *   points  host [n_points][dim]
+ *   cell    host out [n_points]: the cell the point was evaluated in, or -1
+ *   values  host out [n_points][dim+1] or NULL: the Q1 interpolant of (u_0 .. u_{dim-1}, phi)
+ *   grads   host out [n_points][dim+1][dim] or NULL: grads[p][c][d] = d(component c) / d x_d
+ * Cell rule (a DEVIATION from deal.II, which walks the cells around the vertex closest to the point): cell[p] is the
+ * LOWEST-numbered cell with cell_owned[cell] != 0 (NULL = every local cell) for which the Newton inverse of the Q1 map
+ * converges to a xi with every coordinate in [-1e-10, 1 + 1e-10] (find_active_cell_around_point's default tolerance).  The
+ * inverse is attempted only for cells whose vertex bounding box, inflated by 1e-8 * the cell diameter, contains the point;
+ * it starts at the cell centre, takes at most 20 steps and has converged when a step is at most 1e-12 in every coordinate; an
+ * inverse that does not converge is no candidate.  Inside a cell both rules pick that cell; on a face or a vertex the
+ * gradient is discontinuous and the reference's choice depends on the rank, this one on the cell numbers only.
+ * Evaluation: xi is clamped to the unit cell (project_to_unit_cell, cracks.cc:3306).  The entries of a point without a cell
+ * are written as 0.0.  On a partitioned context the caller passes its owned-cell mask and takes the values of the rank
+ * whose cell >= 0 (Utilities::MPI::max in the reference).
+ * PFM_ERR_BAD_ARG with nothing launched and the outputs untouched: n_points outside 0 .. 4096, a non-finite coordinate, a
+ * NULL points or cell.  Integer atomics only: deterministic. */
+int pfm_point_eval(pfm_ctx *ctx, const uint8_t *cell_owned, int n_points, const double *points /* host [n_points][dim] */,
+                   int32_t *cell /* host out [n_points] */, double *values /* host out [n_points][dim+1] or NULL */,
+                   double *grads /* host out [n_points][dim+1][dim] or NULL */);
 
 /* VectorTools::integrate_difference(..., ExactPhiSneddon(alpha_eps), QGauss<dim>(3), L2_norm, phi only) (cracks.cc:4495-4516,
  * 418-450; exact phi = 1 - exp(-dist / alpha_eps), dist = distance to the segment [-1, 1] x {0}, alpha_eps of pfm_set_params):

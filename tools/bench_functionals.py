@@ -5,6 +5,9 @@
                          different eps every call forces the rebuild) and cached (value pass only)
   pfm_face_load          the x = +10 face of the box (216^2 faces)
   pfm_sneddon_phi_error  every cell
+  pfm_point_eval         1 point and 4096 points (the cell search is a sweep over every cell)
+  pfm_cod_buckets        the reference's call (75, -1.5, 1.5, 100) on a 2-D box of --buckets-2d-n^2 cells and on a 3-D box of
+                         --buckets-3d-n^3 cells over [-1.5, 1.5]^dim (1e4 / 1e6 sample points per cell), --buckets-reps calls
 
 HIP events around each (synchronous) call, median of --reps calls.  For context, the numpy restatement
 (tests/postproc_ref.py) of ONE compute_cod line on a small box.  Prints one JSON line.
@@ -30,6 +33,9 @@ def main():
     ap.add_argument("--n", type=int, default=216)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--np-n", type=int, default=24, help="cells per axis of the numpy comparison box")
+    ap.add_argument("--buckets-2d-n", type=int, default=1000)
+    ap.add_argument("--buckets-3d-n", type=int, default=32)
+    ap.add_argument("--buckets-reps", type=int, default=3)
     args = ap.parse_args()
 
     import torch
@@ -55,9 +61,9 @@ def main():
     faces = np.ones(cells.size, np.uint8)
     lines = S.cod_lines()
 
-    def timed(fn):
+    def timed(fn, reps=None):
         ts = []
-        for _ in range(args.reps):
+        for _ in range(reps or args.reps):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             a.record()
@@ -83,6 +89,32 @@ def main():
     ctx.sneddon_phi_error_sq()
     phi_err = timed(lambda: ctx.sneddon_phi_error_sq())
 
+    rng = np.random.default_rng(0)
+    pts = rng.uniform(-9.9, 9.9, (4096, dim))
+    found = int((ctx.point_eval(pts)[0] >= 0).sum())
+    pe1 = timed(lambda: ctx.point_eval(pts[:1]))
+    pe4096 = timed(lambda: ctx.point_eval(pts))
+    del ctx
+
+    buckets = {}
+    for bdim, bn in ((2, args.buckets_2d_n), (3, args.buckets_3d_n)):
+        bmesh = M.box_mesh(bdim, bn, lo=-1.5, hi=1.5)
+        x = bmesh.coords
+        bu = np.stack([1e-3 * np.sin(x[:, c]) * x[:, (c + 1) % bdim] for c in range(bdim)], axis=1)
+        bphi = 0.5 + 0.5 * np.tanh(4.0 * np.abs(x[:, 1]) - 0.3)
+        blay = M.DofLayout(bmesh.n_nodes, bdim, blocked=True)
+        bsol = blay.pack(bu, bphi)
+        bctx = Context(bmesh, True)
+        bctx.set_params(bench.sneddon_params(bmesh.min_cell_diameter(), bdim))
+        bctx.state_set_host(bsol, bsol, bsol)
+        bctx.cod_buckets(75, -1.5, 1.5, 2)  # warm-up (module load)
+        t = timed(lambda: bctx.cod_buckets(), args.buckets_reps)
+        n_points = bmesh.n_cells * 100 ** bdim
+        buckets["%dd" % bdim] = {"n_cells": int(bmesh.n_cells), "n_sub": 100, "points": int(n_points), "cod_buckets_ms": t[0],
+                                 "cod_buckets_min_ms": t[1], "ns_per_1e3_points": 1e9 * t[0] / n_points,
+                                 "volume": float(bctx.cod_buckets()[1].sum())}
+        del bctx
+
     small = M.box_mesh(3, args.np_n, lo=-1.5, hi=1.5)
     slay = M.DofLayout(small.n_nodes, 3, blocked=True)
     ssol = slay.pack(np.zeros((small.n_nodes, 3)), np.ones(small.n_nodes))
@@ -97,6 +129,8 @@ def main():
         "cod_cached_min_ms": cod_cached[1], "face_load_ms": load[0], "face_load_min_ms": load[1],
         "phi_error_ms": phi_err[0], "phi_error_min_ms": phi_err[1], "reps": args.reps,
         "numpy_one_line_s": t_np, "numpy_one_line_cells": int(small.n_cells),
+        "point_eval_1_ms": pe1[0], "point_eval_1_min_ms": pe1[1], "point_eval_4096_ms": pe4096[0],
+        "point_eval_4096_min_ms": pe4096[1], "point_eval_found": found, "cod_buckets": buckets,
     }))
 
 
