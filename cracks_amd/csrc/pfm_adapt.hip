@@ -8,12 +8,13 @@
 //   pfm_indicator_select    the threshold of refine_and_coarsen_fixed_number (and pfm_indicator_count for a distributed host)
 //   pfm_refine_flags_mix    RefinementStrategy::mix                        cracks.cc:4043-4116
 //
-// The first three are memory-bound gathers over the vertex-major cell table.  Counts and minima are fixed-order two-stage
-// reductions, the transfer's weights are powers of two added in a fixed order and every node has one writer: repeated
-// calls are bitwise identical.
-#include "pfm_internal.h"
+// The first three are memory-bound gathers over the vertex-major cell table.  Counts and minima are the two-stage
+// reductions of pfm_reduce.h, the transfer's weights are powers of two added in a fixed order and every node has one writer:
+// repeated calls are bitwise identical.  Cell geometry, q1_weight and dof_of are pfm_q1_point.h, the host helpers pfm_entry.h.
+#include "pfm_entry.h"
+#include "pfm_q1_point.h"
+#include "pfm_reduce.h"
 
-#include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -36,6 +37,20 @@ namespace pfm
       int use_box, max_level;
     };
 
+    RefineCrit make_crit(const pfm_refine_criteria &crit, int max_level)
+    {
+      RefineCrit cr{};
+      cr.thr = crit.phi_threshold;
+      cr.use_box = crit.use_box != 0;
+      cr.max_level = max_level;
+      for (int d = 0; d < 3; ++d)
+        {
+          cr.lo[d] = crit.box_lo[d];
+          cr.hi[d] = crit.box_hi[d];
+        }
+      return cr;
+    }
+
     struct XferVecs
     {
       const double *src[XFER_MAX_VECTORS];
@@ -50,7 +65,6 @@ namespace pfm
                                                           unsigned long long *__restrict__ partial)
     {
       constexpr int nv = 1 << dim;
-      __shared__ unsigned s_cnt[4];
       const long long cell = (long long)blockIdx.x * blockDim.x + threadIdx.x;
       int f = 0;
       if (cell < v.n_cells && (!cell_owned || cell_owned[cell]))
@@ -79,31 +93,9 @@ namespace pfm
         }
       if (cell < v.n_cells)
         flags[cell] = (uint8_t)f;
-      const unsigned long long m = __ballot(f);
-      if ((threadIdx.x & 63) == 0)
-        s_cnt[threadIdx.x >> 6] = (unsigned)__popcll(m);
-      __syncthreads();
+      const unsigned long long total = block_count(f);
       if (threadIdx.x == 0)
-        partial[blockIdx.x] = (unsigned long long)s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    }
-
-    __global__ __launch_bounds__(256) void k_sum_counts(const unsigned long long *__restrict__ partial, long long n,
-                                                        unsigned long long *__restrict__ out)
-    {
-      __shared__ unsigned long long s[256];
-      unsigned long long r = 0;
-      for (long long i = threadIdx.x; i < n; i += 256)
-        r += partial[i];
-      s[threadIdx.x] = r;
-      __syncthreads();
-      for (int w = 128; w >= 1; w >>= 1)
-        {
-          if ((int)threadIdx.x < w)
-            s[threadIdx.x] += s[threadIdx.x + w];
-          __syncthreads();
-        }
-      if (threadIdx.x == 0)
-        out[0] = s[0];
+        partial[blockIdx.x] = total;
     }
 
     // square of cell->diameter(): the largest of the 2^(dim-1) vertex diagonals, every operation rounded on its own
@@ -128,56 +120,21 @@ namespace pfm
       return best;
     }
 
-    template <int dim>
-    __device__ __forceinline__ void load_vertices(const DevView &v, long long cell, double x[1 << dim][dim])
-    {
-#pragma unroll
-      for (int b = 0; b < (1 << dim); ++b)
-        {
-          const int n = v.conn[(long long)b * v.n_cells + cell];
-#pragma unroll
-          for (int d = 0; d < dim; ++d)
-            x[b][d] = v.coords[(long long)d * v.n_nodes + n];
-        }
-    }
-
     // ---- minimum of diameter^2 over the masked cells (the root is taken once, on the host)
     template <int dim>
     __global__ __launch_bounds__(256) void k_min_diameter_sq(DevView v, const uint8_t *__restrict__ cell_owned, double *__restrict__ partial)
     {
-      __shared__ double s_min[4];
       const long long cell = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-      double r = HUGE_VAL;
+      double r[1] = {HUGE_VAL};
       if (cell < v.n_cells && (!cell_owned || cell_owned[cell]))
         {
           double x[1 << dim][dim];
-          load_vertices<dim>(v, cell, x);
-          r = diameter_sq<dim>(x);
+          load_geometry<dim>(v, cell, x);
+          r[0] = diameter_sq<dim>(x);
         }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1)
-        r = fmin(r, __shfl_xor(r, off));
-      if ((threadIdx.x & 63) == 0)
-        s_min[threadIdx.x >> 6] = r;
-      __syncthreads();
+      const double m = block_reduce(r, Min{});
       if (threadIdx.x == 0)
-        partial[blockIdx.x] = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
-    }
-
-    __global__ __launch_bounds__(256) void k_min_reduce(const double *__restrict__ partial, long long n, double *__restrict__ out)
-    {
-      __shared__ double s_min[4];
-      double r = HUGE_VAL;
-      for (long long i = threadIdx.x; i < n; i += 256)
-        r = fmin(r, partial[i]);
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1)
-        r = fmin(r, __shfl_xor(r, off));
-      if ((threadIdx.x & 63) == 0)
-        s_min[threadIdx.x >> 6] = r;
-      __syncthreads();
-      if (threadIdx.x == 0)
-        out[0] = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
+        partial[blockIdx.x] = m;
     }
 
     // reference coordinate of vertex vtx of a dst cell inside its parent: (child bit d + vertex bit d) / 2, or the vertex
@@ -186,16 +143,6 @@ namespace pfm
     {
       const int vb = (vtx >> d) & 1;
       return child == 255 ? (double)vb : 0.5 * (double)(((child >> d) & 1) + vb);
-    }
-
-    template <int dim>
-    __device__ __forceinline__ double q1_weight(int b, const double xi[dim])
-    {
-      double w = 1.0;
-#pragma unroll
-      for (int d = 0; d < dim; ++d)
-        w *= ((b >> d) & 1) ? xi[d] : (1.0 - xi[d]);
-      return w;
     }
 
     // ---- transfer, pass 1: thread <-> dst cell.  Checks the relation against the coordinates (bad[0] = 1 on a mismatch)
@@ -217,7 +164,7 @@ namespace pfm
           return;
         }
       double xs[nv][dim];
-      load_vertices<dim>(s, p, xs);
+      load_geometry<dim>(s, p, xs);
       const double tol = 1e-10 * sqrt(diameter_sq<dim>(xs));
       bool ok = true;
 #pragma unroll
@@ -251,13 +198,6 @@ namespace pfm
         }
       if (!ok)
         bad[0] = 1;
-    }
-
-    __device__ __forceinline__ long long dof_of(int layout, int dim, long long n_nodes, long long node, int comp)
-    {
-      if (layout == PFM_LAYOUT_INTERLEAVED)
-        return node * (dim + 1) + comp;
-      return comp < dim ? node * dim + comp : n_nodes * dim + node;
     }
 
     // ---- transfer, pass 2: thread <-> (vertex, dst cell) in the order of the cell table; the thread of the node's owner
@@ -313,58 +253,6 @@ namespace pfm
               dst[dof_of(d.layout, dim, d.n_nodes, n, comp)] = val;
             }
         }
-    }
-
-    int fail(pfm_ctx *c, int code, const std::string &msg)
-    {
-      if (c)
-        c->err = msg;
-      return code;
-    }
-
-    // the context's adaptation scratch, at least `bytes` large (grow-only; contents undefined)
-    int adapt_scratch(pfm_ctx *c, size_t bytes, char **p)
-    {
-      if (!c->d_adapt || c->adapt_bytes < bytes)
-        {
-          if (c->d_adapt)
-            {
-              (void)hipStreamSynchronize(c->stream);
-              c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), c->d_adapt), c->allocs.end());
-              (void)hipFree(c->d_adapt);
-              c->d_adapt = nullptr;
-              c->adapt_bytes = 0;
-            }
-          if (hipMalloc(&c->d_adapt, std::max<size_t>(bytes, 256)) != hipSuccess)
-            {
-              c->d_adapt = nullptr;
-              return fail(c, PFM_ERR_NOMEM, "hipMalloc adaptation scratch");
-            }
-          c->allocs.push_back(c->d_adapt);
-          c->adapt_bytes = std::max<size_t>(bytes, 256);
-        }
-      *p = static_cast<char *>(c->d_adapt);
-      return PFM_OK;
-    }
-
-    constexpr size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-    int upload_mask(pfm_ctx *c, const uint8_t *cell_owned, uint8_t **d_owned)
-    {
-      *d_owned = nullptr;
-      if (!cell_owned)
-        return PFM_OK;
-      if (!c->d_cell_owned)
-        {
-          if (hipMalloc((void **)&c->d_cell_owned, (size_t)std::max<long long>(c->v.n_cells, 1)) != hipSuccess)
-            return fail(c, PFM_ERR_NOMEM, "hipMalloc cell mask");
-          c->allocs.push_back(c->d_cell_owned);
-        }
-      if (c->v.n_cells > 0 &&
-          hipMemcpyAsync(c->d_cell_owned, cell_owned, (size_t)c->v.n_cells, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return fail(c, PFM_ERR_HIP, "cell mask upload");
-      *d_owned = c->d_cell_owned;
-      return PFM_OK;
     }
 
     // =================================================================================================================
@@ -1040,7 +928,6 @@ namespace pfm
                                                        const uint8_t *__restrict__ cell_level, uint8_t *__restrict__ flags,
                                                        unsigned long long *__restrict__ partial)
     {
-      __shared__ unsigned s_cnt[4];
       const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
       int f = 0;
       if (i < n)
@@ -1050,12 +937,9 @@ namespace pfm
             f = 0;
           flags[i] = (uint8_t)f;
         }
-      const unsigned long long m = __ballot(f);
-      if ((threadIdx.x & 63) == 0)
-        s_cnt[threadIdx.x >> 6] = (unsigned)__popcll(m);
-      __syncthreads();
+      const unsigned long long total = block_count(f);
       if (threadIdx.x == 0)
-        partial[blockIdx.x] = (unsigned long long)s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        partial[blockIdx.x] = total;
     }
 
     unsigned stride_grid(long long n) { return (unsigned)std::min<long long>(std::max<long long>((n + 255) / 256, 1), 2048); }
@@ -1106,22 +990,13 @@ namespace pfm
       bool ok = hipMemsetAsync(occ, 0xff, sizeof(uint32_t) * 2 * cap, st) == hipSuccess && hipMemsetAsync(counter, 0, 256, st) == hipSuccess;
       if (ok && nb)
         {
-          if (dim == 2)
-            {
-              hipLaunchKernelGGL(k_ft_insert<2>, dim3(nb), dim3(256), 0, st, c->v, occ_a, occ_b, cap - 1);
-              hipLaunchKernelGGL(k_ft_match<2>, dim3(nb), dim3(256), 0, st, c->v, occ_a, occ_b, cap - 1, nbr, rel);
-              if (hanging)
-                hipLaunchKernelGGL(k_ft_hanging<2>, dim3(nb), dim3(256), 0, st, c->v, occ_a, occ_b, cap - 1, nbr, rel, coarse_of);
-            }
-          else
-            {
-              hipLaunchKernelGGL(k_ft_insert<3>, dim3(nb), dim3(256), 0, st, c->v, occ_a, occ_b, cap - 1);
-              hipLaunchKernelGGL(k_ft_match<3>, dim3(nb), dim3(256), 0, st, c->v, occ_a, occ_b, cap - 1, nbr, rel);
-              if (hanging)
-                hipLaunchKernelGGL(k_ft_hanging<3>, dim3(nb), dim3(256), 0, st, c->v, occ_a, occ_b, cap - 1, nbr, rel, coarse_of);
-            }
+          PFM_LAUNCH_DIM(dim, k_ft_insert, dim3(nb), dim3(256), st, c->v, occ_a, occ_b, cap - 1);
+          PFM_LAUNCH_DIM(dim, k_ft_match, dim3(nb), dim3(256), st, c->v, occ_a, occ_b, cap - 1, nbr, rel);
           if (hanging)
-            hipLaunchKernelGGL(k_ft_number_coarse, dim3(nb), dim3(256), 0, st, n_faces, rel, nbr, counter);
+            {
+              PFM_LAUNCH_DIM(dim, k_ft_hanging, dim3(nb), dim3(256), st, c->v, occ_a, occ_b, cap - 1, nbr, rel, coarse_of);
+              hipLaunchKernelGGL(k_ft_number_coarse, dim3(nb), dim3(256), 0, st, n_faces, rel, nbr, counter);
+            }
           ok = hipGetLastError() == hipSuccess;
         }
       ok = ok && hipMemcpyAsync(&n_coarse, counter, sizeof(unsigned), hipMemcpyDeviceToHost, st) == hipSuccess &&
@@ -1167,10 +1042,7 @@ namespace pfm
         return PFM_OK;
       const FaceTab ft{c->d_face_nbr, c->d_face_rel, c->d_face_sub};
       const unsigned nb = (unsigned)((NC + 127) / 128);
-      if (c->v.dim == 2)
-        hipLaunchKernelGGL(k_kelly<2>, dim3(nb), dim3(128), 0, c->stream, c->v, ft, d_owned, mask, d_eta);
-      else
-        hipLaunchKernelGGL(k_kelly<3>, dim3(nb), dim3(128), 0, c->stream, c->v, ft, d_owned, mask, d_eta);
+      PFM_LAUNCH_DIM(c->v.dim, k_kelly, dim3(nb), dim3(128), c->stream, c->v, ft, d_owned, mask, d_eta);
       return hipGetLastError() == hipSuccess ? PFM_OK : fail(c, PFM_ERR_HIP, "k_kelly launch");
     }
 
@@ -1246,22 +1118,14 @@ extern "C"
       return fail(c, PFM_ERR_BAD_ARG, "pfm_refine_flags: NULL flags, or a level limit without cell levels");
     if (crit->max_level > 255)
       return fail(c, PFM_ERR_BAD_ARG, "pfm_refine_flags: max_level does not fit the level bytes");
-    RefineCrit cr{};
-    cr.thr = crit->phi_threshold;
-    cr.use_box = crit->use_box != 0;
-    cr.max_level = crit->max_level;
-    for (int d = 0; d < 3; ++d)
-      {
-        cr.lo[d] = crit->box_lo[d];
-        cr.hi[d] = crit->box_hi[d];
-      }
+    const RefineCrit cr = make_crit(*crit, crit->max_level);
     (void)hipSetDevice(c->device);
     const unsigned nb = (unsigned)((NC + 255) / 256);
     // scratch: flags [NC] | levels [NC] | block counts [nb] + the total
     const size_t o_level = align256((size_t)NC), o_part = o_level + align256((size_t)NC);
-    char *base = nullptr;
-    if (int rc = adapt_scratch(c, o_part + sizeof(unsigned long long) * ((size_t)nb + 1), &base))
+    if (int rc = dev_buf_reserve(c, c->buf_adapt, o_part + sizeof(unsigned long long) * ((size_t)nb + 1), "adaptation scratch"))
       return rc;
+    char *base = c->buf_adapt.as<char>();
     uint8_t *d_flags = reinterpret_cast<uint8_t *>(base), *d_level = nullptr;
     unsigned long long *d_part = reinterpret_cast<unsigned long long *>(base + o_part);
     uint8_t *d_owned = nullptr;
@@ -1274,13 +1138,9 @@ extern "C"
           return fail(c, PFM_ERR_HIP, "cell level upload");
       }
     if (nb)
-      {
-        if (c->v.dim == 2)
-          hipLaunchKernelGGL(k_refine_flags<2>, dim3(nb), dim3(256), 0, c->stream, c->v, cr, d_owned, d_level, d_flags, d_part);
-        else
-          hipLaunchKernelGGL(k_refine_flags<3>, dim3(nb), dim3(256), 0, c->stream, c->v, cr, d_owned, d_level, d_flags, d_part);
-      }
-    hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(256), 0, c->stream, d_part, (long long)nb, d_part + nb);
+      PFM_LAUNCH_DIM(c->v.dim, k_refine_flags, dim3(nb), dim3(256), c->stream, c->v, cr, d_owned, d_level, d_flags, d_part);
+    hipLaunchKernelGGL((k_reduce_final<unsigned long long, 1, Sum<unsigned long long>>), dim3(1), dim3(256), 0, c->stream, d_part,
+                       (long long)nb, d_part + nb);
     if (hipGetLastError() != hipSuccess)
       return fail(c, PFM_ERR_HIP, "k_refine_flags launch");
     unsigned long long total = 0;
@@ -1298,21 +1158,15 @@ extern "C"
       return c ? fail(c, PFM_ERR_BAD_ARG, "pfm_min_cell_diameter: NULL output") : PFM_ERR_BAD_ARG;
     (void)hipSetDevice(c->device);
     const unsigned nb = (unsigned)((c->v.n_cells + 255) / 256);
-    char *base = nullptr;
-    if (int rc = adapt_scratch(c, sizeof(double) * ((size_t)nb + 1), &base))
+    if (int rc = dev_buf_reserve(c, c->buf_adapt, sizeof(double) * ((size_t)nb + 1), "adaptation scratch"))
       return rc;
-    double *d_part = reinterpret_cast<double *>(base);
+    double *d_part = c->buf_adapt.as<double>();
     uint8_t *d_owned = nullptr;
     if (int rc = upload_mask(c, cell_owned, &d_owned))
       return rc;
     if (nb)
-      {
-        if (c->v.dim == 2)
-          hipLaunchKernelGGL(k_min_diameter_sq<2>, dim3(nb), dim3(256), 0, c->stream, c->v, d_owned, d_part);
-        else
-          hipLaunchKernelGGL(k_min_diameter_sq<3>, dim3(nb), dim3(256), 0, c->stream, c->v, d_owned, d_part);
-      }
-    hipLaunchKernelGGL(k_min_reduce, dim3(1), dim3(256), 0, c->stream, d_part, (long long)nb, d_part + nb);
+      PFM_LAUNCH_DIM(c->v.dim, k_min_diameter_sq, dim3(nb), dim3(256), c->stream, c->v, d_owned, d_part);
+    hipLaunchKernelGGL((k_reduce_final<double, 1, Min>), dim3(1), dim3(256), 0, c->stream, d_part, (long long)nb, d_part + nb);
     if (hipGetLastError() != hipSuccess)
       return fail(c, PFM_ERR_HIP, "k_min_diameter_sq launch");
     double sq = 0.0;
@@ -1356,9 +1210,9 @@ extern "C"
     const size_t o_owner = align256(sizeof(int32_t) * (size_t)NC);
     const size_t o_child = o_owner + align256(sizeof(int32_t) * (size_t)dst->v.n_nodes);
     const size_t o_bad = o_child + align256((size_t)NC);
-    char *base = nullptr;
-    if (int rc = adapt_scratch(dst, o_bad + 256, &base))
+    if (int rc = dev_buf_reserve(dst, dst->buf_adapt, o_bad + 256, "adaptation scratch"))
       return rc;
+    char *base = dst->buf_adapt.as<char>();
     int32_t *d_parent = reinterpret_cast<int32_t *>(base), *d_owner = reinterpret_cast<int32_t *>(base + o_owner);
     uint8_t *d_child = reinterpret_cast<uint8_t *>(base + o_child);
     int *d_bad = reinterpret_cast<int *>(base + o_bad);
@@ -1372,10 +1226,7 @@ extern "C"
         hipMemsetAsync(d_bad, 0, sizeof(int), st) != hipSuccess)
       return fail(dst, PFM_ERR_HIP, "pfm_state_transfer: relation upload");
     const unsigned nbc = (unsigned)((NC + 255) / 256);
-    if (dim == 2)
-      hipLaunchKernelGGL(k_xfer_check<2>, dim3(nbc), dim3(256), 0, st, src->v, dst->v, d_parent, d_child, d_owner, d_bad);
-    else
-      hipLaunchKernelGGL(k_xfer_check<3>, dim3(nbc), dim3(256), 0, st, src->v, dst->v, d_parent, d_child, d_owner, d_bad);
+    PFM_LAUNCH_DIM(dim, k_xfer_check, dim3(nbc), dim3(256), st, src->v, dst->v, d_parent, d_child, d_owner, d_bad);
     if (hipGetLastError() != hipSuccess)
       return fail(dst, PFM_ERR_HIP, "k_xfer_check launch");
     int bad = 0;
@@ -1387,10 +1238,7 @@ extern "C"
                   "range, or a vertex off the Q1 image of its parent)");
     const long long n_threads = NC * nv;
     const unsigned nbw = (unsigned)((n_threads + 255) / 256);
-    if (dim == 2)
-      hipLaunchKernelGGL(k_xfer_write<2>, dim3(nbw), dim3(256), 0, st, src->v, dst->v, d_parent, d_child, d_owner, vecs);
-    else
-      hipLaunchKernelGGL(k_xfer_write<3>, dim3(nbw), dim3(256), 0, st, src->v, dst->v, d_parent, d_child, d_owner, vecs);
+    PFM_LAUNCH_DIM(dim, k_xfer_write, dim3(nbw), dim3(256), st, src->v, dst->v, d_parent, d_child, d_owner, vecs);
     if (hipGetLastError() != hipSuccess)
       return fail(dst, PFM_ERR_HIP, "k_xfer_write launch");
     return PFM_OK;
@@ -1421,9 +1269,9 @@ extern "C"
     if (!d_ind || !threshold || !counts || k < 1 || k > NC)
       return fail(c, PFM_ERR_BAD_ARG, "pfm_indicator_select: NULL array or output, or k outside [1, n_cells]");
     (void)hipSetDevice(c->device);
-    char *work = nullptr;
-    if (int rc = adapt_scratch(c, SELECT_WORK_BYTES, &work))
+    if (int rc = dev_buf_reserve(c, c->buf_adapt, SELECT_WORK_BYTES, "adaptation scratch"))
       return rc;
+    char *work = c->buf_adapt.as<char>();
     uint8_t *d_owned = nullptr;
     if (int rc = upload_mask(c, cell_owned, &d_owned))
       return rc;
@@ -1443,9 +1291,9 @@ extern "C"
     if ((NC > 0 && !d_ind) || !counts)
       return fail(c, PFM_ERR_BAD_ARG, "pfm_indicator_count: NULL array or output");
     (void)hipSetDevice(c->device);
-    char *work = nullptr;
-    if (int rc = adapt_scratch(c, SELECT_WORK_BYTES, &work))
+    if (int rc = dev_buf_reserve(c, c->buf_adapt, SELECT_WORK_BYTES, "adaptation scratch"))
       return rc;
+    char *work = c->buf_adapt.as<char>();
     uint8_t *d_owned = nullptr;
     if (int rc = upload_mask(c, cell_owned, &d_owned))
       return rc;
@@ -1478,15 +1326,7 @@ extern "C"
       return fail(c, PFM_ERR_UNSUPPORTED,
                   "pfm_refine_flags_mix: partitioned context (the fraction is of the global cell count: compose pfm_refine_flags, "
                   "pfm_kelly_indicator and pfm_indicator_count)");
-    RefineCrit cr{};
-    cr.thr = crit->phi_threshold;
-    cr.use_box = crit->use_box != 0;
-    cr.max_level = -1; // (a): without the level limit; (d) applies it at the end
-    for (int d = 0; d < 3; ++d)
-      {
-        cr.lo[d] = crit->box_lo[d];
-        cr.hi[d] = crit->box_hi[d];
-      }
+    const RefineCrit cr = make_crit(*crit, -1); // (a): without the level limit; (d) applies it at the end
     (void)hipSetDevice(c->device);
     if (int rc = ensure_face_table(c))
       return rc;
@@ -1495,9 +1335,9 @@ extern "C"
     const size_t o_level = align256((size_t)NC), o_eta = o_level + align256((size_t)NC);
     const size_t o_part = o_eta + align256(sizeof(double) * (size_t)NC);
     const size_t o_sel = o_part + align256(sizeof(unsigned long long) * ((size_t)nb + 1));
-    char *base = nullptr;
-    if (int rc = adapt_scratch(c, o_sel + SELECT_WORK_BYTES, &base))
+    if (int rc = dev_buf_reserve(c, c->buf_adapt, o_sel + SELECT_WORK_BYTES, "adaptation scratch"))
       return rc;
+    char *base = c->buf_adapt.as<char>();
     uint8_t *d_flags = reinterpret_cast<uint8_t *>(base), *d_level = nullptr;
     double *d_eta = reinterpret_cast<double *>(base + o_eta);
     unsigned long long *d_part = reinterpret_cast<unsigned long long *>(base + o_part);
@@ -1515,10 +1355,7 @@ extern "C"
     double t = HUGE_VAL;
     if (nb)
       {
-        if (c->v.dim == 2)
-          hipLaunchKernelGGL(k_refine_flags<2>, dim3(nb), dim3(256), 0, st, c->v, cr, d_owned, (const uint8_t *)nullptr, d_flags, d_part);
-        else
-          hipLaunchKernelGGL(k_refine_flags<3>, dim3(nb), dim3(256), 0, st, c->v, cr, d_owned, (const uint8_t *)nullptr, d_flags, d_part);
+        PFM_LAUNCH_DIM(c->v.dim, k_refine_flags, dim3(nb), dim3(256), st, c->v, cr, d_owned, (const uint8_t *)nullptr, d_flags, d_part);
         if (hipGetLastError() != hipSuccess)
           return fail(c, PFM_ERR_HIP, "k_refine_flags launch");
         if (k >= 1)
@@ -1537,7 +1374,8 @@ extern "C"
           return fail(c, PFM_ERR_HIP, "indicator clear");
         hipLaunchKernelGGL(k_mix_flags, dim3(nb), dim3(256), 0, st, NC, d_eta, t, (int)crit->max_level, d_level, d_flags, d_part);
       }
-    hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(256), 0, st, d_part, (long long)nb, d_part + nb);
+    hipLaunchKernelGGL((k_reduce_final<unsigned long long, 1, Sum<unsigned long long>>), dim3(1), dim3(256), 0, st, d_part, (long long)nb,
+                       d_part + nb);
     if (hipGetLastError() != hipSuccess)
       return fail(c, PFM_ERR_HIP, "k_mix_flags launch");
     unsigned long long total = 0;

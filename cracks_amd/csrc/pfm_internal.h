@@ -283,6 +283,18 @@ namespace pfm
                             const int32_t *rows, const long long *ptr, const HgEntry *list, int64_t n_rows, hipStream_t s);
   int launch_zero_rows(const DevView &v, double *const *d_values, const int32_t *rows, int n_rows, hipStream_t s);
   int launch_patch_slots(const DevView &v, unsigned long long *d_slots, int n_blocks, hipStream_t s);
+
+  // a grow-only device buffer of the context (dev_buf_reserve, pfm_entry.h): in pfm_ctx::allocs, counted in device_bytes
+  struct DevBuf
+  {
+    void *p = nullptr;
+    size_t bytes = 0;
+    template <class T>
+    T *as() const
+    {
+      return static_cast<T *>(p);
+    }
+  };
 } // namespace pfm
 
 struct pfm_ctx
@@ -375,8 +387,8 @@ struct pfm_ctx
   int32_t *d_color_cells_reduced = nullptr; // colour-sorted cells that touch a row the patches do not write
   std::vector<long long> color_ptr_reduced;
   uint8_t *d_cell_ring_reduced = nullptr;
-  // scratch of the Newton-side sweeps (pfm_newton.hip)
-  unsigned long long *d_counts = nullptr;
+  // scratch of the Newton-side sweeps (pfm_newton.hip): the 3 counts of pfm_active_set_device
+  pfm::DevBuf buf_counts;
   // gather tables of the cells at hanging vertices (DevView::hs_*): destination rows, their entry lists (hc * 32 + index:
   // index < 16 = resolved node i of cell hc, 16 + a = the hanging vertex a's own row), ascending per row
   int32_t *d_hg_rows = nullptr;
@@ -386,11 +398,10 @@ struct pfm_ctx
   int64_t n_hcells = 0;           // cells at hanging vertices (records of DevView::cres)
   bool hang_gather = false;       // decided at pfm_ctx_create (PFM_HANGING_ATOMIC=1: off)
   bool hang_gather_ready = false; // tables and scratch exist
-  double *d_norm_partial = nullptr; // pfm_residual_norms: [2048][2] block partials + the 3 results
-  double *d_partial = nullptr;
-  int64_t n_partial = 0;
-  uint8_t *d_cell_owned = nullptr;
-  double *d_func_mat = nullptr; // per-cell Lame override of pfm_functionals_material
+  pfm::DevBuf buf_norm_partial; // pfm_residual_norms: [2048][2] block partials + the 3 results
+  pfm::DevBuf buf_partial;      // 3-wide reductions of pfm_newton.hip / pfm_postproc.hip: [blocks][3] partials + the 3 results
+  pfm::DevBuf buf_cell_owned;   // the owned-cell mask of the entry that runs (upload_mask, pfm_entry.h)
+  pfm::DevBuf buf_func_mat;     // per-cell Lame override of pfm_functionals_material
   // post-processing functionals (pfm_postproc.hip): the (line, cell, face) list of pfm_cod_lines, kept for the lines, eps
   // and cell mask it was built for (the mesh geometry of a context never changes).  Device buffers are in `allocs`.
   struct CodCache
@@ -404,15 +415,9 @@ struct pfm_ctx
     long long *d_entry = nullptr;    // [n_entries] cell * 2 dim + face, ordered by line, cell, face
     int64_t n_entries = 0;
   } cod;
-  int32_t *d_face_cells = nullptr; // pfm_face_load input staging (in allocs)
-  uint8_t *d_face_ids = nullptr;
-  int64_t n_face_cap = 0;
-  // mesh adaptation (pfm_adapt.hip): one grow-only scratch buffer (in allocs)
-  void *d_adapt = nullptr;
-  size_t adapt_bytes = 0;
-  // pfm_cod_buckets / pfm_point_eval (pfm_pointstat.hip): one grow-only scratch buffer (in allocs, counted in device_bytes)
-  void *d_stat = nullptr;
-  size_t stat_bytes = 0;
+  pfm::DevBuf buf_face_cells, buf_face_ids; // pfm_face_load input staging
+  pfm::DevBuf buf_adapt;                    // mesh adaptation (pfm_adapt.hip): one scratch buffer
+  pfm::DevBuf buf_stat;                     // pfm_cod_buckets / pfm_point_eval (pfm_pointstat.hip): one scratch buffer
   // face-neighbour table of pfm_kelly_indicator, built on first use (in allocs): neighbour cell or side-list entry and the
   // relation byte per (face, cell), and the fine faces of every face against finer cells
   int32_t *d_face_nbr = nullptr;

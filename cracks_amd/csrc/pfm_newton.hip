@@ -6,13 +6,13 @@
 //                           + constraints_hanging_nodes.distribute    cracks.cc:2888-2890
 //   pfm_functionals         compute_energy, compute_tcv               cracks.cc:3615-3701, 3553-3611
 //
-// All three work on any Q1 mesh (MappingQ1 geometry per cell) with the node state / tables of the context.
-#include "pfm_internal.h"
+// All three work on any Q1 mesh (MappingQ1 geometry per cell) with the node state / tables of the context.  The Q1
+// element is pfm_q1_point.h, the fixed-order reductions are pfm_reduce.h, the host helpers pfm_entry.h.
+#include "pfm_entry.h"
+#include "pfm_q1_point.h"
+#include "pfm_reduce.h"
 
-#include <hip/hip_runtime.h>
 #include <algorithm>
-#include <string>
-#include <vector>
 
 #include "../../include/pfm_newton.h"
 
@@ -20,14 +20,7 @@ namespace pfm
 {
   namespace
   {
-    template <int dim>
-    __device__ __forceinline__ long long dof_of(const DevView &v, int P, int c)
-    {
-      if (v.layout == PFM_LAYOUT_INTERLEAVED)
-        return (long long)P * (dim + 1) + c;
-      return c < dim ? (long long)P * dim + c : (long long)v.n_owned * dim + P;
-    }
-
+    // (k_diag_mass keeps its own Jacobian and determinant: through eval_point the last bits of the 3-D masses change)
     __device__ __forceinline__ double det2(const double J[2][2]) { return J[0][0] * J[1][1] - J[0][1] * J[1][0]; }
     __device__ __forceinline__ double det3(const double J[3][3])
     {
@@ -173,92 +166,28 @@ namespace pfm
                                                          double *__restrict__ partial /* [gridDim.x][3] */)
     {
       constexpr int nv = 1 << dim, nq = dim == 2 ? 9 : 27;
-      const double gx[3] = {0.5 - 0.5 * 0.7745966692414834, 0.5, 0.5 + 0.5 * 0.7745966692414834};
-      const double gw[3] = {5.0 / 18.0, 8.0 / 18.0, 5.0 / 18.0};
       const long long cell = (long long)blockIdx.x * blockDim.x + threadIdx.x;
       double acc[3] = {0.0, 0.0, 0.0};
       if (cell < v.n_cells && (!cell_owned || cell_owned[cell]))
         {
           double x[nv][dim], U[nv][dim], PH[nv];
-#pragma unroll
-          for (int b = 0; b < nv; ++b)
-            {
-              const int n = v.conn[(long long)b * v.n_cells + cell];
-#pragma unroll
-              for (int d = 0; d < dim; ++d)
-                {
-                  x[b][d] = v.coords[(long long)d * v.n_nodes + n];
-                  U[b][d] = v.u[d][n];
-                }
-              PH[b] = v.phi[n];
-            }
+          load_geometry<dim>(v, cell, x);
+          load_state<dim>(v, cell, U, PH);
           const double lam = lam_over ? lam_over[cell] : (v.cell_lambda ? v.cell_lambda[cell] : prm.lambda);
           const double mu = mu_over ? mu_over[cell] : (v.cell_mu ? v.cell_mu[cell] : prm.mu);
 #pragma unroll 1
           for (int q = 0; q < nq; ++q)
             {
               const int qi[3] = {q % 3, (q / 3) % 3, q / 9};
-              double w = 1.0;
+              double xi[dim], w = 1.0;
 #pragma unroll
               for (int d = 0; d < dim; ++d)
-                w *= gw[qi[d]];
-              double N[nv], dNr[nv][dim];
-#pragma unroll
-              for (int b = 0; b < nv; ++b)
                 {
-                  double val = 1.0;
-#pragma unroll
-                  for (int d = 0; d < dim; ++d)
-                    val *= ((b >> d) & 1) ? gx[qi[d]] : (1.0 - gx[qi[d]]);
-                  N[b] = val;
-#pragma unroll
-                  for (int e = 0; e < dim; ++e)
-                    {
-                      double g = 1.0;
-#pragma unroll
-                      for (int d = 0; d < dim; ++d)
-                        g *= (d == e) ? (((b >> d) & 1) ? 1.0 : -1.0) : (((b >> d) & 1) ? gx[qi[d]] : (1.0 - gx[qi[d]]));
-                      dNr[b][e] = g;
-                    }
+                  xi[d] = gauss_x(qi[d]);
+                  w *= gauss_w(qi[d]);
                 }
-              double J[dim][dim], inv[dim][dim], det;
-#pragma unroll
-              for (int i = 0; i < dim; ++i)
-#pragma unroll
-                for (int j = 0; j < dim; ++j)
-                  {
-                    double s = 0.0;
-#pragma unroll
-                    for (int b = 0; b < nv; ++b)
-                      s += x[b][i] * dNr[b][j];
-                    J[i][j] = s;
-                  }
-              if constexpr (dim == 2)
-                {
-                  det = det2(J);
-                  const double id = 1.0 / det;
-                  inv[0][0] = J[1][1] * id;
-                  inv[0][1] = -J[0][1] * id;
-                  inv[1][0] = -J[1][0] * id;
-                  inv[1][1] = J[0][0] * id;
-                }
-              else
-                {
-                  const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-                  const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-                  const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-                  det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-                  const double id = 1.0 / det;
-                  inv[0][0] = c00 * id;
-                  inv[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-                  inv[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-                  inv[1][0] = c01 * id;
-                  inv[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-                  inv[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-                  inv[2][0] = c02 * id;
-                  inv[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-                  inv[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-                }
+              double N[nv], g[nv][dim], inv[dim][dim];
+              const double det = eval_point<dim>(x, xi, N, g, inv);
               double gu[dim][dim], gpf[dim], uq[dim], pf = 0.0;
 #pragma unroll
               for (int c = 0; c < dim; ++c)
@@ -272,25 +201,15 @@ namespace pfm
 #pragma unroll
               for (int b = 0; b < nv; ++b)
                 {
-                  double g[dim]; // physical gradient of N_b: J^{-T} grad_ref
-#pragma unroll
-                  for (int d = 0; d < dim; ++d)
-                    {
-                      double s = 0.0;
-#pragma unroll
-                      for (int e = 0; e < dim; ++e)
-                        s += inv[e][d] * dNr[b][e];
-                      g[d] = s;
-                    }
                   pf += PH[b] * N[b];
 #pragma unroll
                   for (int c = 0; c < dim; ++c)
                     {
                       uq[c] += U[b][c] * N[b];
-                      gpf[c] += PH[b] * g[c];
+                      gpf[c] += PH[b] * g[b][c];
 #pragma unroll
                       for (int d = 0; d < dim; ++d)
-                        gu[c][d] += U[b][c] * g[d];
+                        gu[c][d] += U[b][c] * g[b][d];
                     }
                 }
               double trE = 0.0, tr_e_2 = 0.0, gg = 0.0, ug = 0.0;
@@ -314,43 +233,10 @@ namespace pfm
               acc[2] += ug * JxW;                                                                                      // cracks.cc:3587
             }
         }
-      // block reduction in a fixed order: lanes by xor-shuffles, waves through LDS
-      __shared__ double s_red[4][3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        {
-          double r = acc[k];
-#pragma unroll
-          for (int off = 32; off >= 1; off >>= 1)
-            r += __shfl_xor(r, off);
-          if ((threadIdx.x & 63) == 0)
-            s_red[threadIdx.x >> 6][k] = r;
-        }
-      __syncthreads();
+      const double r = block_reduce(acc, Sum<double>{});
       if (threadIdx.x < 3)
-        partial[(long long)blockIdx.x * 3 + threadIdx.x] =
-          ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
+        partial[(long long)blockIdx.x * 3 + threadIdx.x] = r;
     }
-
-    __global__ __launch_bounds__(256) void k_reduce3(const double *__restrict__ partial, long long n, double *__restrict__ out)
-    {
-      // second stage: each thread sums a strided slice, then the same fixed-order block reduction
-      __shared__ double s_red[4][3];
-      for (int k = 0; k < 3; ++k)
-        {
-          double r = 0.0;
-          for (long long i = threadIdx.x; i < n; i += 256)
-            r += partial[i * 3 + k];
-          for (int off = 32; off >= 1; off >>= 1)
-            r += __shfl_xor(r, off);
-          if ((threadIdx.x & 63) == 0)
-            s_red[threadIdx.x >> 6][k] = r;
-        }
-      __syncthreads();
-      if (threadIdx.x < 3)
-        out[threadIdx.x] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
-    }
-
 
     // ---- norms of a residual vector with the constrained lines zeroed (constraints_update.set_zero, cracks.cc:2791-2794,
     // 2947-2949): thread <-> owned node, grid-stride over a grid that depends on n_owned only; fixed-order reductions
@@ -371,59 +257,25 @@ namespace pfm
               mx = fmax(mx, fabs(r));
             }
         }
-      __shared__ double s_red[4][2];
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1)
-        {
-          sq += __shfl_xor(sq, off);
-          mx = fmax(mx, __shfl_xor(mx, off));
-        }
-      if ((threadIdx.x & 63) == 0)
-        {
-          s_red[threadIdx.x >> 6][0] = sq;
-          s_red[threadIdx.x >> 6][1] = mx;
-        }
-      __syncthreads();
-      if (threadIdx.x == 0)
-        {
-          partial[2 * (long long)blockIdx.x] = ((s_red[0][0] + s_red[1][0]) + s_red[2][0]) + s_red[3][0];
-          partial[2 * (long long)blockIdx.x + 1] = fmax(fmax(s_red[0][1], s_red[1][1]), fmax(s_red[2][1], s_red[3][1]));
-        }
-    }
-    __global__ __launch_bounds__(256) void k_reduce_norms(const double *__restrict__ partial, int n, double *__restrict__ out)
-    {
-      __shared__ double s_red[4][2];
-      double sq = 0.0, mx = 0.0;
-      for (int i = threadIdx.x; i < n; i += 256)
-        {
-          sq += partial[2 * i];
-          mx = fmax(mx, partial[2 * i + 1]);
-        }
-      for (int off = 32; off >= 1; off >>= 1)
-        {
-          sq += __shfl_xor(sq, off);
-          mx = fmax(mx, __shfl_xor(mx, off));
-        }
-      if ((threadIdx.x & 63) == 0)
-        {
-          s_red[threadIdx.x >> 6][0] = sq;
-          s_red[threadIdx.x >> 6][1] = mx;
-        }
-      __syncthreads();
-      if (threadIdx.x == 0)
-        {
-          const double s2 = ((s_red[0][0] + s_red[1][0]) + s_red[2][0]) + s_red[3][0];
-          out[0] = sqrt(s2);
-          out[1] = fmax(fmax(s_red[0][1], s_red[1][1]), fmax(s_red[2][1], s_red[3][1]));
-          out[2] = s2;
-        }
+      const double acc[2] = {sq, mx};
+      const double r = block_reduce(acc, SumMax{});
+      if (threadIdx.x < 2)
+        partial[2 * (long long)blockIdx.x + threadIdx.x] = r;
     }
 
-    int fail(pfm_ctx *c, int code, const std::string &msg)
+    // second stage of the norms: out = (sqrt(sum), max, sum)
+    __global__ __launch_bounds__(256) void k_reduce_norms(const double *__restrict__ partial, int n, double *__restrict__ out)
     {
-      if (c)
-        c->err = msg;
-      return code;
+      double acc[2];
+      fold_partials(partial, n, acc, SumMax{});
+      const double r = block_reduce(acc, SumMax{});
+      if (threadIdx.x == 0)
+        {
+          out[0] = sqrt(r);
+          out[2] = r;
+        }
+      else if (threadIdx.x == 1)
+        out[1] = r;
     }
   } // namespace
 } // namespace pfm
@@ -443,12 +295,7 @@ extern "C"
     const long long n = c->v.n_cells * nv;
     const unsigned nb = (unsigned)((n + 255) / 256);
     if (nb)
-      {
-        if (c->v.dim == 2)
-          hipLaunchKernelGGL(k_diag_mass<2>, dim3(nb), dim3(256), 0, c->stream, c->v, d_mass);
-        else
-          hipLaunchKernelGGL(k_diag_mass<3>, dim3(nb), dim3(256), 0, c->stream, c->v, d_mass);
-      }
+      PFM_LAUNCH_DIM(c->v.dim, k_diag_mass, dim3(nb), dim3(256), c->stream, c->v, d_mass);
     return hipGetLastError() == hipSuccess ? PFM_OK : fail(c, PFM_ERR_HIP, "k_diag_mass launch");
   }
 
@@ -460,38 +307,27 @@ extern "C"
     if (c->v.n_owned != c->v.n_nodes && c->v.hn_index)
       return fail(c, PFM_ERR_UNSUPPORTED, "hanging nodes on a partitioned mesh");
     (void)hipSetDevice(c->device);
-    if (!c->d_counts)
-      {
-        if (hipMalloc((void **)&c->d_counts, 3 * sizeof(unsigned long long)) != hipSuccess)
-          return fail(c, PFM_ERR_NOMEM, "hipMalloc counts");
-        c->allocs.push_back(c->d_counts);
-      }
-    if (hipMemsetAsync(c->d_counts, 0, 3 * sizeof(unsigned long long), c->stream) != hipSuccess)
+    if (int rc = dev_buf_reserve(c, c->buf_counts, 3 * sizeof(unsigned long long), "counts"))
+      return rc;
+    unsigned long long *d_counts = c->buf_counts.as<unsigned long long>();
+    if (hipMemsetAsync(d_counts, 0, 3 * sizeof(unsigned long long), c->stream) != hipSuccess)
       return fail(c, PFM_ERR_HIP, "counts memset");
     const unsigned nb = (unsigned)((c->v.n_owned + 255) / 256); // 0 on a rank that owns no node: nothing to launch
     uint8_t *flags = const_cast<uint8_t *>(c->v.node_flags);
-    if (nb == 0)
-      ;
-    else if (c->v.dim == 2)
-      hipLaunchKernelGGL(k_active_set<2>, dim3(nb), dim3(256), 0, c->stream, c->v, flags, d_residual_total, d_mass, c_const,
-                         d_solution, d_old_solution, d_cycle_counter, c->d_counts);
-    else
-      hipLaunchKernelGGL(k_active_set<3>, dim3(nb), dim3(256), 0, c->stream, c->v, flags, d_residual_total, d_mass, c_const,
-                         d_solution, d_old_solution, d_cycle_counter, c->d_counts);
+    if (nb)
+      PFM_LAUNCH_DIM(c->v.dim, k_active_set, dim3(nb), dim3(256), c->stream, c->v, flags, d_residual_total, d_mass, c_const,
+                     d_solution, d_old_solution, d_cycle_counter, d_counts);
     if (c->v.hn_index && nb)
       {
         // we might have changed values of the solution, so fix the hanging nodes (cracks.cc:2888-2890)
         const long long n = (long long)c->v.n_owned * (c->v.dim + 1);
         const unsigned nbh = (unsigned)((n + 255) / 256);
-        if (c->v.dim == 2)
-          hipLaunchKernelGGL(k_distribute_hanging<2>, dim3(nbh), dim3(256), 0, c->stream, c->v, d_solution);
-        else
-          hipLaunchKernelGGL(k_distribute_hanging<3>, dim3(nbh), dim3(256), 0, c->stream, c->v, d_solution);
+        PFM_LAUNCH_DIM(c->v.dim, k_distribute_hanging, dim3(nbh), dim3(256), c->stream, c->v, d_solution);
       }
     if (hipGetLastError() != hipSuccess)
       return fail(c, PFM_ERR_HIP, "k_active_set launch");
     unsigned long long h[3];
-    if (hipMemcpyAsync(h, c->d_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+    if (hipMemcpyAsync(h, d_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)
       return fail(c, PFM_ERR_HIP, "counts copy");
     counts[0] = (int64_t)h[0];
@@ -519,21 +355,12 @@ extern "C"
     (void)hipSetDevice(c->device);
     const long long nbl = ((long long)c->v.n_owned + 255) / 256;
     const unsigned nb = (unsigned)std::min<long long>(nbl, NORM_BLOCKS_MAX);
-    if (!c->d_norm_partial)
-      {
-        if (hipMalloc((void **)&c->d_norm_partial, sizeof(double) * (2 * (size_t)NORM_BLOCKS_MAX + 4)) != hipSuccess)
-          return fail(c, PFM_ERR_NOMEM, "hipMalloc norm partial sums");
-        c->allocs.push_back(c->d_norm_partial);
-      }
-    double *d_out = c->d_norm_partial + 2 * (size_t)NORM_BLOCKS_MAX;
+    if (int rc = dev_buf_reserve(c, c->buf_norm_partial, sizeof(double) * (2 * (size_t)NORM_BLOCKS_MAX + 4), "norm partial sums"))
+      return rc;
+    double *d_partial = c->buf_norm_partial.as<double>(), *d_out = d_partial + 2 * (size_t)NORM_BLOCKS_MAX;
     if (nb)
-      {
-        if (c->v.dim == 2)
-          hipLaunchKernelGGL(k_residual_norms<2>, dim3(nb), dim3(256), 0, c->stream, c->v, d_residual, c->d_norm_partial);
-        else
-          hipLaunchKernelGGL(k_residual_norms<3>, dim3(nb), dim3(256), 0, c->stream, c->v, d_residual, c->d_norm_partial);
-      }
-    hipLaunchKernelGGL(k_reduce_norms, dim3(1), dim3(256), 0, c->stream, c->d_norm_partial, (int)nb, d_out);
+      PFM_LAUNCH_DIM(c->v.dim, k_residual_norms, dim3(nb), dim3(256), c->stream, c->v, d_residual, d_partial);
+    hipLaunchKernelGGL(k_reduce_norms, dim3(1), dim3(256), 0, c->stream, d_partial, (int)nb, d_out);
     if (hipGetLastError() != hipSuccess)
       return fail(c, PFM_ERR_HIP, "k_residual_norms launch");
     if (hipMemcpyAsync(out, d_out, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -556,53 +383,26 @@ extern "C"
       return fail(c, PFM_ERR_BAD_ARG, "pfm_set_params has not been called");
     (void)hipSetDevice(c->device);
     const unsigned nb = (unsigned)((c->v.n_cells + 255) / 256);
-    if (!c->d_partial || c->n_partial < (int64_t)nb)
-      {
-        double *p = nullptr;
-        if (hipMalloc((void **)&p, sizeof(double) * 3 * ((size_t)nb + 1)) != hipSuccess)
-          return fail(c, PFM_ERR_NOMEM, "hipMalloc partial sums");
-        c->allocs.push_back(p);
-        c->d_partial = p;
-        c->n_partial = nb;
-      }
+    if (int rc = dev_buf_reserve(c, c->buf_partial, sizeof(double) * 3 * ((size_t)nb + 1), "partial sums"))
+      return rc;
     uint8_t *d_owned = nullptr;
-    if (cell_owned)
-      {
-        if (!c->d_cell_owned)
-          {
-            if (hipMalloc((void **)&c->d_cell_owned, (size_t)std::max<long long>(c->v.n_cells, 1)) != hipSuccess)
-              return fail(c, PFM_ERR_NOMEM, "hipMalloc cell mask");
-            c->allocs.push_back(c->d_cell_owned);
-          }
-        if (hipMemcpyAsync(c->d_cell_owned, cell_owned, (size_t)c->v.n_cells, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-          return fail(c, PFM_ERR_HIP, "cell mask upload");
-        d_owned = c->d_cell_owned;
-      }
+    if (int rc = upload_mask(c, cell_owned, &d_owned))
+      return rc;
     double *d_lam = nullptr, *d_mu = nullptr;
     if (cell_lambda && c->v.n_cells > 0)
       {
-        if (!c->d_func_mat)
-          {
-            if (hipMalloc((void **)&c->d_func_mat, 2 * sizeof(double) * (size_t)c->v.n_cells) != hipSuccess)
-              return fail(c, PFM_ERR_NOMEM, "hipMalloc material override");
-            c->allocs.push_back(c->d_func_mat);
-            c->device_bytes += (int64_t)(2 * sizeof(double) * (size_t)c->v.n_cells);
-          }
-        d_lam = c->d_func_mat;
-        d_mu = c->d_func_mat + c->v.n_cells;
+        if (int rc = dev_buf_reserve(c, c->buf_func_mat, 2 * sizeof(double) * (size_t)c->v.n_cells, "material override"))
+          return rc;
+        d_lam = c->buf_func_mat.as<double>();
+        d_mu = d_lam + c->v.n_cells;
         if (hipMemcpyAsync(d_lam, cell_lambda, sizeof(double) * (size_t)c->v.n_cells, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
             hipMemcpyAsync(d_mu, cell_mu, sizeof(double) * (size_t)c->v.n_cells, hipMemcpyHostToDevice, c->stream) != hipSuccess)
           return fail(c, PFM_ERR_HIP, "material override upload");
       }
-    double *d_out = c->d_partial + 3 * (size_t)nb;
+    double *d_partial = c->buf_partial.as<double>(), *d_out = d_partial + 3 * (size_t)nb;
     if (nb)
-      {
-        if (c->v.dim == 2)
-          hipLaunchKernelGGL(k_functionals<2>, dim3(nb), dim3(256), 0, c->stream, c->v, c->prm, d_owned, d_lam, d_mu, c->d_partial);
-        else
-          hipLaunchKernelGGL(k_functionals<3>, dim3(nb), dim3(256), 0, c->stream, c->v, c->prm, d_owned, d_lam, d_mu, c->d_partial);
-      }
-    hipLaunchKernelGGL(k_reduce3, dim3(1), dim3(256), 0, c->stream, c->d_partial, (long long)nb, d_out);
+      PFM_LAUNCH_DIM(c->v.dim, k_functionals, dim3(nb), dim3(256), c->stream, c->v, c->prm, d_owned, d_lam, d_mu, d_partial);
+    hipLaunchKernelGGL((k_reduce_final<double, 3, Sum<double>>), dim3(1), dim3(256), 0, c->stream, d_partial, (long long)nb, d_out);
     if (hipGetLastError() != hipSuccess)
       return fail(c, PFM_ERR_HIP, "k_functionals launch");
     if (hipMemcpyAsync(out, d_out, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||

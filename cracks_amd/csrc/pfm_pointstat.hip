@@ -4,11 +4,12 @@
 //   pfm_point_eval    compute_point_stress, compute_point_value      cracks.cc:3285-3320, 3264-3283
 //
 // MappingQ1 per point on any Q1 mesh, FP64 throughout, the node state of the device view (every kernel path, both layouts).
-// No floating-point atomics: every sum has a fixed order, repeated calls are bitwise identical.
-#include "pfm_internal.h"
+// No floating-point atomics: every sum has a fixed order, repeated calls are bitwise identical.  The bucket sums are
+// reduced per bucket in wave order here (not the block reduction of pfm_reduce.h); the Q1 element is pfm_q1_point.h, the
+// host helpers pfm_entry.h.
+#include "pfm_entry.h"
 #include "pfm_q1_point.h"
 
-#include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -511,35 +512,6 @@ namespace pfm
         }
     }
 
-    constexpr size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-    // the context's scratch of these two entries, at least `bytes` large (grow-only; contents undefined)
-    int stat_scratch(pfm_ctx *c, size_t bytes, char **p)
-    {
-      if (!c->d_stat || c->stat_bytes < bytes)
-        {
-          if (c->d_stat)
-            {
-              (void)hipStreamSynchronize(c->stream);
-              c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), c->d_stat), c->allocs.end());
-              (void)hipFree(c->d_stat);
-              c->device_bytes -= (int64_t)c->stat_bytes;
-              c->d_stat = nullptr;
-              c->stat_bytes = 0;
-            }
-          if (hipMalloc(&c->d_stat, bytes) != hipSuccess)
-            {
-              c->d_stat = nullptr;
-              return fail(c, PFM_ERR_NOMEM, "hipMalloc statistics scratch");
-            }
-          c->allocs.push_back(c->d_stat);
-          c->stat_bytes = bytes;
-          c->device_bytes += (int64_t)bytes;
-        }
-      *p = static_cast<char *>(c->d_stat);
-      return PFM_OK;
-    }
-
     // value_to_bucket before its cast (cracks.cc:3327), every operation rounded on its own
     double bucket_real(double x, double x_lo, double x_hi, int n_buckets)
     {
@@ -616,9 +588,9 @@ extern "C"
     const int slabs = (int)((rows_per_cell + CB_SLAB_ROWS - 1) / CB_SLAB_ROWS);
     const long long cells_per_launch = std::max<long long>(1, CB_MAX_POINTS / pts_per_cell);
     const size_t o_total = align256(sizeof(double) * thr.size()), o_partial = o_total + align256(sizeof(double) * (size_t)n2);
-    char *base = nullptr;
-    if (int rc = stat_scratch(c, o_partial + sizeof(double) * (size_t)n2 * CB_MAX_WAVES, &base))
+    if (int rc = dev_buf_reserve(c, c->buf_stat, o_partial + sizeof(double) * (size_t)n2 * CB_MAX_WAVES, "statistics scratch"))
       return rc;
+    char *base = c->buf_stat.as<char>();
     double *d_thr = reinterpret_cast<double *>(base), *d_total = reinterpret_cast<double *>(base + o_total),
            *d_partial = reinterpret_cast<double *>(base + o_partial);
     uint8_t *d_owned = nullptr;
@@ -633,12 +605,8 @@ extern "C"
         const unsigned nb = (unsigned)((std::min<long long>(n_items, CB_MAX_WAVES) + CB_WAVES - 1) / CB_WAVES);
         const int n_waves = (int)nb * CB_WAVES;
         const long long items_per_wave = (n_items + n_waves - 1) / n_waves;
-        if (dim == 2)
-          hipLaunchKernelGGL(k_cod_buckets<2>, dim3(nb), dim3(64 * CB_WAVES), 0, c->stream, c->v, d_owned, c0, n_items, slabs,
-                             items_per_wave, n_buckets, n_sub, d_thr, d_partial);
-        else
-          hipLaunchKernelGGL(k_cod_buckets<3>, dim3(nb), dim3(64 * CB_WAVES), 0, c->stream, c->v, d_owned, c0, n_items, slabs,
-                             items_per_wave, n_buckets, n_sub, d_thr, d_partial);
+        PFM_LAUNCH_DIM(dim, k_cod_buckets, dim3(nb), dim3(64 * CB_WAVES), c->stream, c->v, d_owned, c0, n_items, slabs, items_per_wave,
+                       n_buckets, n_sub, d_thr, d_partial);
         hipLaunchKernelGGL(k_cod_buckets_reduce, dim3(1), dim3(256), 0, c->stream, d_partial, n_waves, n2, c0 == 0 ? 1 : 0, d_total);
         if (hipGetLastError() != hipSuccess)
           return fail(c, PFM_ERR_HIP, "k_cod_buckets launch");
@@ -674,9 +642,9 @@ extern "C"
     const size_t np = (size_t)n_points;
     const size_t o_cell = align256(sizeof(double) * np * dim), o_val = o_cell + align256(sizeof(int32_t) * np),
                  o_grad = o_val + align256(sizeof(double) * np * nc), total = o_grad + align256(sizeof(double) * np * nc * dim);
-    char *base = nullptr;
-    if (int rc = stat_scratch(c, total, &base))
+    if (int rc = dev_buf_reserve(c, c->buf_stat, total, "statistics scratch"))
       return rc;
+    char *base = c->buf_stat.as<char>();
     double *d_points = reinterpret_cast<double *>(base), *d_val = reinterpret_cast<double *>(base + o_val),
            *d_grad = reinterpret_cast<double *>(base + o_grad);
     int32_t *d_cell = reinterpret_cast<int32_t *>(base + o_cell);
@@ -688,17 +656,9 @@ extern "C"
       return fail(c, PFM_ERR_HIP, "pfm_point_eval: point upload");
     const unsigned nbc = (unsigned)((c->v.n_cells + 255) / 256), nchunks = (unsigned)((n_points + PE_CHUNK - 1) / PE_CHUNK);
     if (nbc)
-      {
-        if (dim == 2)
-          hipLaunchKernelGGL(k_point_find<2>, dim3(nbc, nchunks), dim3(256), 0, c->stream, c->v, d_owned, d_points, n_points, d_cell);
-        else
-          hipLaunchKernelGGL(k_point_find<3>, dim3(nbc, nchunks), dim3(256), 0, c->stream, c->v, d_owned, d_points, n_points, d_cell);
-      }
+      PFM_LAUNCH_DIM(dim, k_point_find, dim3(nbc, nchunks), dim3(256), c->stream, c->v, d_owned, d_points, n_points, d_cell);
     const unsigned nbp = (unsigned)((n_points + 255) / 256);
-    if (dim == 2)
-      hipLaunchKernelGGL(k_point_values<2>, dim3(nbp), dim3(256), 0, c->stream, c->v, d_points, n_points, d_cell, d_val, d_grad);
-    else
-      hipLaunchKernelGGL(k_point_values<3>, dim3(nbp), dim3(256), 0, c->stream, c->v, d_points, n_points, d_cell, d_val, d_grad);
+    PFM_LAUNCH_DIM(dim, k_point_values, dim3(nbp), dim3(256), c->stream, c->v, d_points, n_points, d_cell, d_val, d_grad);
     if (hipGetLastError() != hipSuccess)
       return fail(c, PFM_ERR_HIP, "k_point_find launch");
     std::vector<int32_t> h_cell(np);

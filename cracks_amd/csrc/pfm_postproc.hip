@@ -5,13 +5,13 @@
 //   pfm_cod_lines           compute_functional_values -> compute_cod       cracks.cc:3706-3724, 3453-3550
 //   pfm_sneddon_phi_error   integrate_difference(ExactPhiSneddon, L2, phi)  cracks.cc:4495-4524, 418-450
 //
-// MappingQ1 per quadrature point on any Q1 mesh, FP64 throughout.  Every sum is a fixed-order reduction (no floating-point
-// atomics): repeated calls are bitwise identical.  Each entry returns this rank's part; the MPI sums, the reference's
-// sign flips and its "/2" are the caller's.
-#include "pfm_internal.h"
+// MappingQ1 per quadrature point on any Q1 mesh (pfm_q1_point.h), FP64 throughout.  Every sum is a fixed-order reduction
+// (pfm_reduce.h; no floating-point atomics): repeated calls are bitwise identical.  Each entry returns this rank's part; the
+// MPI sums, the reference's sign flips and its "/2" are the caller's.  Host helpers: pfm_entry.h.
+#include "pfm_entry.h"
 #include "pfm_q1_point.h"
+#include "pfm_reduce.h"
 
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <climits>
@@ -26,13 +26,6 @@ namespace pfm
 {
   namespace
   {
-    // QGauss(3) on [0,1] (the same constants as k_functionals)
-    __device__ __forceinline__ double gauss_x(int i)
-    {
-      return i == 0 ? 0.5 - 0.5 * 0.7745966692414834 : (i == 1 ? 0.5 : 0.5 + 0.5 * 0.7745966692414834);
-    }
-    __device__ __forceinline__ double gauss_w(int i) { return i == 1 ? 8.0 / 18.0 : 5.0 / 18.0; }
-
     // Point q of QGauss<dim-1>(3) on face f (deal.II numbering: axis f/2, side f%2) in cell reference coordinates,
     // QProjector's axis order: 2-D (s,t) / (t,s); 3-D faces 0/1 (s,q0,q1), 2/3 (q1,s,q0), 4/5 (q0,q1,s).
     template <int dim>
@@ -92,38 +85,6 @@ namespace pfm
       return len;
     }
 
-    // block reduction of up to 3 accumulators in a fixed order (lanes by xor-shuffles, the 4 waves through LDS)
-    __device__ __forceinline__ void block_sum3(const double acc[3], double *__restrict__ dst)
-    {
-      __shared__ double s_red[4][3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        {
-          double r = acc[k];
-#pragma unroll
-          for (int off = 32; off >= 1; off >>= 1)
-            r += __shfl_xor(r, off);
-          if ((threadIdx.x & 63) == 0)
-            s_red[threadIdx.x >> 6][k] = r;
-        }
-      __syncthreads();
-      if (threadIdx.x < 3)
-        dst[threadIdx.x] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
-    }
-
-    __global__ __launch_bounds__(256) void k_pp_reduce3(const double *__restrict__ partial, long long n, double *__restrict__ out)
-    {
-      double acc[3];
-      for (int k = 0; k < 3; ++k)
-        {
-          double r = 0.0;
-          for (long long i = threadIdx.x; i < n; i += 256)
-            r += partial[i * 3 + k];
-          acc[k] = r;
-        }
-      block_sum3(acc, out);
-    }
-
     // ---- compute_load: thread <-> (cell, face), QGauss<dim-1>(3), undegraded stress with the global Lame coefficients
     template <int dim>
     __global__ __launch_bounds__(256) void k_face_load(DevView v, double lam, double mu, const int32_t *__restrict__ cells,
@@ -177,7 +138,9 @@ namespace pfm
                 }
             }
         }
-      block_sum3(acc, partial + (long long)blockIdx.x * 3);
+      const double r = block_reduce(acc, Sum<double>{});
+      if (threadIdx.x < 3)
+        partial[(long long)blockIdx.x * 3 + threadIdx.x] = r;
     }
 
     // ---- phi error against ExactPhiSneddon (cracks.cc:418-450, l_0 = 1): thread <-> cell, QGauss(3)^dim
@@ -240,7 +203,9 @@ namespace pfm
               acc[0] += diff * diff * (det * w);
             }
         }
-      block_sum3(acc, partial + (long long)blockIdx.x * 3);
+      const double r = block_reduce(acc, Sum<double>{});
+      if (threadIdx.x < 3)
+        partial[(long long)blockIdx.x * 3 + threadIdx.x] = r;
     }
 
     // ---- COD, geometry pass.  Which lines does face f of an owned cell match (compute_cod, cracks.cc:3493-3513)?
@@ -451,22 +416,14 @@ namespace pfm
     // block partials of the 3-wide reductions: [nb][3] + the 3 results (shared with pfm_functionals, same stream)
     int ensure_partial(pfm_ctx *c, unsigned nb)
     {
-      if (c->d_partial && c->n_partial >= (int64_t)nb)
-        return PFM_OK;
-      double *p = nullptr;
-      if (hipMalloc((void **)&p, sizeof(double) * 3 * ((size_t)nb + 1)) != hipSuccess)
-        return fail(c, PFM_ERR_NOMEM, "hipMalloc partial sums");
-      c->allocs.push_back(p);
-      c->d_partial = p;
-      c->n_partial = nb;
-      return PFM_OK;
+      return dev_buf_reserve(c, c->buf_partial, sizeof(double) * 3 * ((size_t)nb + 1), "partial sums");
     }
 
     // second stage + copy of `width` results to the host; synchronous
     int finish_reduce3(pfm_ctx *c, unsigned nb, double *out, int width, const char *what)
     {
-      double *d_out = c->d_partial + 3 * (size_t)nb;
-      hipLaunchKernelGGL(k_pp_reduce3, dim3(1), dim3(256), 0, c->stream, c->d_partial, (long long)nb, d_out);
+      double *d_partial = c->buf_partial.as<double>(), *d_out = d_partial + 3 * (size_t)nb;
+      hipLaunchKernelGGL((k_reduce_final<double, 3, Sum<double>>), dim3(1), dim3(256), 0, c->stream, d_partial, (long long)nb, d_out);
       if (hipGetLastError() != hipSuccess)
         return fail(c, PFM_ERR_HIP, std::string(what) + " launch");
       double h[3];
@@ -513,12 +470,7 @@ namespace pfm
         return bad(PFM_ERR_HIP, "cod lines upload");
       const unsigned nbc = (unsigned)((NC + 255) / 256);
       if (nbc)
-        {
-          if (dim == 2)
-            hipLaunchKernelGGL(k_cod_count<2>, dim3(nbc), dim3(256), 0, c->stream, c->v, d_owned, d_lines, n_lines, eps, d_count);
-          else
-            hipLaunchKernelGGL(k_cod_count<3>, dim3(nbc), dim3(256), 0, c->stream, c->v, d_owned, d_lines, n_lines, eps, d_count);
-        }
+        PFM_LAUNCH_DIM(dim, k_cod_count, dim3(nbc), dim3(256), c->stream, c->v, d_owned, d_lines, n_lines, eps, d_count);
       // offsets: exclusive sum over the n_cells + 1 counts (the last one is 0) -> offset[NC] = number of entries
       size_t tb_scan = 0;
       if (hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, d_count, d_offset, (int)(NC + 1), c->stream) != hipSuccess)
@@ -543,10 +495,7 @@ namespace pfm
               hipMalloc((void **)&d_key_sorted, sizeof(int32_t) * (size_t)n_entries) != hipSuccess ||
               hipMalloc((void **)&d_entry, sizeof(long long) * (size_t)n_entries) != hipSuccess)
             return bad(PFM_ERR_NOMEM, "hipMalloc cod sort scratch");
-          if (dim == 2)
-            hipLaunchKernelGGL(k_cod_fill<2>, dim3(nbc), dim3(256), 0, c->stream, c->v, d_owned, d_lines, n_lines, eps, d_offset, d_key, d_entry);
-          else
-            hipLaunchKernelGGL(k_cod_fill<3>, dim3(nbc), dim3(256), 0, c->stream, c->v, d_owned, d_lines, n_lines, eps, d_offset, d_key, d_entry);
+          PFM_LAUNCH_DIM(dim, k_cod_fill, dim3(nbc), dim3(256), c->stream, c->v, d_owned, d_lines, n_lines, eps, d_offset, d_key, d_entry);
           int end_bit = 1;
           while (end_bit < 31 && (1LL << end_bit) < (long long)n_lines)
             ++end_bit;
@@ -608,21 +557,17 @@ extern "C"
       return rc;
     if (n_faces > 0)
       {
-        if (c->n_face_cap < n_faces)
-          {
-            if (realloc_owned(c, c->d_face_cells, (size_t)n_faces) != PFM_OK || realloc_owned(c, c->d_face_ids, (size_t)n_faces) != PFM_OK)
-              return fail(c, PFM_ERR_NOMEM, "hipMalloc face list");
-            c->n_face_cap = n_faces;
-          }
-        if (hipMemcpyAsync(c->d_face_cells, cells, sizeof(int32_t) * (size_t)n_faces, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(c->d_face_ids, faces, (size_t)n_faces, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        if (int rc = dev_buf_reserve(c, c->buf_face_cells, sizeof(int32_t) * (size_t)n_faces, "face list"))
+          return rc;
+        if (int rc = dev_buf_reserve(c, c->buf_face_ids, (size_t)n_faces, "face list"))
+          return rc;
+        int32_t *d_cells = c->buf_face_cells.as<int32_t>();
+        uint8_t *d_ids = c->buf_face_ids.as<uint8_t>();
+        if (hipMemcpyAsync(d_cells, cells, sizeof(int32_t) * (size_t)n_faces, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(d_ids, faces, (size_t)n_faces, hipMemcpyHostToDevice, c->stream) != hipSuccess)
           return fail(c, PFM_ERR_HIP, "face list upload");
-        if (dim == 2)
-          hipLaunchKernelGGL(k_face_load<2>, dim3(nb), dim3(256), 0, c->stream, c->v, c->prm.lambda, c->prm.mu, c->d_face_cells,
-                             c->d_face_ids, (long long)n_faces, c->d_partial);
-        else
-          hipLaunchKernelGGL(k_face_load<3>, dim3(nb), dim3(256), 0, c->stream, c->v, c->prm.lambda, c->prm.mu, c->d_face_cells,
-                             c->d_face_ids, (long long)n_faces, c->d_partial);
+        PFM_LAUNCH_DIM(dim, k_face_load, dim3(nb), dim3(256), c->stream, c->v, c->prm.lambda, c->prm.mu, d_cells, d_ids,
+                       (long long)n_faces, c->buf_partial.as<double>());
       }
     return finish_reduce3(c, nb, out, dim, "k_face_load");
   }
@@ -645,12 +590,9 @@ extern "C"
         return rc;
     if (int rc = ensure_partial(c, (unsigned)((n_lines + 2) / 3)))
       return rc;
-    double *d_cod = c->d_partial; // the partial-sum buffer holds 3 ((n_lines + 2) / 3 + 1) >= n_lines doubles
+    double *d_cod = c->buf_partial.as<double>(); // the partial-sum buffer holds 3 ((n_lines + 2) / 3 + 1) >= n_lines doubles
     const unsigned nb = (unsigned)((n_lines + 3) / 4);
-    if (c->v.dim == 2)
-      hipLaunchKernelGGL(k_cod_values<2>, dim3(nb), dim3(256), 0, c->stream, c->v, c->cod.d_line_ptr, c->cod.d_entry, n_lines, d_cod);
-    else
-      hipLaunchKernelGGL(k_cod_values<3>, dim3(nb), dim3(256), 0, c->stream, c->v, c->cod.d_line_ptr, c->cod.d_entry, n_lines, d_cod);
+    PFM_LAUNCH_DIM(c->v.dim, k_cod_values, dim3(nb), dim3(256), c->stream, c->v, c->cod.d_line_ptr, c->cod.d_entry, n_lines, d_cod);
     if (hipGetLastError() != hipSuccess)
       return fail(c, PFM_ERR_HIP, "k_cod_values launch");
     std::vector<long long> ptr((size_t)n_lines + 1);
@@ -677,12 +619,8 @@ extern "C"
     if (int rc = upload_mask(c, cell_owned, &d_owned))
       return rc;
     if (nb)
-      {
-        if (c->v.dim == 2)
-          hipLaunchKernelGGL(k_sneddon_phi_error<2>, dim3(nb), dim3(256), 0, c->stream, c->v, c->prm.alpha_eps, d_owned, c->d_partial);
-        else
-          hipLaunchKernelGGL(k_sneddon_phi_error<3>, dim3(nb), dim3(256), 0, c->stream, c->v, c->prm.alpha_eps, d_owned, c->d_partial);
-      }
+      PFM_LAUNCH_DIM(c->v.dim, k_sneddon_phi_error, dim3(nb), dim3(256), c->stream, c->v, c->prm.alpha_eps, d_owned,
+                     c->buf_partial.as<double>());
     return finish_reduce3(c, nb, sum_sq, 1, "k_sneddon_phi_error");
   }
 }

@@ -1,16 +1,46 @@
-// pfm_q1_point.h -- what the post-processing entries (pfm_postproc.hip, pfm_pointstat.hip) share.  Device: a cell's vertex
-// coordinates and node state from the device view, and shape values / physical gradients / det J at a reference point.
-// Host: the error text and the upload of the owned-cell mask.
+// pfm_q1_point.h -- the Q1 element of the device-side entries (pfm_newton.hip, pfm_postproc.hip, pfm_adapt.hip,
+// pfm_pointstat.hip).  Device only: a cell's vertex coordinates and node state from the device view, the dof of a
+// (node, component), QGauss(3), and shape values / physical gradients / det J at a reference point (MappingQ1).
 #pragma once
 
 #include "pfm_internal.h"
 
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <string>
 
 namespace pfm
 {
+  // dof of (node, component) in a vector of n_nodes nodes
+  __device__ __forceinline__ long long dof_of(int layout, int dim, long long n_nodes, long long node, int comp)
+  {
+    if (layout == PFM_LAYOUT_INTERLEAVED)
+      return node * (dim + 1) + comp;
+    return comp < dim ? node * dim + comp : n_nodes * dim + node;
+  }
+  // ... in a vector over the owned nodes of the view
+  template <int dim>
+  __device__ __forceinline__ long long dof_of(const DevView &v, int P, int c)
+  {
+    return dof_of(v.layout, dim, v.n_owned, P, c);
+  }
+
+  // QGauss(3) on [0,1]
+  __device__ __forceinline__ double gauss_x(int i)
+  {
+    return i == 0 ? 0.5 - 0.5 * 0.7745966692414834 : (i == 1 ? 0.5 : 0.5 + 0.5 * 0.7745966692414834);
+  }
+  __device__ __forceinline__ double gauss_w(int i) { return i == 1 ? 8.0 / 18.0 : 5.0 / 18.0; }
+
+  // Q1 shape value of vertex b at xi
+  template <int dim>
+  __device__ __forceinline__ double q1_weight(int b, const double xi[dim])
+  {
+    double w = 1.0;
+#pragma unroll
+    for (int d = 0; d < dim; ++d)
+      w *= ((b >> d) & 1) ? xi[d] : (1.0 - xi[d]);
+    return w;
+  }
+
   template <int dim>
   __device__ __forceinline__ void load_geometry(const DevView &v, long long cell, double x[1 << dim][dim])
   {
@@ -113,34 +143,5 @@ namespace pfm
           g[b][d] = s;
         }
     return det;
-  }
-
-  // ---- host side, shared by the entries of both files
-
-  inline int fail(pfm_ctx *c, int code, const std::string &msg)
-  {
-    if (c)
-      c->err = msg;
-    return code;
-  }
-
-  // the owned-cell mask of a functional in the context's device buffer (shared with pfm_functionals, same stream);
-  // *d_owned = nullptr for a NULL mask
-  inline int upload_mask(pfm_ctx *c, const uint8_t *cell_owned, uint8_t **d_owned)
-  {
-    *d_owned = nullptr;
-    if (!cell_owned)
-      return PFM_OK;
-    if (!c->d_cell_owned)
-      {
-        if (hipMalloc((void **)&c->d_cell_owned, (size_t)std::max<long long>(c->v.n_cells, 1)) != hipSuccess)
-          return fail(c, PFM_ERR_NOMEM, "hipMalloc cell mask");
-        c->allocs.push_back(c->d_cell_owned);
-      }
-    if (c->v.n_cells > 0 &&
-        hipMemcpyAsync(c->d_cell_owned, cell_owned, (size_t)c->v.n_cells, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-      return fail(c, PFM_ERR_HIP, "cell mask upload");
-    *d_owned = c->d_cell_owned;
-    return PFM_OK;
   }
 } // namespace pfm
