@@ -73,6 +73,28 @@ namespace
     return fail(c, PFM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
   }
 
+  // f() behind the C ABI: what dev_alloc / dev_upload and the lazy table builders throw becomes the call's status
+  // (f returns nothing, or a status)
+  template <class F>
+  int guarded(pfm_ctx *c, F &&f)
+  {
+    try
+      {
+        if constexpr (std::is_void<decltype(f())>::value)
+          return f(), PFM_OK;
+        else
+          return f();
+      }
+    catch (const HipFail &x)
+      {
+        return hipfail(c, x.e, x.what);
+      }
+    catch (const std::bad_alloc &)
+      {
+        return fail(c, PFM_ERR_NOMEM, "host allocation failed");
+      }
+  }
+
   // Host threads for the O(n_nodes) / O(n_cells) loops of the context build (setup_system of the reference runs them
   // after every refine_mesh, cracks.cc:4148): the cores this process may use (affinity mask, cgroup quota), at most 32.
   int host_threads()
@@ -2853,18 +2875,8 @@ extern "C"
     auto rp = [&](int64_t r) -> int64_t { return rp64 ? rp64[r] : (int64_t)rp32[r]; };
     if (rp(0) != 0 || rp(c->block_rows(block)) != c->block_nnz(block))
       return fail(c, PFM_ERR_BAD_ARG, "pfm_pattern_bind: row pointers do not describe this block (size mismatch)");
-    try
-      {
-        ensure_host_graph(c);
-      }
-    catch (const std::bad_alloc &)
-      {
-        return fail(c, PFM_ERR_NOMEM, "host allocation failed");
-      }
-    catch (const HipFail &f)
-      {
-        return hipfail(c, f.e, f.what);
-      }
+    if (const int rcg = guarded(c, [&] { ensure_host_graph(c); }))
+      return rcg;
     std::vector<int32_t> order(c->h_nadj.size());
     std::atomic<int> bad{0}; // 1: structure, 2: column set
     std::atomic<bool> changed{false};
@@ -2925,33 +2937,31 @@ extern "C"
         for (int b = 0; b < c->n_blocks; ++b)
           if (b != block && c->pattern_bound[b])
             return fail(c, PFM_ERR_UNSUPPORTED, "pfm_pattern_bind: all blocks must order the neighbour nodes of a row alike");
-        try
-          {
-            c->h_nadj.swap(order);
-            if (c->general_ready) // else: built from the new order when the general family is first used
-              {
-                if (!c->h_nadj.empty() &&
-                    hipMemcpy(const_cast<int32_t *>(c->v.nadj), c->h_nadj.data(), c->h_nadj.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
-                  throw HipFail{hipGetLastError(), "hipMemcpy nadj"};
-                c->patch_slots_valid = false; // the regular rows' slots follow the bound order
-                c->overlay3_rows_valid = false;
-                if (launch_build_cslot(c->v, nullptr) != PFM_OK || hipDeviceSynchronize() != hipSuccess)
-                  throw HipFail{hipGetLastError(), "cslot kernel"};
-              }
-            if (c->cart_ok)
-              {
-                std::vector<uint32_t> mask;
-                std::vector<uint8_t> perm;
-                bool any_perm = false;
-                if (!row_order_tables(c, dim, NO, c->lat, mask, perm, any_perm))
-                  return fail(c, PFM_ERR_BAD_ARG, "pfm_pattern_bind: lattice rows inconsistent");
-                upload_row_tables(c, mask, perm, any_perm);
-              }
-          }
-        catch (const HipFail &f)
-          {
-            return hipfail(c, f.e, f.what);
-          }
+        const int rcb = guarded(c, [&]() -> int {
+          c->h_nadj.swap(order);
+          if (c->general_ready) // else: built from the new order when the general family is first used
+            {
+              if (!c->h_nadj.empty() &&
+                  hipMemcpy(const_cast<int32_t *>(c->v.nadj), c->h_nadj.data(), c->h_nadj.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+                throw HipFail{hipGetLastError(), "hipMemcpy nadj"};
+              c->patch_slots_valid = false; // the regular rows' slots follow the bound order
+              c->overlay3_rows_valid = false;
+              if (launch_build_cslot(c->v, nullptr) != PFM_OK || hipDeviceSynchronize() != hipSuccess)
+                throw HipFail{hipGetLastError(), "cslot kernel"};
+            }
+          if (c->cart_ok)
+            {
+              std::vector<uint32_t> mask;
+              std::vector<uint8_t> perm;
+              bool any_perm = false;
+              if (!row_order_tables(c, dim, NO, c->lat, mask, perm, any_perm))
+                return fail(c, PFM_ERR_BAD_ARG, "pfm_pattern_bind: lattice rows inconsistent");
+              upload_row_tables(c, mask, perm, any_perm);
+            }
+          return PFM_OK;
+        });
+        if (rcb)
+          return rcb;
       }
     c->pattern_bound[block] = true;
     return PFM_OK;
@@ -3090,32 +3100,6 @@ extern "C"
     c->v.hs_RD = dev_alloc<double>(c, (size_t)nh * pfm::PFM_HS_RD);
     c->hang_gather_ready = true;
     return true;
-  }
-
-  static int assemble_impl(pfm_ctx *c, int residual_only, double *const *d_values, double *d_res_pde, double *d_res_tot, int phase);
-
-  // assemble_nl_residual() of the line search (cracks.cc:2942-2957, 2507-2512): solution := d_solution, then the residuals.
-  // On a single-rank box (2-D or 3-D lattice) the residual kernel reads d_solution itself (DevView::fused_solution); everywhere else this
-  // is pfm_state_set_solution + pfm_assemble_device(residual_only).  Ranks with peers must import ghosts in between: they
-  // call the two entry points themselves.
-  int pfm_assemble_nl_residual_device(pfm_ctx *c, const double *d_solution, double *d_res_pde, double *d_res_tot)
-  {
-    if (!c || (!d_solution && c->n_owned_dofs() != 0))
-      return PFM_ERR_BAD_ARG;
-    if (!c->peers.empty())
-      return fail(c, PFM_ERR_BAD_ARG, "pfm_assemble_nl_residual_device: a rank with peers imports ghosts between the scatter and the assembly");
-    const bool split = c->have_params && c->prm.decompose_stress_matrix > 0 && c->prm.timestep_number > 0;
-    const bool fuse = c->kernel_path == 1 && !split && c->v.n_owned == c->v.n_nodes && c->v.n_owned > 0 &&
-                      getenv("PFM_NO_FUSED_SCATTER") == nullptr;
-    if (!fuse)
-      {
-        const int rc = state_set_impl(c, d_solution, nullptr, nullptr, 1);
-        return rc ? rc : assemble_impl(c, 1, nullptr, d_res_pde, d_res_tot, 0);
-      }
-    c->v.fused_solution = d_solution;
-    const int rc = assemble_impl(c, 1, nullptr, d_res_pde, d_res_tot, 0);
-    c->v.fused_solution = nullptr;
-    return rc;
   }
 
   static int ensure_halo_buffers(pfm_ctx *c);
@@ -3537,23 +3521,12 @@ extern "C"
     return halo_exchange_on(c, comm, peer_ranks, c->stream);
   }
 
-  // cartesian overlay: the slots of the regular rows follow the order of the node-graph rows (pfm_pattern_bind may change it)
+  // cartesian overlay: the slots of the regular rows follow the order of the node-graph rows (pfm_pattern_bind may change it);
+  // v.nadj exists (ensure_tables: lattice contexts build the general tables on first use)
   static int ensure_patch_ready(pfm_ctx *c)
   {
     if (c->n_patch_blocks == 0 || c->patch_slots_valid)
       return PFM_OK;
-    try
-      {
-        ensure_general_tables(c); // v.nadj (lattice contexts build it on first use)
-      }
-    catch (const HipFail &f)
-      {
-        return hipfail(c, f.e, f.what);
-      }
-    catch (const std::bad_alloc &)
-      {
-        return fail(c, PFM_ERR_NOMEM, "host allocation failed");
-      }
     const int rc = launch_patch_slots(c->v, c->d_node_slots, c->n_patch_blocks, c->stream);
     if (rc)
       return fail(c, rc, "patch slots");
@@ -3566,23 +3539,12 @@ extern "C"
   {
     if (c->levels3.empty() || c->overlay3_rows_valid)
       return PFM_OK;
-    try
-      {
-        ensure_general_tables(c); // v.nadj
-        if (!c->d_nbr_mask3)
-          {
+    if (!c->d_nbr_mask3)
+      if (const int rcg = guarded(c, [&] {
             c->d_nbr_mask3 = dev_alloc<uint32_t>(c, (size_t)std::max<int32_t>(c->v.n_owned, 1));
             c->d_row_perm3 = dev_alloc<uint8_t>(c, (size_t)std::max<long long>(c->nadj_total >= 0 ? c->nadj_total : (c->h_nadj_ptr.empty() ? 1 : c->h_nadj_ptr.back()), 1));
-          }
-      }
-    catch (const HipFail &f)
-      {
-        return hipfail(c, f.e, f.what);
-      }
-    catch (const std::bad_alloc &)
-      {
-        return fail(c, PFM_ERR_NOMEM, "host allocation failed");
-      }
+          }))
+        return rcg;
     int *d_bad = nullptr;
     if (hipMalloc((void **)&d_bad, sizeof(int)) != hipSuccess)
       return fail(c, PFM_ERR_NOMEM, "overlay row tables");
@@ -3626,15 +3588,11 @@ extern "C"
       t_uu.push_back(0);
     if (t_res.empty())
       t_res.push_back(0);
-    try
-      {
-        c->cv.bnd_uu3 = dev_upload(c, t_uu.data(), t_uu.size());
-        c->cv.bnd_res3 = dev_upload(c, t_res.data(), t_res.size());
-      }
-    catch (const HipFail &f)
-      {
-        return hipfail(c, f.e, f.what);
-      }
+    if (const int rcu = guarded(c, [&] {
+          c->cv.bnd_uu3 = dev_upload(c, t_uu.data(), t_uu.size());
+          c->cv.bnd_res3 = dev_upload(c, t_res.data(), t_res.size());
+        }))
+      return rcu;
     c->cv.n_bnd_uu3 = n_uu;
     c->cv.n_bnd_res3 = n_res;
     c->cv.zc_res3 = zc;
@@ -3663,6 +3621,381 @@ extern "C"
     c->overlap_lists_ready = false;
   }
 
+  // ---- assembly dispatch: one plan (AssemblyPlan), one routine per kernel family ("Assembly dispatch") ----
+  // The A/B switches of the dispatch.  Read once per process, all of them at the first plan: the members (switches()).
+  // Read on every call that gets as far as needing them, so that one process can compare the variants: the functions.
+  struct Switches
+  {
+    const bool jac_sequential = getenv("PFM_JAC_SEQUENTIAL") != nullptr;         // 3-D box: the two Jacobian kernels in turn
+    const bool general_sequential = getenv("PFM_GENERAL_SEQUENTIAL") != nullptr; // the atomic class behind the colour classes
+    const bool levels_concurrent = getenv("PFM_OVERLAY3_CONCURRENT") != nullptr; // 3-D overlay: a stream per level lattice
+    // -1 = lowest, 1 = highest dispatch priority of the side stream (A/B runs of the phase-field kernel of the pair)
+    const int side_prio = getenv("PFM_SIDE_PRIO") ? atoi(getenv("PFM_SIDE_PRIO")) : 0;
+    // PFM_SIDE_STREAM=1: the residual launch of a 3-D box Jacobian on the side stream.  Measured on MI355X at 216^3: no
+    // gain (21.4 vs 21.1 ms per assembly), the kernels do not share CUs usefully; off by default.
+    static bool side_stream() { return getenv("PFM_SIDE_STREAM") != nullptr; }
+    // PFM_CART2D_NO_FILL: k_cart2d_cells writes the zeros of the (u,phi) block with the rows; PFM_CART2D_ONE_LAUNCH: the
+    // single launch of round 5, which does the same
+    static bool cart2d_fill() { return getenv("PFM_CART2D_NO_FILL") == nullptr && getenv("PFM_CART2D_ONE_LAUNCH") == nullptr; }
+    // PFM_NO_FUSED_SCATTER=1: the line-search call scatters the solution with a launch of its own
+    static bool fused_scatter() { return getenv("PFM_NO_FUSED_SCATTER") == nullptr; }
+  };
+
+  static const Switches &switches() { static const Switches s; return s; }
+  // the stress split in the matrix (cracks.cc:2294): the general family has it, the row-owner kernels do not
+  static bool stress_split(const pfm_ctx *c) { return c->have_params && c->prm.decompose_stress_matrix > 0 && c->prm.timestep_number > 0; }
+
+  // Every decision of one assemble_impl call; what each means stands where it is made (plan_assembly, after_tables).
+  struct AssemblyPlan
+  {
+    int phase = 0; // 0: the whole assembly; 1, 2: the halves of pfm_assemble_overlapped
+    bool residual_only = false, split = false, cart = false, patches = false, overlay3 = false, overlay_uu = false, nothing = false;
+    bool pair = false, fork = false, levels_concurrent = false, fill_up_block = false, up_block_cleared = false;
+    bool gather = false, fork_general = false, atomic_stream = false; // final behind the lazy tables: after_tables
+    void after_tables(const pfm_ctx *c, bool gather_ready);
+  };
+
+  // No side effects, no allocation: what the context, the parameters and the switches say about this call.
+  static AssemblyPlan plan_assembly(const pfm_ctx *c, int residual_only, int phase, double *const *d_values)
+  {
+    AssemblyPlan p;
+    p.phase = phase;
+    p.residual_only = residual_only != 0;
+    p.split = stress_split(c);
+    p.cart = c->kernel_path == 1 && !p.split && (residual_only || cart_matrix_supported(c->v.dim)); // assemble_box
+    // the general family and the overlays are not cut into interior / boundary work: everything in phase 2
+    p.nothing = !p.cart && phase == 1;
+    // debug: general + cart (u,u).  Path 2 implies no overlay (pfm_ctx_force_path: lattice contexts only, which have no
+    // patches and no level lattices), so assemble_general alone launches the (u,u) kernel
+    p.overlay_uu = c->kernel_path == 2 && !residual_only && !p.split;
+    // cartesian overlay of a general mesh (AMR meshes; stress-split runs on a lattice): patch kernel (2-D) or level
+    // lattices (3-D) for the regular rows, the general family for the rest (PFM_NO_PATCH=1 at context creation: general
+    // family alone): assemble_overlay
+    p.overlay3 = !p.cart && c->v.dim == 3 && !c->levels3.empty() && c->kernel_path != 0 && !p.nothing && !p.split;
+    p.patches = (!p.cart && c->v.dim == 2 && c->n_patch_blocks > 0 && c->kernel_path != 0 && !p.nothing) || p.overlay3;
+    // 3-D cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*) -- wanted
+    p.gather = !p.cart && c->v.dim == 3 && c->hang_gather && !p.split && !p.nothing;
+    // The two Jacobian kernels of a 3-D box next to each other (default): with equal LDS allocations (64 granules of 1280 B
+    // each) any freed slot of a CU takes a workgroup of either kernel, the (u,u) and the phase-field workgroups mix and
+    // fill each other's stalls: 14.07 -> 13.75 ms per assembly at 216^3 (PFM_JAC_SEQUENTIAL=1: one after the other).
+    p.pair = p.cart && !switches().jac_sequential && cart_jacobian_pair(c->v, c->cv, c->prm, residual_only, phase);
+    // 2-D boxes never fork: the second launch of k_cart2d_cells (phase-field rows) reads the mean |diagonal| the first one
+    // leaves in CartView::cell_avg, so it must follow it on the same stream.  (The fork was measured at 0.262 -> 0.259 ms of
+    // kernel time at 1000^2 and was off by default; with an event between the launches nothing of that overlap is left.)
+    p.fork = p.cart && !residual_only && phase == 0 && (p.pair || (c->v.dim != 2 && Switches::side_stream()));
+    // the row-owner kernels of the cartesian family on every level lattice: each level on a stream of its own, forked
+    // off the context's stream (a level lattice of 6e5 nodes fills a third of the chip's dispatch slots; the levels
+    // write disjoint rows) when PFM_OVERLAY3_CONCURRENT=1 is set.  Default: one after the other on the context's
+    // stream -- measured the better of the two (profiles/r05/ov3_ab.txt: 4.56 against 4.86 ms per Jacobian)
+    p.levels_concurrent = p.overlay3 && c->levels3.size() > 1 && switches().levels_concurrent;
+    // 2-D box, blocked layout: the structurally zero (u,phi) block (cracks.cc:2333-2337) by a fill in front of the kernels,
+    // in the whole assembly and in phase 1; phase 2 takes it as cleared by phase 1 (CartView::up_block_cleared).
+    // (round 6, measured and removed for 3-D: clearing the block with a fill on a third stream instead of by 21 of the 49
+    // store instructions of every copy-out of k_cart_phi4 -- 10.95 -> 11.35 ms per assembly at 216^3,
+    // profiles/r06/ab_up_fill.txt: the fill takes bandwidth in a burst and dispatch slots from the pair)
+    const bool blocked2 = p.cart && c->v.dim == 2 && !residual_only && c->v.layout == PFM_LAYOUT_BLOCKED;
+    p.fill_up_block = blocked2 && phase <= 1 && c->n_blocks == 4 && d_values[1] && Switches::cart2d_fill();
+    p.up_block_cleared = p.fill_up_block || (blocked2 && phase == 2 && Switches::cart2d_fill());
+    return p;
+  }
+
+  // What depends on the lazy tables (ensure_tables): the gather has its tables or the context keeps its atomic class, and
+  // DevView::cell_ring exists once the colours do.
+  void AssemblyPlan::after_tables(const pfm_ctx *c, bool gather_ready)
+  {
+    gather = gather && gather_ready;
+    // general family: the atomic class (cells with hanging vertices) on the side stream next to the colour classes, behind
+    // the zeroing of the outputs (DevView::cell_ring; a residual-only assembly keeps the stream order: its atomic class
+    // takes 15 us, less than a fork and a join).  Overlay: the patch kernel on the stream, every class of the (small) rest
+    // of the general family on the side stream.
+    fork_general = !cart && !switches().general_sequential &&
+                   ((!residual_only && c->v.cell_ring != nullptr) || (patches && c->n_general_cells > 0));
+    // 3-D overlay Jacobian: the class of the cells at hanging vertices (FP64 atomics, 4.7 of the general family's 6 ms at
+    // 1.1e6 cells) on a third stream next to the plain classes (DevView::cell_ring makes that safe).
+    // (PFM_HANGING_COLOURED: a hanging cell in a plain class adds to its PARENTS' rows without atomics; should a cell with
+    // more than 16 resolved nodes ever sit in the atomic class next to it, that class must not run beside the plain ones)
+    atomic_stream = overlay3 && fork_general && !residual_only && (c->v.cell_ring || gather) && c->n_general_cells > 0 &&
+                    !c->hanging_coloured;
+  }
+
+  // the only place that makes side_stream, ev_fork and ev_join
+  static int ensure_side_stream(pfm_ctx *c)
+  {
+    if (c->side_stream)
+      return PFM_OK;
+    const int side_prio = switches().side_prio;
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    const hipError_t es = side_prio == 0 ? hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking)
+                                         : hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, side_prio > 0 ? prio_hi : prio_lo);
+    if (es != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)
+      return fail(c, PFM_ERR_HIP, "side stream");
+    return PFM_OK;
+  }
+
+  // what `to` gets from here on runs behind what `from` has got so far; join_from: the same, named for the reader
+  static int fork_to(pfm_ctx *c, hipStream_t from, hipStream_t to, hipEvent_t ev, const char *what)
+  {
+    hipError_t e = hipEventRecord(ev, from);
+    if (e == hipSuccess)
+      e = hipStreamWaitEvent(to, ev, 0);
+    return e == hipSuccess ? PFM_OK : hipfail(c, e, what);
+  }
+  static int join_from(pfm_ctx *c, hipStream_t from, hipStream_t to, hipEvent_t ev, const char *what) { return fork_to(c, from, to, ev, what); }
+
+  // the side stream behind what the context's stream has got so far (its join: join_from with ev_join)
+  static int fork_side(pfm_ctx *c, const char *what)
+  {
+    const int rc = ensure_side_stream(c);
+    return rc ? rc : fork_to(c, c->stream, c->side_stream, c->ev_fork, what);
+  }
+
+  // the next pair of timing events; the interval opens on the context's stream
+  static int open_interval(pfm_ctx *c, hipEvent_t &ev0, hipEvent_t &ev1)
+  {
+    if (c->ev_used == c->ev_pool.size())
+      {
+        hipEvent_t a, b;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)
+          return fail(c, PFM_ERR_HIP, "hipEventCreate");
+        c->ev_pool.emplace_back(a, b);
+      }
+    ev0 = c->ev_pool[c->ev_used].first;
+    ev1 = c->ev_pool[c->ev_used++].second;
+    (void)hipEventRecord(ev0, c->stream);
+    return PFM_OK;
+  }
+
+  // deferred placeholder patches of the pair: one entry per flagged displacement dof at most; emptied on the stream
+  static int ensure_patch_list(pfm_ctx *c)
+  {
+    if (c->cv.patch_cap < c->n_flag_u || !c->cv.patch_count)
+      {
+        for (void *q : {(void *)c->cv.patch_idx, (void *)c->cv.patch_val, (void *)c->cv.patch_count})
+          if (q)
+            (void)hipFree(q);
+        c->device_bytes -= (int64_t)c->cv.patch_cap * 16 + (c->cv.patch_count ? 4 : 0);
+        c->cv.patch_idx = nullptr, c->cv.patch_val = nullptr, c->cv.patch_count = nullptr;
+        const size_t cap = (size_t)std::max<int64_t>(c->n_flag_u, 1);
+        if (hipMalloc((void **)&c->cv.patch_idx, cap * sizeof(long long)) != hipSuccess ||
+            hipMalloc((void **)&c->cv.patch_val, cap * sizeof(double)) != hipSuccess ||
+            hipMalloc((void **)&c->cv.patch_count, sizeof(int)) != hipSuccess)
+          return fail(c, PFM_ERR_NOMEM, "patch list");
+        c->cv.patch_cap = (int)std::min<size_t>(cap, 0x7fffffff);
+        c->device_bytes += (int64_t)c->cv.patch_cap * 16 + 4;
+      }
+    return hipMemsetAsync(c->cv.patch_count, 0, sizeof(int), c->stream) == hipSuccess ? PFM_OK : fail(c, PFM_ERR_HIP, "patch list reset");
+  }
+
+  // the lazy tables of the plan's family; gather_ready: the gather has its tables (false: the atomic class stays)
+  static int ensure_tables(pfm_ctx *c, const AssemblyPlan &p, bool &gather_ready)
+  {
+    int rc = PFM_OK;
+    if (p.cart && p.phase != 0 && !c->overlap_lists_ready)
+      rc = ensure_overlap_lists(c); // dropped by pfm_ctx_force_zchunk: the lists of the new residual length
+    if (rc == PFM_OK && !p.cart)
+      rc = guarded(c, [&] { ensure_general_tables(c); }); // (lattice contexts build them on first use)
+    if (rc == PFM_OK && p.patches)
+      rc = p.overlay3 ? ensure_overlay3_ready(c) : ensure_patch_ready(c);
+    else if (rc == PFM_OK && !p.cart && c->full_colours_lazy)
+      rc = guarded(c, [&] { ensure_full_colours(c); }); // (a context that has only run with its overlay so far)
+    if (rc == PFM_OK && p.gather)
+      rc = guarded(c, [&] { gather_ready = ensure_hang_gather(c); });
+    return rc;
+  }
+
+  // zero the outputs (cracks.cc:2133-2137).  The row-owner kernels write every entry exactly once -- the structurally zero
+  // (u,phi) block of the blocked layout included (k_cart_phi4) -- and need no zeroing pass: of a box nothing is zeroed, of
+  // an overlay the residuals and the rows of the general family.
+  static int zero_outputs(pfm_ctx *c, const AssemblyPlan &p, double *const *d_values, double *d_res_pde, double *d_res_tot)
+  {
+    hipError_t e = hipSuccess;
+    if (!p.cart)
+      e = hipMemsetAsync(d_res_pde, 0, sizeof(double) * (size_t)c->n_owned_dofs(), c->stream);
+    if (!p.cart && e == hipSuccess && p.residual_only)
+      e = hipMemsetAsync(d_res_tot, 0, sizeof(double) * (size_t)c->n_owned_dofs(), c->stream);
+    if (e == hipSuccess && !p.residual_only)
+      for (int b = 0; b < c->n_blocks && e == hipSuccess; ++b)
+        {
+          if (!d_values[b] && c->block_nnz(b) > 0)
+            return fail(c, PFM_ERR_BAD_ARG, "null matrix block");
+          if (!p.cart && !p.patches)
+            e = hipMemsetAsync(d_values[b], 0, sizeof(double) * (size_t)c->block_nnz(b), c->stream);
+        }
+    if (e == hipSuccess && p.patches && !p.residual_only && c->n_rows_general > 0 &&
+        launch_zero_rows(c->v, d_values, c->d_rows_general, c->n_rows_general, c->stream) != PFM_OK)
+      return fail(c, PFM_ERR_HIP, "zero the rows of the general family");
+    return e == hipSuccess ? PFM_OK : hipfail(c, e, "zero outputs");
+  }
+
+  // Two statuses, here and in launch_levels / gather_hanging: the return value ends the call at once (its text is set);
+  // `rc` (in/out) is the status of the launches, which assemble_impl reports behind the joins and the closing event.
+  // cartesian box, 2-D / 3-D: the pair with its deferred placeholder patches, the fork, the fill of the (u,phi) block
+  static int assemble_box(pfm_ctx *c, const AssemblyPlan &p, double *const *d_values, double *d_res_pde, double *d_res_tot, int &rc)
+  {
+    if (p.pair)
+      if (const int rcp = ensure_patch_list(c))
+        return rcp;
+    if (p.fork)
+      if (const int rcf = fork_side(c, "fork"))
+        return rcf;
+    if (!p.residual_only && c->v.dim == 3 && c->scal_dirty)
+      {
+        // off the hot path: once per pfm_set_params, complete before any kernel of any stream may read it
+        int rcs = upload_mat_scal(c->prm, c->cv, c->d_scal, c->stream);
+        if (rcs == PFM_OK && hipStreamSynchronize(c->stream) != hipSuccess)
+          rcs = PFM_ERR_HIP;
+        if (rcs)
+          return fail(c, rcs, "scalar tables");
+        c->scal_dirty = false;
+      }
+    if (p.fill_up_block && hipMemsetAsync(d_values[1], 0, sizeof(double) * (size_t)c->block_nnz(1), c->stream) != hipSuccess)
+      return fail(c, PFM_ERR_HIP, "clear the (u,phi) block");
+    pfm::CartView cv = c->cv;
+    cv.up_block_cleared = p.up_block_cleared ? 1 : 0;
+    if (!p.pair)
+      cv.patch_idx = nullptr, cv.patch_val = nullptr, cv.patch_count = nullptr, cv.patch_cap = 0;
+    rc = launch_assemble_cart(c->v, cv, c->prm, p.residual_only, d_values, d_res_pde, d_res_tot, c->stream,
+                              p.fork ? c->side_stream : c->stream, c->d_scal, p.phase);
+    if (p.fork)
+      if (const int rcj = join_from(c, c->side_stream, c->stream, c->ev_join, "join"))
+        return rcj;
+    if (p.pair && rc == PFM_OK)
+      rc = launch_cart_apply_patches(c->cv, d_values[0], c->stream, c->v.status);
+    return PFM_OK;
+  }
+
+  // The view the launches of the general family take.  classes: for its colour and atomic classes -- the reduced colour
+  // lists next to an overlay, and either the atomic adds or the scratch of the cells at hanging vertices, never both.
+  static pfm::DevView general_view(const pfm_ctx *c, const AssemblyPlan &p, bool classes)
+  {
+    pfm::DevView vg = c->v;
+    if (!p.patches)
+      vg.row_patch = nullptr; // no overlay in this assembly: the general family writes every row
+    if (!classes)
+      return vg;
+    if (p.patches)
+      vg.color_cells = c->d_color_cells_reduced;
+    if (p.gather)
+      vg.cell_ring = nullptr; // nobody adds atomically: the cells at hanging vertices only write their scratch
+    else
+      vg.hs_K = nullptr, vg.hs_off = nullptr, vg.hs_RD = nullptr;
+    return vg;
+  }
+
+  // behind every class and every level kernel (joined by the caller): the rows the hanging cells reach, in list order
+  static void gather_hanging(pfm_ctx *c, const AssemblyPlan &p, double *const *d_values, double *d_res_pde, double *d_res_tot, int &rc)
+  {
+    if (p.gather && rc == PFM_OK)
+      rc = launch_hanging_gather(general_view(c, p, false), c->prm, p.residual_only, d_values, d_res_pde, d_res_tot, c->d_hg_rows, c->d_hg_ptr,
+                                 c->d_hg_list, c->n_hg_rows, c->stream);
+  }
+
+  // 3-D overlay: the row-owner kernels on every level lattice, on the context's stream or (plan.levels_concurrent) each
+  // level on a stream of its own between a fork and a join
+  static int launch_levels(pfm_ctx *c, const AssemblyPlan &p, double *const *d_values, double *d_res_pde, double *d_res_tot, int &rc)
+  {
+    const size_t nl = c->levels3.size();
+    hipError_t e = hipSuccess;
+    for (auto &lv : c->levels3)
+      if (rc == PFM_OK && !p.residual_only && lv.scal_dirty)
+        {
+          rc = upload_mat_scal(c->prm, lv.cv, lv.d_scal, c->stream);
+          lv.scal_dirty = rc != PFM_OK;
+        }
+    const bool par = p.levels_concurrent && rc == PFM_OK;
+    if (par)
+      {
+        while (c->ov_streams.size() < nl)
+          {
+            hipStream_t st = nullptr;
+            hipEvent_t ev = nullptr;
+            if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+              return fail(c, PFM_ERR_HIP, "overlay level stream");
+            c->ov_streams.push_back(st);
+            c->ov_events.push_back(ev);
+          }
+        if (!c->ov_fork && hipEventCreateWithFlags(&c->ov_fork, hipEventDisableTiming) != hipSuccess)
+          return fail(c, PFM_ERR_HIP, "overlay level event");
+        e = hipEventRecord(c->ov_fork, c->stream); // one event, every level stream behind it
+        for (size_t i = 0; i < nl && e == hipSuccess; ++i)
+          e = hipStreamWaitEvent(c->ov_streams[i], c->ov_fork, 0);
+        if (e != hipSuccess)
+          return hipfail(c, e, "fork (overlay levels)");
+      }
+    for (size_t i = 0; i < nl && rc == PFM_OK; ++i)
+      {
+        hipStream_t st = par ? c->ov_streams[i] : c->stream;
+        rc = launch_assemble_cart(c->v, c->levels3[i].cv, c->prm, p.residual_only, d_values, d_res_pde, d_res_tot, st, st, c->levels3[i].d_scal, 0);
+      }
+    for (size_t i = 0; par && i < nl; ++i)
+      if (const int rcj = join_from(c, c->ov_streams[i], c->stream, c->ov_events[i], "join (overlay levels)"))
+        return rcj;
+    return PFM_OK;
+  }
+
+  // 2-D patch overlay / 3-D level overlay.  The patch kernel or the level kernels write every regular row once, with plain
+  // stores; next to them (side stream) the general family over the cells that touch a non-regular row (it skips the
+  // regular ones: DevView::row_patch), its classes one after the other, the atomic class of a 3-D Jacobian on a third stream
+  static int assemble_overlay(pfm_ctx *c, const AssemblyPlan &p, double *const *d_values, double *d_res_pde, double *d_res_tot, int &rc)
+  {
+    if (p.fork_general)
+      if (const int rcf = fork_side(c, "fork (general family)"))
+        return rcf;
+    if (!p.overlay3)
+      rc = launch_assemble_patches(c->v, c->prm, p.residual_only, d_values, d_res_pde, d_res_tot, c->n_patch_blocks, c->stream);
+    else if (const int rcl = launch_levels(c, p, d_values, d_res_pde, d_res_tot, rc))
+      return rcl;
+    hipStream_t s_atomic = nullptr;
+    if (p.atomic_stream)
+      {
+        int prio_lo = 0, prio_hi = 0; // (numerically lower = higher priority) the long pole gets its workgroups dispatched first
+        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+        if (!c->atomic_stream && (hipStreamCreateWithPriority(&c->atomic_stream, hipStreamNonBlocking, prio_hi) != hipSuccess ||
+                                  hipEventCreateWithFlags(&c->ev_atomic, hipEventDisableTiming) != hipSuccess))
+          return fail(c, PFM_ERR_HIP, "atomic-class stream");
+        const hipError_t e = hipStreamWaitEvent(c->atomic_stream, c->ev_fork, 0); // behind the fork of the side stream
+        if (e != hipSuccess)
+          return hipfail(c, e, "fork (atomic class)");
+        s_atomic = c->atomic_stream;
+      }
+    if (rc == PFM_OK && c->n_general_cells > 0)
+      rc = launch_assemble_general(general_view(c, p, true), c->prm, p.residual_only, d_values, d_res_pde, d_res_tot,
+                                   p.fork_general ? c->side_stream : c->stream, c->color_ptr_reduced, s_atomic);
+    if (s_atomic)
+      if (const int rcj = join_from(c, s_atomic, c->stream, c->ev_atomic, "join (atomic class)"))
+        return rcj;
+    if (p.fork_general)
+      if (const int rcj = join_from(c, c->side_stream, c->stream, c->ev_join, "join (general family)"))
+        return rcj;
+    gather_hanging(c, p, d_values, d_res_pde, d_res_tot, rc);
+    return PFM_OK;
+  }
+
+  // general family: the colour classes on the context's stream, the atomic class next to them on the side stream, the
+  // gather; kernel path 2 puts the cartesian (u,u) kernel on top
+  static int assemble_general(pfm_ctx *c, const AssemblyPlan &p, double *const *d_values, double *d_res_pde, double *d_res_tot, int &rc)
+  {
+    if (p.fork_general)
+      if (const int rcf = fork_side(c, "fork (general family)"))
+        return rcf;
+    rc = launch_assemble_general(general_view(c, p, true), c->prm, p.residual_only, d_values, d_res_pde, d_res_tot, c->stream, c->color_ptr,
+                                 (p.fork_general && !c->hanging_coloured) ? c->side_stream : nullptr);
+    if (p.fork_general)
+      if (const int rcj = join_from(c, c->side_stream, c->stream, c->ev_join, "join (general family)"))
+        return rcj;
+    gather_hanging(c, p, d_values, d_res_pde, d_res_tot, rc);
+    if (rc == PFM_OK && p.overlay_uu && c->scal_dirty)
+      {
+        rc = upload_mat_scal(c->prm, c->cv, c->d_scal, c->stream);
+        c->scal_dirty = rc != PFM_OK;
+      }
+    if (rc == PFM_OK && p.overlay_uu)
+      rc = launch_cart_uu_only(c->v, c->cv, c->prm, d_values[0], c->stream, c->d_scal);
+    return PFM_OK;
+  }
+
   // phase 0: the whole assembly (pfm_assemble_device).  phases 1, 2: the two halves of pfm_assemble_overlapped -- 1 = what
   // reads no ghost node, 2 = the rest; timing events bracket 1..2 together.
   static int assemble_impl(pfm_ctx *c, int residual_only, double *const *d_values, double *d_res_pde, double *d_res_tot, int phase)
@@ -3674,368 +4007,31 @@ extern "C"
     if (!c->have_params)
       return fail(c, PFM_ERR_BAD_ARG, "pfm_set_params has not been called");
     (void)hipSetDevice(c->device);
-    hipError_t e = hipSuccess;
-    const bool split = c->prm.decompose_stress_matrix > 0 && c->prm.timestep_number > 0; // cracks.cc:2294
-    const bool cart = c->kernel_path == 1 && !split && (residual_only || cart_matrix_supported(c->v.dim));
-    if (cart && phase != 0 && !c->overlap_lists_ready)
-      {
-        const int rcl = ensure_overlap_lists(c); // dropped by pfm_ctx_force_zchunk: the lists of the new residual length
-        if (rcl)
-          return rcl;
-      }
-    if (!cart && !c->general_ready)
-      {
-        try
-          {
-            ensure_general_tables(c);
-          }
-        catch (const HipFail &f)
-          {
-            return hipfail(c, f.e, f.what);
-          }
-        catch (const std::bad_alloc &)
-          {
-            return fail(c, PFM_ERR_NOMEM, "host allocation failed");
-          }
-      }
-    const bool overlay_uu = c->kernel_path == 2 && !residual_only && !split; // debug: general + cart (u,u)
-    // cartesian overlay of a general 2-D mesh (AMR meshes; stress-split runs on a lattice): patch kernel for the regular rows,
-    // the general family for the rest (PFM_NO_PATCH=1 at context creation: general family alone)
-    const bool overlay3 = !cart && c->v.dim == 3 && !c->levels3.empty() && c->kernel_path != 0 && phase != 1 && !split;
-    const bool patches = (!cart && c->v.dim == 2 && c->n_patch_blocks > 0 && c->kernel_path != 0 && phase != 1) || overlay3;
-    if (patches)
-      {
-        const int rcp = overlay3 ? ensure_overlay3_ready(c) : ensure_patch_ready(c);
-        if (rcp)
-          return rcp;
-      }
-    else if (!cart && c->full_colours_lazy)
-      {
-        try
-          {
-            ensure_full_colours(c); // the general family over all cells of a context that has only run with its overlay so far
-          }
-        catch (const HipFail &f)
-          {
-            return hipfail(c, f.e, f.what);
-          }
-        catch (const std::bad_alloc &)
-          {
-            return fail(c, PFM_ERR_NOMEM, "host allocation failed");
-          }
-      }
-    // 3-D cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*)
-    bool gather = false;
-    if (!cart && c->v.dim == 3 && c->hang_gather && !split && phase != 1)
-      {
-        try
-          {
-            gather = ensure_hang_gather(c);
-          }
-        catch (const HipFail &f)
-          {
-            return hipfail(c, f.e, f.what);
-          }
-        catch (const std::bad_alloc &)
-          {
-            return fail(c, PFM_ERR_NOMEM, "host allocation failed");
-          }
-      }
+    AssemblyPlan plan = plan_assembly(c, residual_only, phase, d_values);
+    bool gather_ready = false;
+    if (const int rct = ensure_tables(c, plan, gather_ready))
+      return rct;
+    plan.after_tables(c, gather_ready);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (c->timing && phase == 2)
       ev1 = c->ev_pool[c->ev_used - 1].second; // opened by phase 1
-    if (c->timing && phase != 2)
-      {
-        if (c->ev_used == c->ev_pool.size())
-          {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)
-              return fail(c, PFM_ERR_HIP, "hipEventCreate");
-            c->ev_pool.emplace_back(a, b);
-          }
-        ev0 = c->ev_pool[c->ev_used].first;
-        ev1 = c->ev_pool[c->ev_used].second;
-        ++c->ev_used;
-        (void)hipEventRecord(ev0, c->stream);
-      }
-    // Optional (PFM_SIDE_STREAM=1): residual kernel on a side stream next to the Jacobian kernels.  Measured on MI355X at 216^3: no gain (21.4 vs 21.1 ms per assembly),
-    // the kernels do not share CUs usefully; off by default.
-    hipStream_t s_res = c->stream;
-    // The two Jacobian kernels of a 3-D box next to each other (default): with equal LDS allocations (64 granules of 1280 B
-    // each) any freed slot of a CU takes a workgroup of either kernel, the (u,u) and the phase-field workgroups mix and
-    // fill each other's stalls: 14.07 -> 13.75 ms per assembly at 216^3 (PFM_JAC_SEQUENTIAL=1: one after the other).
-    static const bool jac_sequential = getenv("PFM_JAC_SEQUENTIAL") != nullptr;
-    const bool pair = cart && !jac_sequential && cart_jacobian_pair(c->v, c->cv, c->prm, residual_only, phase);
-    if (pair)
-      {
-        // deferred placeholder patches: one entry per flagged displacement dof at most
-        if (c->cv.patch_cap < c->n_flag_u || !c->cv.patch_count)
-          {
-            for (void *q : {(void *)c->cv.patch_idx, (void *)c->cv.patch_val, (void *)c->cv.patch_count})
-              if (q)
-                (void)hipFree(q);
-            c->device_bytes -= (int64_t)c->cv.patch_cap * 16 + (c->cv.patch_count ? 4 : 0);
-            c->cv.patch_idx = nullptr, c->cv.patch_val = nullptr, c->cv.patch_count = nullptr;
-            const size_t cap = (size_t)std::max<int64_t>(c->n_flag_u, 1);
-            if (hipMalloc((void **)&c->cv.patch_idx, cap * sizeof(long long)) != hipSuccess ||
-                hipMalloc((void **)&c->cv.patch_val, cap * sizeof(double)) != hipSuccess ||
-                hipMalloc((void **)&c->cv.patch_count, sizeof(int)) != hipSuccess)
-              return fail(c, PFM_ERR_NOMEM, "patch list");
-            c->cv.patch_cap = (int)std::min<size_t>(cap, 0x7fffffff);
-            c->device_bytes += (int64_t)c->cv.patch_cap * 16 + 4;
-          }
-        if (hipMemsetAsync(c->cv.patch_count, 0, sizeof(int), c->stream) != hipSuccess)
-          return fail(c, PFM_ERR_HIP, "patch list reset");
-      }
-    // 2-D boxes never fork: the second launch of k_cart2d_cells (phase-field rows) reads the mean |diagonal| the first one
-    // leaves in CartView::cell_avg, so it must follow it on the same stream.  (The fork was measured at 0.262 -> 0.259 ms of
-    // kernel time at 1000^2 and was off by default; with an event between the launches nothing of that overlap is left.)
-    const bool fork = cart && !residual_only && phase == 0 && (pair || (c->v.dim != 2 && getenv("PFM_SIDE_STREAM")));
-    if (fork)
-      {
-        if (!c->side_stream)
-          {
-            // PFM_SIDE_PRIO (A/B runs): -1 = lowest, 1 = highest dispatch priority for the stream of the phase-field kernel
-            static const int side_prio = getenv("PFM_SIDE_PRIO") ? atoi(getenv("PFM_SIDE_PRIO")) : 0;
-            int prio_lo = 0, prio_hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-            const hipError_t es = side_prio == 0 ? hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking)
-                                                 : hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, side_prio > 0 ? prio_hi : prio_lo);
-            if (es != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)
-              return fail(c, PFM_ERR_HIP, "side stream");
-          }
-        s_res = c->side_stream;
-        e = hipEventRecord(c->ev_fork, c->stream);
-        if (e == hipSuccess)
-          e = hipStreamWaitEvent(s_res, c->ev_fork, 0);
-        if (e != hipSuccess)
-          return hipfail(c, e, "fork");
-      }
-    // zero the outputs (cracks.cc:2133-2137); the row-owner kernels of the cartesian path
-    // write every entry exactly once and need no zeroing pass
-    if (!cart && phase == 1)
-      return PFM_OK; // the general family is not cut into interior / boundary work: everything in phase 2
-    if (!cart)
-      e = hipMemsetAsync(d_res_pde, 0, sizeof(double) * (size_t)c->n_owned_dofs(), c->stream);
-    if (!cart && e == hipSuccess && residual_only)
-      e = hipMemsetAsync(d_res_tot, 0, sizeof(double) * (size_t)c->n_owned_dofs(), c->stream);
-    if (e == hipSuccess && !residual_only)
-      for (int b = 0; b < c->n_blocks && e == hipSuccess; ++b)
-        {
-          if (!d_values[b] && c->block_nnz(b) > 0)
-            return fail(c, PFM_ERR_BAD_ARG, "null matrix block");
-          // the row-owner kernels write every value once, the structurally zero (u,phi) block
-          // of the blocked layout included (k_cart_phi4)
-          if (!cart && !patches)
-            e = hipMemsetAsync(d_values[b], 0, sizeof(double) * (size_t)c->block_nnz(b), c->stream);
-        }
-    if (e == hipSuccess && patches && !residual_only && c->n_rows_general > 0 &&
-        launch_zero_rows(c->v, d_values, c->d_rows_general, c->n_rows_general, c->stream) != PFM_OK)
-      return fail(c, PFM_ERR_HIP, "zero the rows of the general family");
-    if (e != hipSuccess)
-      return hipfail(c, e, "zero outputs");
-    // general family: the atomic class (cells with hanging vertices) on the side stream next to the colour classes, behind
-    // the zeroing of the outputs (DevView::cell_ring; PFM_GENERAL_SEQUENTIAL=1: one after the other)
-    static const bool general_sequential = getenv("PFM_GENERAL_SEQUENTIAL") != nullptr;
-    // (a residual-only assembly keeps the stream order: its atomic class takes 15 us, less than a fork and a join)
-    // overlay: the patch kernel on the stream, every class of the (small) rest of the general family on the side stream
-    const bool fork_general = !cart && !general_sequential &&
-                              ((!residual_only && c->v.cell_ring != nullptr) || (patches && c->n_general_cells > 0));
-    if (fork_general)
-      {
-        if (!c->side_stream)
-          {
-            if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)
-              return fail(c, PFM_ERR_HIP, "side stream");
-          }
-        e = hipEventRecord(c->ev_fork, c->stream);
-        if (e == hipSuccess)
-          e = hipStreamWaitEvent(c->side_stream, c->ev_fork, 0);
-        if (e != hipSuccess)
-          return hipfail(c, e, "fork (general family)");
-      }
-    if (cart && !residual_only && c->v.dim == 3 && c->scal_dirty)
-      {
-        // off the hot path: once per pfm_set_params, complete before any kernel of any stream may read it
-        int rcs = upload_mat_scal(c->prm, c->cv, c->d_scal, c->stream);
-        if (rcs == PFM_OK && hipStreamSynchronize(c->stream) != hipSuccess)
-          rcs = PFM_ERR_HIP;
-        if (rcs)
-          return fail(c, rcs, "scalar tables");
-        c->scal_dirty = false;
-      }
-    pfm::CartView cv_launch = c->cv;
-    cv_launch.up_block_cleared = 0;
-    // 2-D box, blocked layout: the structurally zero (u,phi) block (cracks.cc:2333-2337) by a fill in front of the kernels
-    // (PFM_CART2D_NO_FILL: the kernel writes the zeros with the rows, A/B runs)
-    if (cart && c->v.dim == 2 && !residual_only && phase <= 1 && c->v.layout == PFM_LAYOUT_BLOCKED && c->n_blocks == 4 && d_values[1] &&
-        getenv("PFM_CART2D_NO_FILL") == nullptr && getenv("PFM_CART2D_ONE_LAUNCH") == nullptr)
-      {
-        if (hipMemsetAsync(d_values[1], 0, sizeof(double) * (size_t)c->block_nnz(1), c->stream) != hipSuccess)
-          return fail(c, PFM_ERR_HIP, "clear the (u,phi) block");
-        cv_launch.up_block_cleared = 1;
-      }
-    if (cart && c->v.dim == 2 && phase == 2 && c->v.layout == PFM_LAYOUT_BLOCKED && getenv("PFM_CART2D_NO_FILL") == nullptr &&
-        getenv("PFM_CART2D_ONE_LAUNCH") == nullptr && !residual_only)
-      cv_launch.up_block_cleared = 1; // cleared in phase 1 of this overlapped assembly
-    // (round 6, measured and removed: clearing the structurally zero (u,phi) block with a fill on a third stream instead of
-    // by 21 of the 49 store instructions of every copy-out of k_cart_phi4 -- 10.95 -> 11.35 ms per assembly at 216^3,
-    // profiles/r06/ab_up_fill.txt: the fill takes bandwidth in a burst and dispatch slots from the pair)
-    if (!pair)
-      cv_launch.patch_idx = nullptr, cv_launch.patch_val = nullptr, cv_launch.patch_count = nullptr, cv_launch.patch_cap = 0;
-    int rc;
-    if (cart)
-      rc = launch_assemble_cart(c->v, cv_launch, c->prm, residual_only, d_values, d_res_pde, d_res_tot, c->stream, pair || fork ? s_res : c->stream, c->d_scal, phase);
-    else if (patches)
-      {
-        // the patch kernel: every regular row is written once, with plain stores; next to it (side stream) the general
-        // family over the cells that touch a non-regular row (it skips the regular ones: DevView::row_patch), its classes one
-        // after the other
-        rc = PFM_OK;
-        if (overlay3)
-          {
-            // the row-owner kernels of the cartesian family on every level lattice: each level on a stream of its own, forked
-            // off the context's stream (a level lattice of 6e5 nodes fills a third of the chip's dispatch slots; the levels
-            // write disjoint rows) when PFM_OVERLAY3_CONCURRENT=1 is set.  Default: one after the other on the context's
-            // stream -- measured the better of the two (profiles/r05/ov3_ab.txt: 4.56 against 4.86 ms per Jacobian)
-            static const bool levels_sequential = getenv("PFM_OVERLAY3_CONCURRENT") == nullptr;
-            const size_t nl = c->levels3.size();
-            for (auto &lv : c->levels3)
-              if (rc == PFM_OK && !residual_only && lv.scal_dirty)
-                {
-                  rc = upload_mat_scal(c->prm, lv.cv, lv.d_scal, c->stream);
-                  lv.scal_dirty = rc != PFM_OK;
-                }
-            const bool par = nl > 1 && !levels_sequential && rc == PFM_OK;
-            if (par)
-              {
-                while (c->ov_streams.size() < nl)
-                  {
-                    hipStream_t st = nullptr;
-                    hipEvent_t ev = nullptr;
-                    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-                      return fail(c, PFM_ERR_HIP, "overlay level stream");
-                    c->ov_streams.push_back(st);
-                    c->ov_events.push_back(ev);
-                  }
-                if (!c->ov_fork && hipEventCreateWithFlags(&c->ov_fork, hipEventDisableTiming) != hipSuccess)
-                  return fail(c, PFM_ERR_HIP, "overlay level event");
-                e = hipEventRecord(c->ov_fork, c->stream);
-                for (size_t i = 0; i < nl && e == hipSuccess; ++i)
-                  e = hipStreamWaitEvent(c->ov_streams[i], c->ov_fork, 0);
-                if (e != hipSuccess)
-                  return hipfail(c, e, "fork (overlay levels)");
-              }
-            for (size_t i = 0; i < nl && rc == PFM_OK; ++i)
-              {
-                hipStream_t st = par ? c->ov_streams[i] : c->stream;
-                rc = launch_assemble_cart(c->v, c->levels3[i].cv, c->prm, residual_only, d_values, d_res_pde, d_res_tot, st, st, c->levels3[i].d_scal, 0);
-              }
-            if (par)
-              {
-                for (size_t i = 0; i < nl && e == hipSuccess; ++i)
-                  {
-                    e = hipEventRecord(c->ov_events[i], c->ov_streams[i]);
-                    if (e == hipSuccess)
-                      e = hipStreamWaitEvent(c->stream, c->ov_events[i], 0);
-                  }
-                if (e != hipSuccess)
-                  return hipfail(c, e, "join (overlay levels)");
-              }
-          }
-        else
-          rc = launch_assemble_patches(c->v, c->prm, residual_only, d_values, d_res_pde, d_res_tot, c->n_patch_blocks, c->stream);
-        pfm::DevView vg = c->v;
-        vg.color_cells = c->d_color_cells_reduced;
-        if (gather)
-          vg.cell_ring = nullptr; // nobody adds atomically: the cells at hanging vertices only write their scratch
-        else
-          vg.hs_K = nullptr, vg.hs_off = nullptr, vg.hs_RD = nullptr;
-        // 3-D overlay Jacobian: the class of the cells at hanging vertices (FP64 atomics, 4.7 of the general family's 6 ms at
-        // 1.1e6 cells) on a third stream next to the plain classes (DevView::cell_ring makes that safe)
-        hipStream_t s_atomic = nullptr;
-        // (PFM_HANGING_COLOURED: a hanging cell in a plain class adds to its PARENTS' rows without atomics; should a cell with
-        // more than 16 resolved nodes ever sit in the atomic class next to it, that class must not run beside the plain ones)
-        if (overlay3 && fork_general && !residual_only && (c->v.cell_ring || gather) && c->n_general_cells > 0 && !c->hanging_coloured)
-          {
-            int prio_lo = 0, prio_hi = 0; // (numerically lower = higher priority) the long pole gets its workgroups dispatched first
-            (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-            if (!c->atomic_stream && (hipStreamCreateWithPriority(&c->atomic_stream, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-                                      hipEventCreateWithFlags(&c->ev_atomic, hipEventDisableTiming) != hipSuccess))
-              return fail(c, PFM_ERR_HIP, "atomic-class stream");
-            e = hipStreamWaitEvent(c->atomic_stream, c->ev_fork, 0);
-            if (e != hipSuccess)
-              return hipfail(c, e, "fork (atomic class)");
-            s_atomic = c->atomic_stream;
-          }
-        if (rc == PFM_OK && c->n_general_cells > 0)
-          rc = launch_assemble_general(vg, c->prm, residual_only, d_values, d_res_pde, d_res_tot, fork_general ? c->side_stream : c->stream,
-                                       c->color_ptr_reduced, s_atomic);
-        if (s_atomic)
-          {
-            e = hipEventRecord(c->ev_atomic, s_atomic);
-            if (e == hipSuccess)
-              e = hipStreamWaitEvent(c->stream, c->ev_atomic, 0);
-            if (e != hipSuccess)
-              return hipfail(c, e, "join (atomic class)");
-          }
-      }
-    else
-      {
-        pfm::DevView vg = c->v;
-        vg.row_patch = nullptr; // no overlay in this assembly: the general family writes every row
-        if (gather)
-          vg.cell_ring = nullptr;
-        else
-          vg.hs_K = nullptr, vg.hs_off = nullptr, vg.hs_RD = nullptr;
-        rc = launch_assemble_general(vg, c->prm, residual_only, d_values, d_res_pde, d_res_tot, c->stream, c->color_ptr,
-                                     (fork_general && !c->hanging_coloured) ? c->side_stream : nullptr);
-      }
-    if (fork_general)
-      {
-        e = hipEventRecord(c->ev_join, c->side_stream);
-        if (e == hipSuccess)
-          e = hipStreamWaitEvent(c->stream, c->ev_join, 0);
-        if (e != hipSuccess)
-          return hipfail(c, e, "join (general family)");
-      }
-    if (gather && rc == PFM_OK && !cart)
-      {
-        // behind every class and every level kernel (joined above): the rows the cells at hanging vertices reach, in list order
-        pfm::DevView vg = c->v;
-        if (!patches)
-          vg.row_patch = nullptr;
-        rc = launch_hanging_gather(vg, c->prm, residual_only, d_values, d_res_pde, d_res_tot, c->d_hg_rows, c->d_hg_ptr, c->d_hg_list,
-                                   c->n_hg_rows, c->stream);
-      }
-    if (fork)
-      {
-        e = hipEventRecord(c->ev_join, s_res);
-        if (e == hipSuccess)
-          e = hipStreamWaitEvent(c->stream, c->ev_join, 0);
-        if (e != hipSuccess)
-          return hipfail(c, e, "join");
-      }
-    if (pair && rc == PFM_OK)
-      rc = launch_cart_apply_patches(c->cv, d_values[0], c->stream, c->v.status);
-    if (phase == 1)
+    else if (c->timing)
+      if (const int rco = open_interval(c, ev0, ev1))
+        return rco;
+    if (plan.nothing)
+      return PFM_OK;
+    if (const int rcz = zero_outputs(c, plan, d_values, d_res_pde, d_res_tot))
+      return rcz;
+    int rc = PFM_OK; // of the launches
+    if (const int rcf = plan.cart      ? assemble_box(c, plan, d_values, d_res_pde, d_res_tot, rc)
+                        : plan.patches ? assemble_overlay(c, plan, d_values, d_res_pde, d_res_tot, rc)
+                                       : assemble_general(c, plan, d_values, d_res_pde, d_res_tot, rc))
+      return rcf;
+    if (phase == 1) // the interval stays open for phase 2
       return rc ? fail(c, rc, "assemble launch failed (interior tiles)") : PFM_OK;
-    if (rc == PFM_OK && overlay_uu && c->scal_dirty)
-      {
-        rc = upload_mat_scal(c->prm, c->cv, c->d_scal, c->stream);
-        c->scal_dirty = rc != PFM_OK;
-      }
-    if (rc == PFM_OK && overlay_uu)
-      rc = launch_cart_uu_only(c->v, c->cv, c->prm, d_values[0], c->stream, c->d_scal);
     if (ev1)
       (void)hipEventRecord(ev1, c->stream);
-    if (rc)
-      return fail(c, rc, "assemble launch failed");
-    return PFM_OK;
+    return rc ? fail(c, rc, "assemble launch failed") : PFM_OK;
   }
 
   int pfm_assemble_device(pfm_ctx *c, int residual_only, double *const *d_values, double *d_res_pde, double *d_res_tot)
@@ -4046,18 +4042,8 @@ extern "C"
         c->timing = false;
         hipEvent_t a = nullptr, b = nullptr;
         if (timing)
-          {
-            if (c->ev_used == c->ev_pool.size())
-              {
-                if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)
-                  return fail(c, PFM_ERR_HIP, "hipEventCreate");
-                c->ev_pool.emplace_back(a, b);
-              }
-            a = c->ev_pool[c->ev_used].first;
-            b = c->ev_pool[c->ev_used].second;
-            ++c->ev_used;
-            (void)hipEventRecord(a, c->stream);
-          }
+          if (const int rco = open_interval(c, a, b))
+            return rco;
         const int rc = assemble_impl(c, residual_only, d_values, d_res_pde, d_res_tot, c->force_phase);
         if (timing)
           (void)hipEventRecord(b, c->stream);
@@ -4065,6 +4051,28 @@ extern "C"
         return rc;
       }
     return assemble_impl(c, residual_only, d_values, d_res_pde, d_res_tot, 0);
+  }
+
+  // assemble_nl_residual() of the line search (cracks.cc:2942-2957, 2507-2512): solution := d_solution, then the residuals.
+  // On a single-rank box (2-D or 3-D lattice) the residual kernel reads d_solution itself (DevView::fused_solution); everywhere else this
+  // is pfm_state_set_solution + pfm_assemble_device(residual_only).  Ranks with peers must import ghosts in between: they
+  // call the two entry points themselves.
+  int pfm_assemble_nl_residual_device(pfm_ctx *c, const double *d_solution, double *d_res_pde, double *d_res_tot)
+  {
+    if (!c || (!d_solution && c->n_owned_dofs() != 0))
+      return PFM_ERR_BAD_ARG;
+    if (!c->peers.empty())
+      return fail(c, PFM_ERR_BAD_ARG, "pfm_assemble_nl_residual_device: a rank with peers imports ghosts between the scatter and the assembly");
+    const bool fuse = c->kernel_path == 1 && !stress_split(c) && c->v.n_owned == c->v.n_nodes && c->v.n_owned > 0 && Switches::fused_scatter();
+    if (!fuse)
+      {
+        const int rc = state_set_impl(c, d_solution, nullptr, nullptr, 1);
+        return rc ? rc : assemble_impl(c, 1, nullptr, d_res_pde, d_res_tot, 0);
+      }
+    c->v.fused_solution = d_solution;
+    const int rc = assemble_impl(c, 1, nullptr, d_res_pde, d_res_tot, 0);
+    c->v.fused_solution = nullptr;
+    return rc;
   }
 
   int pfm_ctx_force_phase(pfm_ctx *c, int phase)
@@ -4110,28 +4118,18 @@ extern "C"
     if (c->peers.empty())
       return assemble_impl(c, residual_only, d_values, d_res_pde, d_res_tot, 0);
     (void)hipSetDevice(c->device);
-    if (!c->side_stream)
-      {
-        if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)
-          return fail(c, PFM_ERR_HIP, "side stream");
-      }
-    {
-      const int rcl = ensure_overlap_lists(c);
-      if (rcl)
-        return rcl;
-    }
+    int rc = ensure_side_stream(c);
+    if (rc == PFM_OK)
+      rc = ensure_overlap_lists(c);
     // fork behind the state scatter; the pack kernel of the exchange reads the owned node state
-    hipError_t e = hipEventRecord(c->ev_fork, c->stream);
-    if (e == hipSuccess)
-      e = hipStreamWaitEvent(c->side_stream, c->ev_fork, 0);
-    if (e != hipSuccess)
-      return hipfail(c, e, "fork");
-    int rc = halo_exchange_on(c, comm, peer_ranks, c->side_stream);
+    if (rc == PFM_OK)
+      rc = fork_to(c, c->stream, c->side_stream, c->ev_fork, "fork");
+    if (rc == PFM_OK)
+      rc = halo_exchange_on(c, comm, peer_ranks, c->side_stream);
     if (rc)
       return rc;
-    e = hipEventRecord(c->ev_join, c->side_stream);
+    // the join in two parts around phase 1, which records neither event again: phase 1 forks nothing
+    hipError_t e = hipEventRecord(c->ev_join, c->side_stream);
     if (e != hipSuccess)
       return hipfail(c, e, "join event");
     rc = assemble_impl(c, residual_only, d_values, d_res_pde, d_res_tot, 1); // interior: no ghost node is read

@@ -294,9 +294,10 @@ def test_cart_residual_with_old_timestep_phase_field(dim, n):
 
 
 def test_jacobian_pair_sequential_and_residual_kernel_agree(tmp_path):
-    """The same 3-D assembly in its three launch modes: default (the (u,u) and the phase-field kernel next to each other on
-    two streams, residual from the matrix rows, deferred placeholder patches), PFM_JAC_SEQUENTIAL=1 (one after the other)
-    and PFM_RES_KERNEL=1 (quadrature residual kernel) -- on a box with several tiles, partial tiles, z-chunks, constraint
+    """The same 3-D assembly in its four launch modes: default (the (u,u) and the phase-field kernel next to each other on
+    two streams, residual from the matrix rows, deferred placeholder patches), PFM_JAC_SEQUENTIAL=1 (one after the other),
+    PFM_JAC_SEQUENTIAL=1 PFM_SIDE_STREAM=1 (the fork without the pair: the residual launch on the side stream) and
+    PFM_RES_KERNEL=1 (quadrature residual kernel) -- on a box with several tiles, partial tiles, z-chunks, constraint
     flags and both layouts.  The mode is chosen when the library is first used, hence one process each."""
     import os
     import subprocess
@@ -319,14 +320,17 @@ def test_jacobian_pair_sequential_and_residual_kernel_agree(tmp_path):
         "np.save(sys.argv[1], np.concatenate(out))\n"
         "np.save(sys.argv[2], np.concatenate(rhs))\n")
     val, rhs = {}, {}
-    for tag, env in (("rows", {}), ("rows_seq", {"PFM_JAC_SEQUENTIAL": "1"}), ("quad", {"PFM_RES_KERNEL": "1"})):
+    modes = (("rows", {}), ("rows_seq", {"PFM_JAC_SEQUENTIAL": "1"}), ("rows_seq_side", {"PFM_JAC_SEQUENTIAL": "1", "PFM_SIDE_STREAM": "1"}),
+             ("quad", {"PFM_RES_KERNEL": "1"}))
+    for tag, env in modes:
         f, g = tmp_path / f"{tag}.npy", tmp_path / f"{tag}_rhs.npy"
-        e = {k: v for k, v in os.environ.items() if k not in ("PFM_RES_KERNEL", "PFM_JAC_SEQUENTIAL")}
+        e = {k: v for k, v in os.environ.items() if k not in ("PFM_RES_KERNEL", "PFM_JAC_SEQUENTIAL", "PFM_SIDE_STREAM")}
         e.update(env)
         subprocess.run([sys.executable, str(script), str(f), str(g)], check=True, env=e, timeout=600)
         val[tag], rhs[tag] = np.load(f), np.load(g)
     # side by side or one after the other: the same kernels, the same bits (run-to-run reproducibility)
     assert np.array_equal(val["rows"], val["rows_seq"]) and np.array_equal(rhs["rows"], rhs["rows_seq"])
+    assert np.array_equal(val["rows"], val["rows_seq_side"]) and np.array_equal(rhs["rows"], rhs["rows_seq_side"])
     # the quadrature residual against the residual from the rows: round-off apart; the matrix to round-off as well
     assert val["rows"].shape == val["quad"].shape and linf_scaled(val["rows"], val["quad"]) < TOL
     assert rhs["rows"].shape == rhs["quad"].shape and linf_scaled(rhs["rows"], rhs["quad"]) < TOL
