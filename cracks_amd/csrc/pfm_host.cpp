@@ -1258,9 +1258,11 @@ namespace
     c->color_ptr.swap(col.ptr);
     if (col.overflow)
       {
-        // (never seen: a node of more than 62 cells) every cell adds atomically
+        // a node of more than 62 cells: every cell adds atomically (the rule of pfm_ctx_create, which
+        // tests/test_gpu_topology.py reaches with fan2d_closed64 and fan3d_41)
         std::vector<uint8_t> all((size_t)NC, 1);
         v.cell_ring = dev_upload(c, all.data(), all.size());
+        c->colour_overflow = true;
       }
     c->full_colours_lazy = false;
   }
@@ -2584,8 +2586,10 @@ extern "C"
             c->color_ptr.swap(full.ptr);
             if (full.overflow)
               {
-                ring.assign((size_t)NC, 1); // (never seen: a node of more than 62 cells) every cell adds atomically
+                // a node of more than 62 cells (tests/test_gpu_topology.py: fan2d_closed64, fan3d_41): every cell adds atomically
+                ring.assign((size_t)NC, 1);
                 v.cell_ring = dev_upload(c, ring.data(), ring.size());
+                c->colour_overflow = true;
               }
           }
         clk.mark("colour classes");
@@ -3877,9 +3881,12 @@ extern "C"
       return vg;
     if (p.patches)
       vg.color_cells = c->d_color_cells_reduced;
-    if (p.gather)
-      vg.cell_ring = nullptr; // nobody adds atomically: the cells at hanging vertices only write their scratch
-    else
+    // gather: the cells at hanging vertices only write their scratch and nobody adds atomically -- unless cells that found
+    // no colour sit in the last class next to them (colour_overflow): those add to the outputs with atomics, on the side
+    // stream of a Jacobian assembly, so the plain classes keep the ring and add atomically as well
+    if (p.gather && !c->colour_overflow)
+      vg.cell_ring = nullptr;
+    if (!p.gather)
       vg.hs_K = nullptr, vg.hs_off = nullptr, vg.hs_RD = nullptr;
     return vg;
   }

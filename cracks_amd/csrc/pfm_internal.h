@@ -398,6 +398,7 @@ struct pfm_ctx
   int64_t n_hcells = 0;           // cells at hanging vertices (records of DevView::cres)
   bool hang_gather = false;       // decided at pfm_ctx_create (PFM_HANGING_ATOMIC=1: off)
   bool hang_gather_ready = false; // tables and scratch exist
+  bool colour_overflow = false;   // cells without a hanging vertex sit in the last class (a node of more than 62 cells)
   pfm::DevBuf buf_norm_partial; // pfm_residual_norms: [2048][2] block partials + the 3 results
   pfm::DevBuf buf_partial;      // 3-wide reductions of pfm_newton.hip / pfm_postproc.hip: [blocks][3] partials + the 3 results
   pfm::DevBuf buf_cell_owned;   // the owned-cell mask of the entry that runs (upload_mask, pfm_entry.h)

@@ -1775,8 +1775,8 @@ namespace pfm
     // distinct accumulators, and the summation order of every value is the order of the list -- no atomics, bitwise
     // reproducible.  Masks (constraint flags of row and column) as in the atomic class; lane 15 of an entry's group adds the
     // placeholder diagonal of a constrained vertex (deal.II distribute_local_to_global) and the residual entries.
-    // Rows of more than HG_DEG neighbours (none on 2:1 meshes of hexes) take the entries one by one with plain
-    // read-modify-writes of the outputs (same order).
+    // Rows of more than HG_DEG neighbours (none on 2:1 meshes of hexes; tests/test_gpu_topology.py: fan3d_30_hanging) take the
+    // entries one by one with plain read-modify-writes of the outputs (same order).
     constexpr int HG_DEG = 64;
     template <bool FULL>
     __global__ __launch_bounds__(256) void k_hanging_gather(DevView v, pfm_params prm, Vals vals, double *__restrict__ res_pde,

@@ -5,7 +5,11 @@ from __future__ import annotations
 import numpy as np
 import scipy.sparse as sp
 
+import oracle_api as O
+from cracks_amd import mesh as M
 from cracks_amd.assembler import Context, node_flags_from_dof_flags
+
+TOL = 1e-12  # README: |x - x_ref|_inf < 1e-12 max(1, |x_ref|_inf)
 
 
 def make_context(case, **kw) -> Context:
@@ -35,6 +39,37 @@ def linf_scaled(a, b) -> float:
     a = np.asarray(a)
     b = np.asarray(b)
     return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
+
+
+def oracle(c, residual_only):
+    rowptr = colind = None
+    if not residual_only:
+        rowptr, colind = M.dof_sparsity(c.mesh, c.layout)
+    r = O.assemble(c.mesh, c.layout, c.params, c.sol, c.old, c.oldold, c.cu, c.ch, residual_only,
+                   rowptr, colind, c.cell_lambda, c.cell_mu)
+    assert r.err == 0
+    return r, rowptr, colind
+
+
+def full_parity(c, tol=TOL, ctx=None):
+    """Full assembly, then the residual-only call, of a Case against the oracle: identical pattern, every matrix entry and
+    both residuals within tol.  ctx: a context of the case to run on (default: a new one); returned."""
+    if ctx is None:
+        ctx = make_context(c)
+    values, res_pde, _ = ctx.assemble_host(c.sol, c.old, c.oldold, residual_only=False)
+    r, rowptr, colind = oracle(c, False)
+    A_ref = sp.csr_matrix((r.values, colind, rowptr), shape=(c.layout.n_dofs,) * 2)
+    A = blocks_to_global(ctx, c.layout, values)
+    # identical pattern (the library's canonical pattern == make_sparsity_pattern stand-in)
+    A.sort_indices()
+    assert A.nnz == A_ref.nnz and (A.indptr == A_ref.indptr).all() and (A.indices == A_ref.indices).all()
+    assert linf_scaled(A.data, A_ref.data) < tol
+    assert linf_scaled(res_pde, r.residual_pde) < tol
+    _, res_pde2, res_tot2 = ctx.assemble_host(c.sol, c.old, c.oldold, residual_only=True)
+    r2, _, _ = oracle(c, True)
+    assert linf_scaled(res_pde2, r2.residual_pde) < tol
+    assert linf_scaled(res_tot2, r2.residual_total) < tol
+    return ctx
 
 
 def exchange_ghosts(lps, ctxs, dim: int):

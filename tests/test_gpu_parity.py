@@ -10,21 +10,11 @@ import pytest
 import cases
 import oracle_api as O
 from cracks_amd import mesh as M
-from gpu_util import blocks_to_global, linf_scaled, make_context
+from gpu_util import full_parity as _full_parity, linf_scaled, make_context, oracle as _oracle
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-12
-
-
-def _oracle(c, residual_only):
-    rowptr = colind = None
-    if not residual_only:
-        rowptr, colind = M.dof_sparsity(c.mesh, c.layout)
-    r = O.assemble(c.mesh, c.layout, c.params, c.sol, c.old, c.oldold, c.cu, c.ch, residual_only,
-                   rowptr, colind, c.cell_lambda, c.cell_mu)
-    assert r.err == 0
-    return r, rowptr, colind
 
 
 @pytest.mark.parametrize("make", cases.ALL_KATS, ids=lambda f: f.__name__)
@@ -37,26 +27,6 @@ def test_step0_residual_golden_through_the_abi(make):
     r, _, _ = _oracle(c, True)
     assert linf_scaled(res_pde, r.residual_pde) < TOL
     assert linf_scaled(res_tot, r.residual_total) < TOL
-
-
-def _full_parity(c, tol=TOL):
-    import scipy.sparse as sp
-
-    ctx = make_context(c)
-    values, res_pde, _ = ctx.assemble_host(c.sol, c.old, c.oldold, residual_only=False)
-    r, rowptr, colind = _oracle(c, False)
-    A_ref = sp.csr_matrix((r.values, colind, rowptr), shape=(c.layout.n_dofs,) * 2)
-    A = blocks_to_global(ctx, c.layout, values)
-    # identical pattern (the library's canonical pattern == make_sparsity_pattern stand-in)
-    A.sort_indices()
-    assert A.nnz == A_ref.nnz and (A.indptr == A_ref.indptr).all() and (A.indices == A_ref.indices).all()
-    assert linf_scaled(A.data, A_ref.data) < tol
-    assert linf_scaled(res_pde, r.residual_pde) < tol
-    _, res_pde2, res_tot2 = ctx.assemble_host(c.sol, c.old, c.oldold, residual_only=True)
-    r2, _, _ = _oracle(c, True)
-    assert linf_scaled(res_pde2, r2.residual_pde) < tol
-    assert linf_scaled(res_tot2, r2.residual_total) < tol
-    return ctx
 
 
 @pytest.mark.parametrize("make", cases.ALL_KATS, ids=lambda f: f.__name__)
