@@ -1190,8 +1190,10 @@ namespace pfm
           stamp(0);
           if (t < NPH && s.flag[(ck + 1) & 3][2 * t])
             s.anyflag[(ck + 1) & 3] = 1;
+          // (the 49 rows sit in the lanes of ONE wave: every lane that writes holds the same value -- bit 1: some row of the
+          // tile-plane has its CSR slots permuted, the generic copy-out then looks them up)
           if (ck >= kA && t >= 128 && t < 128 + NPN && s.off[cp][t - 128] >= 0 && s.deg[cp][t - 128] != 0x7ffffff)
-            s.irregular[cp] = 1;
+            s.irregular[cp] = __ballot(((unsigned)s.deg[cp][t - 128] >> 31) != 0) != 0 ? 3 : 1;
           if (ck >= kA && t >= 128 && t < 128 + NPN && (s.off[cp][t - 128] < 0 || ((unsigned)s.deg[cp][t - 128] & 0x7ffffffu) != 0x7ffffffu))
             s.incomplete[cp] = 1;
 
@@ -1599,6 +1601,13 @@ namespace pfm
                       // than 27 neighbours
                       const unsigned *nfl = &s.flag[(ck + fe_oz - 1) & 3][2 * fe_nbo];
                       const unsigned below = (1u << fe_o) - 1u;
+                      // Round 7: the loop in two versions, selected per tile-plane (bit 1 of s.irregular).  The look-up of a
+                      // permuted slot is a global load in one arm of a branch: the compiler waits for it at the join with
+                      // vmcnt(0) on every path, i.e. every row waits for the stores of the row before it.  Without a permuted
+                      // row in the tile-plane (the faces of a lattice-ordered box, flagged planes, partial tiles) the loop has
+                      // no global load and no such wait.  Its store count depends on the rows' masks: nst stays 0.
+                      auto generic_rows = [&](auto Perm) __attribute__((always_inline)) {
+                        constexpr bool PERM = decltype(Perm)::value;
 #pragma unroll 1
                       for (int nl = fe_sub; nl < NPN; nl += 2)
                         {
@@ -1624,9 +1633,12 @@ namespace pfm
                           if (off >= 0 && ((nmask >> fe_o) & 1u)) // owned node, neighbour inside the mesh
                             {
                               int sl = __popc(nmask & below);
-                              if (nmask >> 31) // row not in lattice order: permutation of the ranks
-                                sl = cv.row_perm[off + sl];
-                              asm volatile("" ::"v"(sl));
+                              if constexpr (PERM)
+                                {
+                                  if (nmask >> 31) // row not in lattice order: permutation of the ranks
+                                    sl = cv.row_perm[off + sl];
+                                  asm volatile("" ::"v"(sl));
+                                }
                               if constexpr (NCOL == 3)
                                 {
                                   if (fe_pp)
@@ -1641,6 +1653,11 @@ namespace pfm
                                 vals_uu[16 * off + (long long)3 * 4 * __popc(nmask & 0x7ffffffu) + sl * 4 + fe_d] = val;
                             }
                         }
+                      };
+                      if (__builtin_amdgcn_readfirstlane(s.irregular[cp]) & 2)
+                        generic_rows(std::true_type{});
+                      else
+                        generic_rows(std::false_type{});
                     }
                 }
               stamp(8);

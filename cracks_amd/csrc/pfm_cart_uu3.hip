@@ -341,7 +341,8 @@ namespace pfm
       double pres[RES ? 3 * NN3 : 1]; // pressure part of the residual rows of the current plane [component][node]
       unsigned char ok[NR3], flag[NR3];
       int anyflag[4][2];               // per ring slot and request wave: some node of the plane carries a displacement flag
-      int irregular[2];                // by plane parity: some row is not a full, lattice-ordered 27-neighbour row
+      int irregular[2];                // by plane parity: bit 0 = some row is not a full, lattice-ordered 27-neighbour row,
+                                       // bit 1 = some row's CSR slots are a permutation of the lattice order (bit 31 of its mask)
     };
     static_assert(27 * CS3 <= NN3 * STG, "w*g scratch must fit in the staging buffer");
     static_assert(NN3 * STG <= 4 * TGRP3 && 2 * 8 * NN3 <= TGRP3, "second staging buffer in front of group 4, the residual sums inside it");
@@ -519,8 +520,9 @@ namespace pfm
             sh.rowbase[0][nl] = base;
             sh.mask[0][nl] = mask;
             const unsigned long long irr = __ballot(mask != 0x7ffffffu); // fewer than 27 neighbours, or not an owned node
+            const unsigned long long prm = __ballot((mask >> 31) != 0);  // some row's slots are a permutation of the ranks
             if (nl == 0)
-              sh.irregular[0] = irr != 0;
+              sh.irregular[0] = (irr != 0 ? 1 : 0) | (prm != 0 ? 2 : 0);
           }
         stamp(7); // thread 0: its own halo loads have returned and are stored
       }
@@ -644,8 +646,9 @@ namespace pfm
                           sh.mask[par][lane] = mask;
                         }
                       const unsigned long long irr = __ballot(mask != 0x7ffffffu);
+                      const unsigned long long prm = __ballot((mask >> 31) != 0);
                       if (lane == 0)
-                        sh.irregular[par] = irr != 0;
+                        sh.irregular[par] = (irr != 0 ? 1 : 0) | (prm != 0 ? 2 : 0);
                       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the landing zone is read out before it is requested into again
                     }
                   if (more)
@@ -969,7 +972,49 @@ namespace pfm
                   // permutation of that rank
                   const unsigned *rowmask = sh.mask[par];
                   constexpr int rowlen = 27 * NCOL;
-                  for (int f = t; f < NN3 * rowlen; f += NT3)
+                  // Round 7: two loops, selected per tile-plane.  The look-up of a permuted slot below is a global load in one
+                  // arm of a branch: the compiler waits for it at the join with vmcnt(0) on EVERY path, and vmcnt counts the
+                  // stores as well -- each position then waits for the store of the last one (profiles/HISTORY.md, round 2).
+                  // On a tile-plane without a permuted row (the faces of a lattice-ordered box) the loop has no global load
+                  // and no such wait: the LDS reads of three positions in one batch, then their stores.
+                  if (!(__builtin_amdgcn_readfirstlane(sh.irregular[par]) & 2))
+                    {
+                      constexpr int NPOS = NN3 * rowlen, NB = 3;
+#pragma unroll 1
+                      for (int f0 = t; f0 < NPOS; f0 += NB * NT3)
+                        {
+                          long long dst[NB];
+                          unsigned mk[NB];
+                          int od[NB];
+                          double val[NB];
+#pragma unroll
+                          for (int i = 0; i < NB; ++i)
+                            {
+                              const int f = min(f0 + i * NT3, NPOS - 1); // (clamped duplicates are dropped below)
+                              const int nl = f / rowlen, e = f - nl * rowlen;
+                              const int o = e / NCOL, d = e - o * NCOL;
+                              dst[i] = rowbase[nl];
+                              mk[i] = rowmask[nl];
+                              val[i] = lds_read64(stage + nl * STG + o * 3 + min(d, 2)); // (d = 3: zeroed below, no read in a branch)
+                              od[i] = o | (d << 8);
+                            }
+                          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                          for (int i = 0; i < NB; ++i)
+                            {
+                              const int o = od[i] & 0xff, d = od[i] >> 8;
+                              const unsigned mask = mk[i];
+                              if (f0 + i * NT3 < NPOS && dst[i] >= 0 && ((mask >> o) & 1u))
+                                {
+                                  const int sl = __popc(mask & ((1u << o) - 1u));
+                                  const int deg = __popc(mask & 0x7ffffffu);
+                                  vals[dst[i] + (long long)c * NCOL * deg + sl * NCOL + d] = (d < 3) ? val[i] : 0.0;
+                                }
+                            }
+                        }
+                    }
+                  else // some row with a permutation: one position at a time, as in rounds 1-6
+                    for (int f = t; f < NN3 * rowlen; f += NT3)
                     {
                       const int nl = f / rowlen, e = f - nl * rowlen;
                       const int o = e / NCOL, d = e - o * NCOL;

@@ -67,14 +67,44 @@ def instructions(body: str):
         yield s.split()[0]
 
 
-def compile_to_asm(src: str) -> str:
+def vmcnt0(body: str) -> int:
+    """Waits that drain every outstanding vector-memory instruction, stores included."""
+    return len(re.findall(r"s_waitcnt[^\n]*vmcnt\(0\)", body))
+
+
+def compile_to_asm(src: str, resources: bool = False, pattern: str = "") -> str:
     from cracks_amd import build as B
 
     out = tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
-    flags = [f for f in B.FLAGS if f != "-fPIC"]
-    subprocess.check_call([B.hipcc()] + flags + ["-I/opt/rocm/include", "-x", "hip", "--cuda-device-only", "-S", src, "-o", out],
-                          stderr=subprocess.DEVNULL)
+    # the flags the library is built with, the per-source ones included (without -disable-machine-licm k_cart_uu3 is
+    # another kernel: scratch spills and a vmcnt(0) in front of most stores)
+    flags = [f for f in B.FLAGS if f != "-fPIC"] + B.EXTRA_FLAGS.get(os.path.basename(src), [])
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    cmd = [B.hipcc()] + flags + ["-I" + os.path.join(rocm, "include"), "-x", "hip", "--cuda-device-only", "-S", src, "-o", out]
+    if resources:
+        cmd.append("-Rpass-analysis=kernel-resource-usage")
+    p = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
+    if p.returncode:
+        sys.stderr.write(p.stderr)
+        raise subprocess.CalledProcessError(p.returncode, cmd)
+    if resources:
+        print_resources(p.stderr, pattern)
     return out
+
+
+def print_resources(remarks: str, pattern: str):
+    """The compiler's resource-usage remarks (registers, scratch, LDS, occupancy), one line per kernel that matches."""
+    name, vals = None, {}
+    for line in remarks.split("\n") + ["Function Name: "]:
+        m = re.search(r"remark:\s+(?:Function Name: (\S*)|([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+))", line)
+        if not m:
+            continue
+        if m.group(1) is not None:
+            if name and (not pattern or re.search(pattern, name)):
+                print("resources %s: %s" % (name, ", ".join(f"{k} {v}" for k, v in vals.items())))
+            name, vals = m.group(1), {}
+        elif name:
+            vals[m.group(2).strip()] = m.group(3)
 
 
 def analyse(asm_path: str, pattern: str, blocks: bool, min_ins: int):
@@ -87,7 +117,7 @@ def analyse(asm_path: str, pattern: str, blocks: bool, min_ins: int):
         tot = collections.Counter(classify(op) for op in instructions(body))
         ops = collections.Counter(instructions(body))
         valu = sum(v for k, v in tot.items() if k.startswith("valu"))
-        rec = {"instructions": sum(tot.values()), "valu": valu, "classes": dict(sorted(tot.items())),
+        rec = {"instructions": sum(tot.values()), "valu": valu, "vmcnt0_waits": vmcnt0(body), "classes": dict(sorted(tot.items())),
                "fp64_share_of_valu": round(tot["valu_fp64"] / max(valu, 1), 4),
                "top_valu_ops": dict(collections.Counter({k: v for k, v in ops.items() if k.startswith("v_")}).most_common(14))}
         if blocks:
@@ -103,7 +133,7 @@ def analyse(asm_path: str, pattern: str, blocks: bool, min_ins: int):
                     bl.append({"block": lab, "n": n, "valu": v, "fp64": c["valu_fp64"], "rdwrlane": c["valu_rdwrlane"],
                                "mov": c["valu_mov"], "cmp_sel": c["valu_cmp_select"], "int": c["valu_int_other"],
                                "permute": c["valu_lane_permute"], "lds": c["lds"], "vmem": c["vmem"], "wait": c["s_waitcnt"],
-                               "salu": c["salu"] + c["smem"]})
+                               "salu": c["salu"] + c["smem"], "vmcnt0": vmcnt0(b)})
             rec["blocks"] = bl
         res[name] = rec
     return res
@@ -117,18 +147,20 @@ def main():
     ap.add_argument("--min", type=int, default=40)
     ap.add_argument("--json", default="")
     ap.add_argument("--asm", default="", help="use this .s instead of compiling")
+    ap.add_argument("--resources", action="store_true", help="print the compiler's resource usage of the matching kernels")
     a = ap.parse_args()
-    asm = a.asm or compile_to_asm(a.source)
+    asm = a.asm or compile_to_asm(a.source, a.resources, a.kernel)
     res = analyse(asm, a.kernel, a.blocks, a.min)
     for name, r in res.items():
         print(name)
         print("  instructions %d, VALU %d, FP64 share of VALU %.1f %%" % (r["instructions"], r["valu"], 100 * r["fp64_share_of_valu"]))
+        print("  s_waitcnt vmcnt(0): %d" % r["vmcnt0_waits"])
         print("  classes:", r["classes"])
         print("  top VALU ops:", r["top_valu_ops"])
         for b in r.get("blocks", []):
-            print("   %-12s n=%5d valu=%5d fp64=%5d rdwr=%4d mov=%4d cmpsel=%4d int=%4d perm=%4d lds=%4d vmem=%3d wait=%3d salu=%4d" % (
+            print("   %-12s n=%5d valu=%5d fp64=%5d rdwr=%4d mov=%4d cmpsel=%4d int=%4d perm=%4d lds=%4d vmem=%3d wait=%3d salu=%4d vmcnt0=%d" % (
                 b["block"], b["n"], b["valu"], b["fp64"], b["rdwrlane"], b["mov"], b["cmp_sel"], b["int"], b["permute"], b["lds"],
-                b["vmem"], b["wait"], b["salu"]))
+                b["vmem"], b["wait"], b["salu"], b["vmcnt0"]))
     if a.json:
         json.dump(res, open(a.json, "w"), indent=1)
 
