@@ -217,6 +217,41 @@ class Context:
     def host_unregister(self, arr: np.ndarray = None):
         self._check(self.lib.pfm_host_unregister(self._h, C.c_void_p(arr.ctypes.data) if arr is not None else None), "pfm_host_unregister")
 
+    def values_to_host(self, value_ptrs: Sequence[int], host_arrays: Sequence[np.ndarray]):
+        """``pfm_values_to_host``: the device value blocks ``value_ptrs`` into the host arrays, synchronously."""
+        dp = (C.c_void_p * 4)(*[C.c_void_p(p) for p in list(value_ptrs) + [0] * (4 - len(value_ptrs))])
+        hp = (C.c_void_p * 4)(*[C.c_void_p(a.ctypes.data if a is not None and a.size else 0) for a in host_arrays])
+        self._check(self.lib.pfm_values_to_host(self._h, dp, hp), "pfm_values_to_host")
+
+    DELTA_STATS = ("bytes_moved", "bytes_total", "chunks_changed", "chunks", "slabs_direct", "slabs_packed")
+
+    def values_to_host_delta(self, value_ptrs: Sequence[int], host_arrays: Sequence[np.ndarray]) -> dict:
+        """``pfm_values_to_host_delta``: like ``values_to_host``, but only the chunks whose bits differ from what the last
+        call left in ``host_arrays`` cross the link.  Returns the call's statistics: ``DELTA_STATS``, ``chunks_changed_block``
+        (per block) and ``raw`` (the ten counters of the C ABI)."""
+        dp = (C.c_void_p * 4)(*[C.c_void_p(p) for p in list(value_ptrs) + [0] * (4 - len(value_ptrs))])
+        hp = (C.c_void_p * 4)(*[C.c_void_p(a.ctypes.data if a is not None and a.size else 0) for a in host_arrays])
+        st = (C.c_int64 * 10)()
+        self._check(self.lib.pfm_values_to_host_delta(self._h, dp, hp, st), "pfm_values_to_host_delta")
+        raw = [int(x) for x in st]
+        out = dict(zip(self.DELTA_STATS, raw[:6]))
+        out["chunks_changed_block"] = raw[6:10]
+        out["raw"] = raw
+        return out
+
+    def values_delta_reset(self):
+        """``pfm_values_delta_reset``: the host wrote (zeroed, reallocated) its value arrays; the next delta call ships all."""
+        self._check(self.lib.pfm_values_delta_reset(self._h), "pfm_values_delta_reset")
+
+    def values_delta_config(self, chunk_bytes: int = 0, slab_bytes: int = 0):
+        """tests and tuning: chunk and slab size of the delta transfer in bytes (0 = default); implies a reset."""
+        self._check(self.lib.pfm_values_delta_config(self._h, int(chunk_bytes), int(slab_bytes)), "pfm_values_delta_config")
+
+    def values_delta_info(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.pfm_values_delta_info(self._h, out), "pfm_values_delta_info")
+        return {"chunk_bytes": int(out[0]), "slab_bytes": int(out[1]), "device_bytes": int(out[2]), "valid": bool(out[3])}
+
     def assemble_host(self, sol, old, oldold, residual_only: bool, out=None):
         """``pfm_assemble``: synchronous, host numpy in / host numpy out (single rank).  ``out`` = (values, res_pde,
         res_tot): arrays of an earlier call to write into again (what a host with its own matrix storage does; with

@@ -2704,6 +2704,7 @@ extern "C"
         (void)hipStreamDestroy(c->copy_stream);
         (void)hipEventDestroy(c->ev_copy);
       }
+    delta_release(c); // (its device buffers were in allocs)
     for (double *p : c->d_stage_vec)
       if (p)
         (void)hipFree(p);
@@ -2866,6 +2867,7 @@ extern "C"
     if (!c || block < 0 || block >= c->n_blocks || (!rp64 && !rp32) || !colind)
       return PFM_ERR_BAD_ARG;
     (void)hipSetDevice(c->device);
+    c->delta.valid = false; // the values move to other slots: what the host holds is not what the shadow describes
     const int dim = c->v.dim;
     int ncr, ncc;
     if (c->v.layout == PFM_LAYOUT_INTERLEAVED)
@@ -4221,6 +4223,7 @@ extern "C"
     (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream)
       (void)hipStreamSynchronize(c->copy_stream);
+    delta_forget_host(c, p);
     for (auto &hp : c->host_pins)
       if (!p || hp.p == p)
         {
@@ -4439,3 +4442,18 @@ extern "C"
 
   int64_t pfm_ctx_device_bytes(const pfm_ctx *c) { return c ? c->device_bytes : 0; }
 }
+
+namespace pfm
+{
+  // d2h_user for a piece [h, h + bytes) of an array: page-locked if it lies inside a registered array
+  hipError_t d2h_user_piece(pfm_ctx *c, void *h, const void *d, size_t bytes, hipStream_t s)
+  {
+    if (bytes == 0)
+      return hipSuccess;
+    const char *lo = static_cast<const char *>(h);
+    for (const auto &hp : c->host_pins)
+      if (lo >= static_cast<const char *>(hp.p) && lo + bytes <= static_cast<const char *>(hp.p) + hp.bytes)
+        return hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s);
+    return d2h_user(c, h, d, bytes, s);
+  }
+} // namespace pfm

@@ -295,6 +295,26 @@ namespace pfm
       return static_cast<T *>(p);
     }
   };
+
+  // pfm_values_to_host_delta (pfm_delta.hip): what the library knows about the host's copy of the matrix values
+  struct DeltaState
+  {
+    bool valid = false;                          // shadow[b] holds what h_last[b] holds
+    int64_t chunk_bytes = 0, slab_bytes = 0;     // pfm_values_delta_config; 0 = the default
+    DevBuf shadow[4];                            // device copy of the host's values, per block
+    const void *h_last[4] = {nullptr, nullptr, nullptr, nullptr};
+    // per staging slot (two slabs in flight): chunk flags, [count, payload offset], index list + packed chunks
+    DevBuf flags[2], count[2], pack[2];
+    void *h_pack[2] = {nullptr, nullptr};        // page-locked images of pack[]
+    unsigned long long *h_count = nullptr;       // page-locked, [2][2]
+    size_t h_pack_bytes = 0;
+    hipEvent_t ev_cmp[2] = {nullptr, nullptr}, ev_dma[2] = {nullptr, nullptr};
+  };
+  // the transfer path of pfm_values_to_host for one piece of a caller-owned array (pfm_host.cpp: d2h_user)
+  hipError_t d2h_user_piece(pfm_ctx *c, void *h, const void *d, size_t bytes, hipStream_t s);
+  // pfm_host_unregister of p (nullptr: all), pfm_ctx_destroy
+  void delta_forget_host(pfm_ctx *c, const void *p);
+  void delta_release(pfm_ctx *c);
 } // namespace pfm
 
 struct pfm_ctx
@@ -350,6 +370,7 @@ struct pfm_ctx
   std::vector<HostPin> host_pins;
   hipStream_t copy_stream = nullptr; // second device -> host stream of pfm_values_to_host
   hipEvent_t ev_copy = nullptr;
+  pfm::DeltaState delta; // pfm_values_to_host_delta
   std::vector<pfm::HaloPeer> peers;
   int32_t *d_send_all = nullptr, *d_recv_all = nullptr; // concatenated halo lists and their per-peer offsets
   long long *d_send_ptr = nullptr, *d_recv_ptr = nullptr;

@@ -120,9 +120,19 @@ namespace pfm_glue_detail
     //   residual_to_host:  false = a residual-only assemble() leaves both residual vectors on the device and the caller asks
     //                      for what the line search reads, residual_l2_norm() (cracks.cc:2946-2949): 24 bytes instead of
     //                      2 x 8 n_dofs per call.
+    //   delta_values:      assemble() hands the matrix values over with pfm_values_to_host_delta: only the chunks whose bits
+    //                      differ from what the last assemble() left in Epetra's arrays cross the link (within a time step
+    //                      the displacement rows do not change without the stress split: about a third of the bytes
+    //                      travels).  A host that switches this on must NOT write the matrix values itself between two
+    //                      assemblies -- in particular not keep the `system_pde_matrix = 0` of cracks.cc:2133 in front of
+    //                      the call; if it does write them it calls values_written_by_host() first.  The library's
+    //                      copy of the host's values goes with the context (release(), before_setup_system()).  If the
+    //                      device cannot hold that copy the values travel through pfm_values_to_host as before.
     bool pin_host_matrix = false;
+    bool delta_values = false;
     bool residual_to_host = true;
     bool holds_host_pins = false;
+    int64_t delta_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // of the last assemble() with delta_values (pfm_values_to_host_delta)
 
     ~PfmGlue()
     {
@@ -134,6 +144,13 @@ namespace pfm_glue_detail
     // top of setup_system() (cracks.cc:1579), BEFORE system_pde_matrix.reinit / clear: drops the context and with it every
     // page lock on arrays the matrix is about to free
     void before_setup_system() { release(); }
+
+    // delta_values: the host has written the matrix values itself; the next assemble() ships all of them
+    void values_written_by_host()
+    {
+      if (ctx)
+        (void)pfm_values_delta_reset(ctx);
+    }
 
     void release()
     {
@@ -679,7 +696,12 @@ namespace pfm_glue_detail
                 int *rowptr = nullptr, *colind = nullptr;
                 P.system_pde_matrix.block(r, c).trilinos_matrix().ExtractCrsDataPointers(rowptr, colind, h_val[blocked ? 2 * r + c : 0]);
               }
-          PFM_CALL(ctx, pfm_values_to_host(ctx, d_val, h_val));
+          int rcv = PFM_ERR_NOMEM;
+          if (delta_values)
+            rcv = pfm_values_to_host_delta(ctx, d_val, h_val, delta_stats);
+          if (rcv == PFM_ERR_NOMEM) // switch off, or no room for the shadow (the host arrays are untouched then)
+            rcv = pfm_values_to_host(ctx, d_val, h_val);
+          AssertThrow(rcv == PFM_OK, ExcMessage(ctx ? pfm_last_error(ctx) : "pfm_values_to_host"));
         }
       // the AMG set-up of cracks.cc:2477-2497 follows in the caller, unchanged
     }

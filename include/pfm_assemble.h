@@ -238,6 +238,44 @@ int pfm_assemble(pfm_ctx *ctx, const double *sol, const double *old, const doubl
                  int residual_only, double *const *values, double *residual_pde,
                  double *residual_total);
 
+/* Delta transfer of the matrix values ("Delta transfer"): within a time step most of the Jacobian does not
+ * change between Newton iterations (without the stress split the displacement rows depend on the lagged phase field
+ * only), and the library finds out itself which values did.
+ *
+ * Like pfm_values_to_host, but only chunks of d_values[b] whose BITS differ from what this function last left in
+ * h_values[b] are transferred.  On return h_values[b][i] has the bit pattern of d_values[b][i] for every i, provided the
+ * host has not written h_values[b] since the previous call on this context (the assumption pfm_values_to_host already
+ * makes for a registered (u,phi) array).  Synchronous; ordered behind earlier work on the context's stream.
+ *   comparison     on the 64-bit patterns, never a floating-point compare: -0.0 and 0.0 differ, two NaNs with different
+ *                  payloads differ, identical NaNs are equal.
+ *   state          the library keeps a device copy (the "shadow") of what the host holds for each block: exact, not a
+ *                  hash.  Allocated at the first call, counted in pfm_ctx_device_bytes, freed by pfm_ctx_destroy.  If it
+ *                  (or the staging buffers) cannot be allocated the call returns PFM_ERR_NOMEM with the host arrays
+ *                  untouched; the caller falls back to pfm_values_to_host.
+ *   host pointers  h_values[b] is remembered per block; another pointer than last time ships all of that block.
+ *   invalidation   pfm_pattern_bind*, pfm_values_delta_reset, pfm_values_delta_config, pfm_host_unregister of a
+ *                  remembered array (or of all) and any error inside a delta call mark the state invalid: the next call
+ *                  ships everything.
+ *   sizes          1 block or 4, blocks with nnz == 0, blocks shorter than a chunk, a short last chunk, host arrays that
+ *                  are only 8-byte aligned, registered or pageable.  Per rank; nothing collective.
+ *   (u,phi)        in the 4-block layout a REGISTERED h_values[1] is cleared on the host instead of shipped when all of it
+ *                  is due (once per registration, and again after pfm_values_delta_reset); it is compared like the other
+ *                  blocks all the same, so a device block that is not all +0.0 still arrives bit for bit.
+ * Each block is worked through in slabs: compare (one wave per chunk; a chunk that differs is copied to the shadow),
+ * ordered scan of the flags, then the slab goes directly (d_values -> h_values, when most of its chunks changed) or packed
+ * (changed chunks + their index list -> page-locked staging of the context -> memcpy per chunk by host threads).
+ * stats (may be NULL): [0] bytes moved over the link (payload + chunk lists; not the 8-byte count word per slab),
+ * [1] bytes of all blocks, [2] changed chunks, [3] chunks, [4] slabs shipped directly, [5] slabs shipped packed,
+ * [6 + b] changed chunks of block b (b < 4). */
+int pfm_values_to_host_delta(pfm_ctx *ctx, double *const *d_values, double *const *h_values, int64_t stats[10]);
+/* forget what the host holds: the next delta call ships everything (the host zeroed or reallocated its arrays) */
+int pfm_values_delta_reset(pfm_ctx *ctx);
+/* tests and tuning, like pfm_ctx_force_zchunk: chunk_bytes a power of two >= 64, slab_bytes a multiple of chunk_bytes,
+ * 0 = default; implies a reset.  Anything else PFM_ERR_BAD_ARG. */
+int pfm_values_delta_config(pfm_ctx *ctx, int64_t chunk_bytes, int64_t slab_bytes);
+/* out[0] chunk bytes, [1] slab bytes, [2] device bytes held for the feature, [3] 1 if the next call can skip anything */
+int pfm_values_delta_info(const pfm_ctx *ctx, int64_t out[4]);
+
 /* -- measurement ---------------------------------------------------------------------- */
 /* When enabled, every pfm_assemble_device() brackets its kernel group (output zeroing where
  * the kernel family needs it, residual and Jacobian kernels; not the state scatter, which is
