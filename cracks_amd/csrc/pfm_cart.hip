@@ -25,6 +25,7 @@
 // Arithmetic is the reference's (cracks.cc:2248-2432) re-associated; parity with the CPU
 // oracle is at round-off level (tests/test_gpu_parity.py, tolerance 1e-12).
 #include "pfm_internal.h"
+#include "pfm_cart_plan.h"
 #include "pfm_poly.h"
 #include "pfm_dma.h"
 
@@ -299,7 +300,7 @@ namespace pfm
       });
     }
 
-    constexpr int R2N = 62; // owned nodes per wave
+    // (R2N = 62 owned nodes per wave: pfm_cart_plan.h)
     template <bool LIN>
     __global__ __launch_bounds__(64) void k_cart_residual2m(DevView v, CartView cv, Scal S, double *__restrict__ res_pde,
                                                             double *__restrict__ res_tot, int write_total, int zc)
@@ -552,8 +553,7 @@ namespace pfm
     // adds its 4 cell columns in a fixed order and writes its rows exactly once.  Nodal values live in a
     // two-plane LDS ring: every plane is read from HBM/L2 once per tile.
     // =====================================================================================
-    constexpr int RTX = 16, RTY = 16;           // cell columns per workgroup = threads
-    constexpr int RNX = RTX - 1, RNY = RTY - 1; // owned nodes per tile plane
+    constexpr int RTX = RNX + 1, RTY = RNY + 1; // cell columns per workgroup = threads (RNX x RNY owned nodes per tile plane: pfm_cart_plan.h)
     constexpr int RHX = RTX + 1, RHY = RTY + 1; // nodal halo per plane
     constexpr int RPL = RHX * RHY + 3;          // padded plane stride (292)
 
@@ -1634,187 +1634,64 @@ namespace pfm
     }
   } // namespace
 
-  int launch_cart_matrix(const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
-                         hipStream_t s, void *d_scal, double *res_pde, int phase, hipStream_t s_phi);
-
-  int choose_zchunk(long long tiles, int planes, int zc_min, int zc_max, int per_cu)
+  int cart_n_cu()
   {
-    static int n_cu = 0;
-    if (!n_cu)
-      {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-      }
-    // time model: workgroups are dispatched as slots free up, so the launch takes about (wgs / slots + 1/2) workgroup
-    // durations, and a workgroup's duration is proportional to its zc + 1 cell layers
-    const double slots = (double)per_cu * n_cu;
-    const int lo = std::max(1, std::min(zc_min, planes)), hi = std::min(zc_max, planes);
-    double tmin = 1e300;
-    for (int zc = lo; zc <= hi; ++zc)
-      tmin = std::min(tmin, ((double)tiles * ((planes + zc - 1) / zc) / slots + 0.5) * (zc + 1));
-    int best = lo;
-    for (int zc = lo; zc <= hi; ++zc) // the longest chunk within 1 % of the optimum: fewest redundant layers
-      if (((double)tiles * ((planes + zc - 1) / zc) / slots + 0.5) * (zc + 1) <= 1.01 * tmin)
-        best = zc;
-    return best;
+    static const int n_cu = [] {
+      int dev = 0;
+      hipDeviceProp_t prop;
+      return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+    }();
+    return n_cu;
   }
 
-  namespace
+  int cart_zchunk(CartView cv, int kernel)
   {
-    int env_planes(const char *name)
-    {
-      const char *s = getenv(name);
-      return s ? atoi(s) : 0;
-    }
-  } // namespace
-
-  int zchunk_of(const CartView &cv, int kernel, long long tiles, int planes)
-  {
-    // the tuning variables, once per process: nothing is read from the environment per launch
-    static const int env[PFM_ZC_KERNELS] = {env_planes("PFM_UU_ZC"), env_planes("PFM_PHI_ZC"), env_planes("PFM_RES_ZC"),
-                                            env_planes("PFM_RES2_ZC")};
-    // the model's range and resident workgroups per CU of each kernel (k_cart_residual2m: one wave per workgroup)
-    static constexpr int zmin[PFM_ZC_KERNELS] = {8, 6, 4, 4}, zmax[PFM_ZC_KERNELS] = {48, 48, 24, 64}, per_cu[PFM_ZC_KERNELS] = {2, 2, 2, 8};
-    const int forced = cv.zc_force[kernel] > 0 ? cv.zc_force[kernel] : env[kernel];
-    if (forced > 0)
-      return std::max(1, std::min(forced, planes));
-    return choose_zchunk(tiles, planes, zmin[kernel], zmax[kernel], per_cu[kernel]);
+    cv.tile_sel = 0;
+    return cart_tile_grid(cv, kernel, cart_n_cu()).zc;
   }
 
-  int cart_res3_zchunk(const CartView &cv)
+  // Carries out pl = plan_cart(v, cv, p, ...) on the context's stream s; s_side: the stream the caller has forked off it (for the
+  // phase-field kernel of the pair, or under PFM_SIDE_STREAM for the residual kernel: both only read the node state), else s.
+  int launch_assemble_cart(const CartPlan &pl, const DevView &v, const CartView &cv_in, const pfm_params &p, double *const *d_values,
+                           double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock)
   {
-    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
-    const int ntx = (OWX + RNX - 1) / RNX, nty = (OWY + RNY - 1) / RNY;
-    return zchunk_of(cv, PFM_ZC_RES3, (long long)ntx * nty, OWZ);
-  }
-
-  int cart_res2_zchunk(const CartView &cv) // chunks of node rows, one wave per R2N nodes of a row
-  {
-    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1;
-    return zchunk_of(cv, PFM_ZC_RES2, (OWX + R2N - 1) / R2N, OWY);
-  }
-
-  // the conditions of `rows_residual` in launch_assemble_cart + what the pair needs: the default (u,u) kernel
-  bool cart_jacobian_pair(const DevView &v, const CartView &cv, const pfm_params &p, int residual_only, int phase)
-  {
-    if (v.dim != 3 || residual_only || phase != 0 || cv.cell_lam)
-      return false;
-    static const bool other_mode = getenv("PFM_RES_KERNEL") || getenv("PFM_UU_CLK") || getenv("PFM_PHI_CLK");
-    if ((p.decompose_stress_matrix > 0 && p.timestep_number > 0) || other_mode)
-      return false;
-    const Scal S = make_scal(p, cv, v.dim);
-    return !S.monolithic && S.gamma_fac == 0.0 && S.kappa < 0.5;
-  }
-
-  // phase: 0 = the whole assembly; 1 / 2 = the two halves of pfm_assemble_overlapped: 1 launches what reads no ghost
-  // node (the "interior" tiles of the first kernel of the sequence), 2 the rest -- the ghost import lands in between
-  int launch_assemble_cart(const DevView &v, const CartView &cv_in, const pfm_params &p, int residual_only,
-                           double *const *d_values, double *res_pde, double *res_tot, hipStream_t s,
-                           hipStream_t s_residual, void *d_scal, int phase)
-  {
-    // the residual and the Jacobian only read the node state: on different streams they overlap
-    // (s_residual == s: plain stream order)
-    hipStream_t s_jac = s;
-    s = s_residual;
-    int rc = ensure_tab();
-    if (rc)
-      return rc;
-    const bool split = p.decompose_stress_matrix > 0 && p.timestep_number > 0; // cracks.cc:2294
-    if (split)
+    using ResidualKernel = void (*)(DevView, CartView, Scal, double *, double *, int, int);
+    static const ResidualKernel residual_kernel[5][2] = {{nullptr, nullptr}, // by CartResidual and its flag: every instantiation there is
+                                                         {k_cart_residual3x<false>, k_cart_residual3x<true>},
+                                                         {k_cart_residual3d<false>, k_cart_residual3d<true>},
+                                                         {k_cart_residual3<false>, k_cart_residual3<true>},
+                                                         {k_cart_residual2m<false>, k_cart_residual2m<true>}};
+    if (const int rc0 = ensure_tab())
+      return rc0;
+    if (!pl.supported)
       return PFM_ERR_UNSUPPORTED; // the host routes split runs to the general path
+    if (pl.pair && !cv_in.patch_count)
+      return PFM_ERR_BAD_ARG; // concurrent kernels need the deferred patch list
     CartView cv = cv_in;
-    cv.tile_sel = phase; // 0: all tiles, 1: interior, 2: boundary -- of the FIRST kernel of the sequence only (below)
-    if (v.dim == 2 && !residual_only)
-      return launch_cart2d(v, cv, p, residual_only, d_values, res_pde, res_tot, s_jac, s); // 2-D Jacobian + residual (s != s_jac: forked by the caller)
-    const Scal S = make_scal(p, cv, v.dim);
-    // Full 3-D assembly, staggered scheme (no q-point clamps of the phase fields, no penalty term): the unsplit law makes
-    // every residual row an exact function of its own matrix row (R_u = pressure part - K_uu u, R_phi = G_c/eps mass - K_phiphi
-    // phi), so the Jacobian kernels write the residual as well and the residual kernel is not launched (2.1 of 15.8 ms at
-    // 216^3).  PFM_RES_KERNEL=1 keeps the quadrature kernel (A/B runs; tests compare both against the oracle).
-    static const bool res_kernel_forced = getenv("PFM_RES_KERNEL") != nullptr;
-    const bool rows_residual = v.dim == 3 && !residual_only && !S.monolithic && S.gamma_fac == 0.0 && S.kappa < 0.5 && !res_kernel_forced &&
-                               !cv.cell_lam; // (the heterogeneous (u,u) variant has no registers left for it)
-    if (rows_residual) // s_residual != s_jac: the caller forked it off for the phase-field kernel (cart_jacobian_pair)
-      return launch_cart_matrix(v, cv, p, d_values, s_jac, d_scal, res_pde, phase, (phase == 0 && cv.patch_count) ? s : s_jac);
-    const long long OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = v.dim == 3 ? cv.o1[2] - cv.o0[2] + 1 : 1;
-    if (v.dim == 2)
+    cv.tile_sel = pl.phase; // of the first kernel of the sequence alone
+    if (pl.cells2())
+      return launch_cart2d(pl, v, cv, p, d_values, res_pde, res_tot, s);
+    if (pl.residual)
       {
-        const int ntx = (int)((OWX + R2N - 1) / R2N);
-        const int zc = cart_res2_zchunk(cv);
-        const unsigned nw = (unsigned)(ntx * ((OWY + zc - 1) / zc));
-        if (nw == 0)
-          ;
-        else if (!S.monolithic && S.gamma_fac == 0.0)
-          hipLaunchKernelGGL(k_cart_residual2m<true>, dim3(nw), dim3(64), 0, s, v, cv, S, res_pde, res_tot, residual_only, zc);
-        else
-          hipLaunchKernelGGL(k_cart_residual2m<false>, dim3(nw), dim3(64), 0, s, v, cv, S, res_pde, res_tot, residual_only, zc);
+        const bool flat = pl.residual == PFM_RES_2M; // a wave per R2N nodes of a row and chunk of rows; 3-D: chunks of z-planes
+        const TileGrid &g = pl.grid[flat ? PFM_ZC_RES2 : PFM_ZC_RES3];
+        const ResidualKernel kernel = residual_kernel[pl.residual][pl.residual_flag()];
+        if (g.n_tiles != 0)
+          hipLaunchKernelGGL(kernel, dim3(flat ? g.n_tiles : xcd_grid(g.n_tiles)), dim3(flat ? 64 : RTX * RTY), 0, s_side, v, cv,
+                             make_scal(p, cv, v.dim), res_pde, res_tot, (int)pl.residual_only, g.zc);
+        if (hipGetLastError() != hipSuccess)
+          return PFM_ERR_HIP;
       }
-    else
-      {
-        const int ntx = (int)((OWX + RNX - 1) / RNX), nty = (int)((OWY + RNY - 1) / RNY);
-        // chunks of z-planes: fill the dispatch rounds of the chip (2 workgroups per CU) at few redundant layers
-        const int zc = cart_res3_zchunk(cv);
-        const int nch = (int)((OWZ + zc - 1) / zc);
-        const bool listed = cv.tile_sel == 2 && cv.bnd_res3 != nullptr && cv.zc_res3 == zc;
-        const unsigned nt = listed ? (unsigned)cv.n_bnd_res3 : (unsigned)(ntx * nty * nch);
-        // the whole lexicographic box of a single rank, every byte offset of a node below 4 GiB: planes by transfer
-        // (read per launch: the tests compare the three kernels in one process)
-        const bool no_transfers = getenv("PFM_RES_NO_TRANSFERS") != nullptr;   // k_cart_residual3 <true>
-        const bool wide_off = getenv("PFM_RES_NO_WIDE_TRANSFERS") != nullptr;  // k_cart_residual3d instead of 3x
-        const bool whole_lex = cv.owned_lex && cv.o0[0] == 0 && cv.o0[1] == 0 && cv.o0[2] == 0 && cv.o1[0] == cv.NX - 1 &&
-                               cv.o1[1] == cv.NY - 1 && cv.o1[2] == cv.NZ - 1 && cv.tile_sel == 0 && !cv.row_of_box &&
-                               (long long)v.n_nodes == (long long)cv.NX * cv.NY * cv.NZ && v.n_owned == v.n_nodes &&
-                               (long long)v.n_nodes * 32 < (1LL << 32) && !no_transfers;
-        if (nt == 0)
-          ;
-        else if (!S.monolithic && S.gamma_fac == 0.0 && whole_lex && v.fused_solution && v.layout == PFM_LAYOUT_BLOCKED && v.n_nodes >= 64 &&
-                 !wide_off)
-          {
-            if (cv.cell_lam)
-              hipLaunchKernelGGL(k_cart_residual3x<true>, dim3(xcd_grid(nt)), dim3(RTX * RTY), 0, s, v, cv, S, res_pde, res_tot, residual_only, zc);
-            else
-              hipLaunchKernelGGL(k_cart_residual3x<false>, dim3(xcd_grid(nt)), dim3(RTX * RTY), 0, s, v, cv, S, res_pde, res_tot, residual_only, zc);
-          }
-        else if (!S.monolithic && S.gamma_fac == 0.0 && whole_lex)
-          {
-            if (cv.cell_lam)
-              hipLaunchKernelGGL(k_cart_residual3d<true>, dim3(xcd_grid(nt)), dim3(RTX * RTY), 0, s, v, cv, S, res_pde, res_tot, residual_only, zc);
-            else
-              hipLaunchKernelGGL(k_cart_residual3d<false>, dim3(xcd_grid(nt)), dim3(RTX * RTY), 0, s, v, cv, S, res_pde, res_tot, residual_only, zc);
-          }
-        else if (!S.monolithic && S.gamma_fac == 0.0)
-          hipLaunchKernelGGL(k_cart_residual3<true>, dim3(xcd_grid(nt)), dim3(RTX * RTY), 0, s, v, cv, S, res_pde, res_tot, residual_only, zc);
-        else
-          hipLaunchKernelGGL(k_cart_residual3<false>, dim3(xcd_grid(nt)), dim3(RTX * RTY), 0, s, v, cv, S, res_pde, res_tot, residual_only, zc);
-      }
-    if (hipGetLastError() != hipSuccess)
-      return PFM_ERR_HIP;
-    // the residual kernel was the first of the sequence (and the one split into interior / boundary tiles): the Jacobian
-    // kernels follow it completely, in the second phase of an overlapped assembly
-    if (!residual_only && phase != 1)
-      return launch_cart_matrix(v, cv_in, p, d_values, s_jac, d_scal, nullptr, 0, s_jac);
-    return PFM_OK;
-  }
-} // namespace pfm
-namespace pfm
-{
-  void cart_res3_boundary_tiles(const CartView &cv, std::vector<int32_t> &out, int &zc)
-  {
-    out.clear();
-    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
-    const int ntx = (OWX + RNX - 1) / RNX, nty = (OWY + RNY - 1) / RNY;
-    zc = cart_res3_zchunk(cv); // as launch_assemble_cart
-    const int nch = (OWZ + zc - 1) / zc;
-    for (int ch = 0; ch < nch; ++ch)
-      for (int tiy = 0; tiy < nty; ++tiy)
-        for (int tix = 0; tix < ntx; ++tix)
-          {
-            const int i0 = cv.o0[0] + tix * RNX, j0 = cv.o0[1] + tiy * RNY, kA = cv.o0[2] + ch * zc;
-            const int kB = std::min(kA + zc, cv.o1[2] + 1);
-            if (cart_range_has_ghost(cv, 0, i0 - 1, i0 + RNX) || cart_range_has_ghost(cv, 1, j0 - 1, j0 + RNY) ||
-                cart_range_has_ghost(cv, 2, kA - 1, kB))
-              out.push_back(tix + ntx * (tiy + nty * ch));
-          }
+    // Jacobian of a 3-D box: (u,u) rows first; k_cart_phi4 patches constrained (u,u) diagonals afterwards (same stream, or
+    // deferred: the pair) and clears the structurally zero (u,phi) block (cracks.cc:2333-2337) along with its (phi,u) stores
+    double *const res_rows = pl.rows_residual ? res_pde : nullptr;
+    cv.tile_sel = pl.tile_sel(PFM_ZC_UU3);
+    int rc = PFM_OK;
+    if (pl.uu3())
+      rc = launch_cart_uu3(pl, v, cv, p, d_values[0], s, res_rows, clock);
+    cv.tile_sel = 0;
+    if (rc == PFM_OK && pl.phi4())
+      rc = launch_cart_phi4(pl, v, cv, d_values, pl.pair ? s_side : s, d_scal, res_rows, clock);
+    return rc;
   }
 } // namespace pfm

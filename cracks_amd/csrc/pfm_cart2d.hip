@@ -45,7 +45,7 @@ namespace pfm
     // operations per evaluation).  Rows c = 0, 1 are completed and stored first, then the phase-field row: the moments
     // and the accumulators of one group fit the registers of two waves per SIMD.  No LDS allocation, no barrier.
     // =====================================================================================
-    constexpr int B2 = 8, O2 = B2 - 1; // cells per block side, owned nodes per block side
+    constexpr int B2 = O2 + 1; // cells per block side (O2 owned nodes per block side: pfm_cart_plan.h)
 
     struct Cst2 // per-launch constants of the sum-factorised kernel
     {
@@ -660,12 +660,16 @@ namespace pfm
 
   // 2-D cartesian boxes: Jacobian + residual without the stress split (the plain 2-D residual has its own kernel in
   // pfm_cart.hip)
-  int launch_cart2d(const DevView &v, const CartView &cv, const pfm_params &p, int residual_only, double *const *d_values,
-                    double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_phi)
+  int launch_cart2d(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
+                    double *res_pde, double *res_tot, hipStream_t s)
   {
-    int rc = ensure_g1();
-    if (rc)
+    if (!pl.cells2())
+      return PFM_ERR_UNSUPPORTED; // stress-split runs take the general family with the cartesian overlay (pfm_kernels.hip, PATCH; kernel path 3), residual-only assemblies k_cart_residual2m (pfm_cart.hip)
+    if (const int rc = ensure_g1())
       return rc;
+    const TileGrid &g = pl.grid[PFM_TILES_CELLS2];
+    if (g.n_tiles == 0)
+      return PFM_OK;
     Prm2 P{};
     P.lam = p.lambda;
     P.mu = p.mu;
@@ -686,17 +690,9 @@ namespace pfm
     P.monolithic = p.outer_solver == PFM_SOLVER_SIMPLE_MONOLITHIC;
     P.use_old = p.use_old_timestep_pf;
     const int total_via_update = p.outer_solver != PFM_SOLVER_ACTIVE_SET;
-    const bool split = p.decompose_stress_matrix > 0 && p.timestep_number > 0; // cracks.cc:2294
     Vals2 vals{};
-    if (!residual_only)
-      for (int b = 0; b < (v.layout == PFM_LAYOUT_BLOCKED ? 4 : 1); ++b)
-        vals.b[b] = d_values[b];
-    if (split)
-      return PFM_ERR_UNSUPPORTED; // stress-split runs are not a moment of a q-point field: they take the general family with the cartesian overlay (pfm_kernels.hip, PATCH; kernel path 3)
-    if (residual_only)
-      return PFM_ERR_UNSUPPORTED; // residual-only 2-D assemblies: k_cart_residual2m (pfm_cart.hip)
-    if (cv.o1[0] < cv.o0[0] || cv.o1[1] < cv.o0[1])
-      return PFM_OK;
+    for (int b = 0; b < (pl.interleaved ? 1 : 4); ++b)
+      vals.b[b] = d_values[b];
     Cst2 K{};
     K.omk = 1.0 - P.kappa;
     K.omk2 = 2.0 * (1.0 - P.kappa);
@@ -706,17 +702,14 @@ namespace pfm
     K.gce = P.Gc * P.eps;
     K.gc_eps_vol_x = P.Gc * P.eps * P.vol * P.ihx * P.ihx;
     K.gc_eps_vol_y = P.Gc * P.eps * P.vol * P.ihy * P.ihy;
-    const long long ntx = (cv.o1[0] - cv.o0[0] + 1 + O2 - 1) / O2, nty = (cv.o1[1] - cv.o0[1] + 1 + O2 - 1) / O2;
-    const bool one_launch = getenv("PFM_CART2D_ONE_LAUNCH") != nullptr; // A/B runs, tests
-    if (one_launch)
-      hipLaunchKernelGGL(k_cart2d_cells<2>, dim3(xcd_grid((unsigned)(ntx * nty))), dim3(64), 0, s, v, cv, P, K, vals, res_pde, res_tot, residual_only,
-                         total_via_update, (int)nty);
+    // both launches on one stream: the second (phase-field rows) reads the mean |diagonal| the first leaves in CartView::cell_avg
+    const dim3 grid(xcd_grid(g.n_tiles)), block(64);
+    if (pl.one_launch)
+      hipLaunchKernelGGL(k_cart2d_cells<2>, grid, block, 0, s, v, cv, P, K, vals, res_pde, res_tot, 0 /* residual_only */, total_via_update, g.nty);
     else
       {
-        hipLaunchKernelGGL(k_cart2d_cells<0>, dim3(xcd_grid((unsigned)(ntx * nty))), dim3(64), 0, s, v, cv, P, K, vals, res_pde, res_tot, residual_only,
-                           total_via_update, (int)nty);
-        hipLaunchKernelGGL(k_cart2d_cells<1>, dim3(xcd_grid((unsigned)(ntx * nty))), dim3(64), 0, s_phi, v, cv, P, K, vals, res_pde, res_tot, residual_only,
-                           total_via_update, (int)nty);
+        hipLaunchKernelGGL(k_cart2d_cells<0>, grid, block, 0, s, v, cv, P, K, vals, res_pde, res_tot, 0 /* residual_only */, total_via_update, g.nty);
+        hipLaunchKernelGGL(k_cart2d_cells<1>, grid, block, 0, s, v, cv, P, K, vals, res_pde, res_tot, 0 /* residual_only */, total_via_update, g.nty);
       }
     return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
   }

@@ -3,6 +3,7 @@
 // an anonymous namespace: each translation unit owns its copy of the __constant__ table.
 #pragma once
 #include "pfm_internal.h"
+#include "pfm_cart_plan.h"
 
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -88,8 +89,8 @@ namespace pfm
         }
     }
 
-    // tiles of pfm_cart_uu3.hip: 8 x 4 nodes, 512 threads
-    constexpr int T3X = 8, T3Y = 4, NT3 = 512;
+    // tiles of pfm_cart_uu3.hip: T3X x T3Y = 8 x 4 nodes (pfm_cart_plan.h), 512 threads
+    constexpr int NT3 = 512;
     constexpr int H3X = T3X + 2, H3Y = T3Y + 2, NH3 = H3X * H3Y * 3; // nodal halo 10 x 6 x 3
     constexpr int C3X = T3X + 1, C3Y = T3Y + 1, CL3 = C3X * C3Y;     // 45 cells per layer
     constexpr int CS3 = 2 * CL3;                                     // 90 cell slots

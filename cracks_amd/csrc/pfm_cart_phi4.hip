@@ -42,7 +42,7 @@ namespace pfm
 {
   namespace
   {
-    constexpr int PT = 8, PN = PT - 1, PH = PT + 1; // cells, owned nodes, halo nodes per tile edge
+    constexpr int PT = PN + 1, PH = PT + 1;        // cells, (owned nodes: PN, pfm_cart_plan.h,) halo nodes per tile edge
     constexpr int NPN = PN * PN, NPH = PH * PH;     // 49 owned nodes, 81 halo nodes per plane
     constexpr int NT4 = 4 * PT * PT;                // 4 roles x 64 cells
     constexpr int SLAB_PU = NPN * 27, SLAB_PP = NPN * 9;
@@ -1733,132 +1733,69 @@ namespace pfm
     return hipMemcpyAsync(d_scal, &Sh, sizeof(MatScal), hipMemcpyHostToDevice, s) == hipSuccess ? PFM_OK : PFM_ERR_HIP;
   }
 
-  int cart_phi4_zchunk(const CartView &cv)
+  namespace
   {
-    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
-    const int ntx = (OWX + PN - 1) / PN, nty = (OWY + PN - 1) / PN;
-    return zchunk_of(cv, PFM_ZC_PHI4, (long long)ntx * nty, OWZ);
-  }
+    // k_cart_phi4 by the plan's flags, every instantiation there is.  Per layout: plain, with the phase-field rows of the
+    // residual, the general form (OLDF; never with the residual rows), and plain / OLDF for heterogeneous material (the
+    // residual kernel runs); clocked (1 per phase, 2 per role): blocked, homogeneous, !OLDF.
+    using PhiKernel = void (*)(DevView, CartView, const MatScal *, double *, double *, double *, double *, int, unsigned long long *, double *);
+    PhiKernel phi4_kernel(const CartPlan &pl)
+    {
+      static const PhiKernel plain[2][5] = {{k_cart_phi4<3, 0, false, false, false>, k_cart_phi4<3, 0, false, true, false>, k_cart_phi4<3, 0, false, false, true>,
+                                             k_cart_phi4<3, 0, true, false, false>, k_cart_phi4<3, 0, true, false, true>},
+                                            {k_cart_phi4<4, 0, false, false, false>, k_cart_phi4<4, 0, false, true, false>, k_cart_phi4<4, 0, false, false, true>,
+                                             k_cart_phi4<4, 0, true, false, false>, k_cart_phi4<4, 0, true, false, true>}};
+      static const PhiKernel clocked[2][2] = {{k_cart_phi4<3, 1>, k_cart_phi4<3, 1, false, true>}, {k_cart_phi4<3, 2>, k_cart_phi4<3, 2, false, true>}};
+      if (pl.phi4_clock)
+        return clocked[pl.phi4_clock - 1][pl.rows_residual];
+      return plain[pl.interleaved][pl.het ? 3 + pl.oldf() : pl.oldf() ? 2 : pl.rows_residual];
+    }
 
-  int launch_cart_phi4(const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values, hipStream_t s,
-                       const void *d_scal, double *res_pde)
-  {
-    const MatScal *S = static_cast<const MatScal *>(d_scal);
-    if (v.dim != 3)
-      return PFM_ERR_UNSUPPORTED;
-    int rc = ensure_g1();
-    if (rc)
-      return rc;
-    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
-    const int ntx = (OWX + PN - 1) / PN, nty = (OWY + PN - 1) / PN;
-    // z-chunks: one extra cell layer per chunk is recomputed; keep that below ~4 % while filling the chip
-    // (round 6: chunks of up to 48 planes as in k_cart_uu3 -- at 216^3 the model picks 31 = 217 / 7, seven equal chunks per
-    // column instead of ten of 22 with a short last one: 10.7 -> 10.4 ms per assembly, profiles/r06/zc_scan.txt)
-    const int zc_abs = cart_phi4_zchunk(cv);
-    const int nch = (OWZ + zc_abs - 1) / zc_abs;
-    static const bool no_prio = getenv("PFM_NO_PRIO") != nullptr; // A/B runs only
-    const int zc = no_prio ? -zc_abs : zc_abs;
-    const unsigned nb = (unsigned)(ntx * nty * nch);
-    const bool il = v.layout == PFM_LAYOUT_INTERLEAVED, het = cv.cell_lam != nullptr, res = res_pde != nullptr;
-    const dim3 grid(xcd_grid(nb)), block(NT4);
-  // the general form (q-point loops, old phase fields in the nodal ring) only where the scheme needs it: clamped phase field
-  // (monolithic) or penalisation term (same rules as make_mat_scal)
-  const MatScal Sh = make_mat_scal(p, cv);
-  const bool oldf = Sh.gamma_fac != 0.0 || Sh.monolithic;
-#define PFM_PHI4_(NC, HETV, RESV, OLDV)                                                                                           \
-  hipLaunchKernelGGL((k_cart_phi4<NC, 0, HETV, RESV, OLDV>), grid, block, 0, s, v, cv, S, (NC == 3 ? d_values[2] : nullptr),      \
-                     (NC == 3 ? d_values[3] : nullptr), d_values[0], (NC == 3 ? d_values[1] : nullptr), zc, nullptr, res_pde)
-#define PFM_PHI4(NC, HETV, RESV)                                                                                                  \
-  do                                                                                                                              \
-    {                                                                                                                             \
-      if (oldf && !(RESV))                                                                                                        \
-        PFM_PHI4_(NC, HETV, false, true);                                                                                         \
-      else                                                                                                                        \
-        PFM_PHI4_(NC, HETV, RESV, false);                                                                                         \
-    }                                                                                                                             \
-  while (0)
-    if (il)
-      {
-        if (het)
-          PFM_PHI4(4, true, false); // heterogeneous material: the residual kernel runs
-        else
-          {
-            if (res)
-              PFM_PHI4(4, false, true);
-            else
-              PFM_PHI4(4, false, false);
-          }
-      }
-    else if (het)
-      PFM_PHI4(3, true, false); // heterogeneous material: the residual kernel runs
-    else if (getenv("PFM_PHI_CLK") && !oldf) // profiling only
-      {
-        static unsigned long long *d_dbg = nullptr;
-        const size_t nd = (size_t)xcd_grid(nb) * 16;
-        if (!d_dbg && hipMalloc((void **)&d_dbg, nd * sizeof(unsigned long long)) != hipSuccess)
-          return PFM_ERR_HIP;
-        (void)hipMemsetAsync(d_dbg, 0, nd * sizeof(unsigned long long), s);
-        if (atoi(getenv("PFM_PHI_CLK")) == 2 && res)
-          hipLaunchKernelGGL((k_cart_phi4<3, 2, false, true>), dim3(xcd_grid(nb)), dim3(NT4), 0, s, v, cv, S, d_values[2], d_values[3],
-                             d_values[0], d_values[1], zc, d_dbg, res_pde);
-        else if (atoi(getenv("PFM_PHI_CLK")) == 2)
-          hipLaunchKernelGGL((k_cart_phi4<3, 2>), dim3(xcd_grid(nb)), dim3(NT4), 0, s, v, cv, S, d_values[2], d_values[3],
-                             d_values[0], d_values[1], zc, d_dbg, nullptr);
-        else if (res)
-          hipLaunchKernelGGL((k_cart_phi4<3, 1, false, true>), dim3(xcd_grid(nb)), dim3(NT4), 0, s, v, cv, S, d_values[2], d_values[3],
-                             d_values[0], d_values[1], zc, d_dbg, res_pde);
-        else
-          hipLaunchKernelGGL((k_cart_phi4<3, 1>), dim3(xcd_grid(nb)), dim3(NT4), 0, s, v, cv, S, d_values[2], d_values[3],
-                             d_values[0], d_values[1], zc, d_dbg, nullptr);
-        std::vector<unsigned long long> hall(nd);
-        (void)hipMemcpy(hall.data(), d_dbg, nd * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        unsigned long long h[16] = {};
-        for (size_t i = 0; i < nd; ++i)
-          h[i % 16] += hall[i];
-        const char *names[4] = {"load+barrier", "entries+push", "barrier", "copy-out"};
-        fprintf(stderr, "[k_cart_phi4 phase clock, wave 0, cycles per workgroup (%d planes)]", zc_abs);
-        for (int i = 0; i < 4; ++i)
-          fprintf(stderr, " %s=%.0f", names[i], (double)h[i] / nb);
-        for (int i = 0; i < 4; ++i)
-          fprintf(stderr, " role%d=%.0f", i, (double)h[4 + i] / nb);
-        fprintf(stderr, " request-next=%.0f copy-loop=%.0f copy-barrier=%.0f", (double)h[10] / nb, (double)h[8] / nb, (double)h[9] / nb);
-        if (atoi(getenv("PFM_PHI_CLK")) == 2)
-          fprintf(stderr, " | role 3 up to: moments+pushes=%.0f placeholders=%.0f", (double)h[8] / nb, (double)h[9] / nb);
-        fprintf(stderr, "\n");
-      }
-    else if (res)
-      PFM_PHI4(3, false, true);
-    else
-      PFM_PHI4(3, false, false);
-#undef PFM_PHI4
-#undef PFM_PHI4_
-    return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
-  }
-  bool cart_matrix_supported(int dim) { return dim == 2 || dim == 3; }
+    void report_phi4_clock(const KernelClock &clock, size_t nd, const TileGrid &g, int mode)
+    {
+      unsigned long long h[16];
+      clock.sums(nd, 16, h);
+      const unsigned nb = g.n_tiles;
+      const char *names[4] = {"load+barrier", "entries+push", "barrier", "copy-out"};
+      fprintf(stderr, "[k_cart_phi4 phase clock, wave 0, cycles per workgroup (%d planes)]", g.zc);
+      for (int i = 0; i < 4; ++i)
+        fprintf(stderr, " %s=%.0f", names[i], (double)h[i] / nb);
+      for (int i = 0; i < 4; ++i)
+        fprintf(stderr, " role%d=%.0f", i, (double)h[4 + i] / nb);
+      fprintf(stderr, " request-next=%.0f copy-loop=%.0f copy-barrier=%.0f", (double)h[10] / nb, (double)h[8] / nb, (double)h[9] / nb);
+      if (mode == 2)
+        fprintf(stderr, " | role 3 up to: moments+pushes=%.0f placeholders=%.0f", (double)h[8] / nb, (double)h[9] / nb);
+      fprintf(stderr, "\n");
+    }
+  } // namespace
 
-  // Jacobian of a cartesian box: (u,u) rows first, k_cart_phi4 patches constrained (u,u) diagonals afterwards
-  // (same stream) and clears the structurally zero (u,phi) block (cracks.cc:2333-2337) along with its (phi,u) stores
-  // s_phi != s: the two kernels next to each other (the caller has forked s_phi off s and joins them; CartView::patch_*
-  // must be set: the phase-field kernel defers its (u,u) patches)
-  int launch_cart_matrix(const DevView &v, const CartView &cv_in, const pfm_params &p, double *const *d_values, hipStream_t s,
-                         void *d_scal, double *res_pde, int phase, hipStream_t s_phi)
+  // res_pde (pl.rows_residual): the kernel also writes the phase-field rows of the residual.  z-chunks of up to 48 planes as in
+  // k_cart_uu3: at 216^3 the model picks 31 = 217 / 7 instead of ten of 22 with a short last one (10.7 -> 10.4 ms, profiles/r06/zc_scan.txt)
+  int launch_cart_phi4(const CartPlan &pl, const DevView &v, const CartView &cv, double *const *d_values, hipStream_t s,
+                       const void *d_scal, double *res_pde, KernelClock *clock)
   {
-    if (v.dim != 3)
+    if (!pl.phi4())
       return PFM_ERR_UNSUPPORTED;
-    // phase 1 / 2 of an overlapped assembly: the (u,u) kernel is cut into interior and boundary tiles (CartView::tile_sel),
-    // the phase-field kernel follows completely in phase 2 -- it patches (u,u) diagonals of constrained rows and must see
-    // every (u,u) tile written, and the ghost import (~0.1 ms) is hidden behind the interior (u,u) tiles alone
-    CartView cv = cv_in;
-    cv.tile_sel = phase;
-    // next to the phase-field kernel: the same LDS allocation as that kernel (64 granules of 1280 B; 79,472 B are 63), so
-    // that a slot freed by either kernel takes a workgroup of either
-    int rc = launch_cart_uu3(v, cv, p, d_values[0], s, d_scal, res_pde, s_phi != s ? 64 * 1280 : 0);
-    cv.tile_sel = 0;
-    if (rc || phase == 1)
+    if (const int rc = ensure_g1())
       return rc;
-    if (s_phi != s && !cv.patch_count)
-      return PFM_ERR_BAD_ARG; // concurrent kernels need the deferred patch list
-    return launch_cart_phi4(v, cv, p, d_values, s_phi, d_scal, res_pde);
+    const TileGrid &g = pl.grid[PFM_ZC_PHI4];
+    if (g.n_tiles == 0)
+      return PFM_OK;
+    const int zc = switches().no_prio ? -g.zc : g.zc; // (the kernel takes a negated length as "no wave priorities")
+    const dim3 grid(xcd_grid(g.n_tiles)), block(NT4);
+    const size_t nd = (size_t)grid.x * 16;
+    unsigned long long *dbg = nullptr;
+    if (pl.phi4_clock && !(dbg = clock ? clock->reserve(nd, s) : nullptr))
+      return PFM_ERR_HIP;
+    const bool il = pl.interleaved; // one block of values: no (phi,u), (phi,phi) and (u,phi) blocks of their own
+    const PhiKernel kernel = phi4_kernel(pl);
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, v, cv, static_cast<const MatScal *>(d_scal), il ? nullptr : d_values[2], il ? nullptr : d_values[3], d_values[0],
+                       il ? nullptr : d_values[1], zc, dbg, res_pde);
+    if (hipGetLastError() != hipSuccess)
+      return PFM_ERR_HIP;
+    if (pl.phi4_clock)
+      report_phi4_clock(*clock, nd, g, pl.phi4_clock);
+    return PFM_OK;
   }
 
   namespace

@@ -1178,126 +1178,74 @@ namespace pfm
 #undef UU_ENV
   } // namespace
 
-  int launch_cart_uu3(const DevView &v, const CartView &cv, const pfm_params &p, double *vals_uu, hipStream_t s,
-                      const void *d_scal, double *res_pde, int lds_total /* LDS bytes per workgroup to pad to (launch_cart_matrix), 0: none */)
+  namespace
   {
-    int rc = ensure_g1();
-    if (rc)
-      return rc;
-    (void)d_scal; // (the scalar tables travel by value in the kernel's argument segment since round 5)
-    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
-    const int ntx = (OWX + T3X - 1) / T3X, nty = (OWY + T3Y - 1) / T3Y;
-    const bool listed = cv.tile_sel == 2 && cv.bnd_uu3 != nullptr;
-    // planes per workgroup: the interior / boundary launches of an overlapped assembly select tiles plane by plane (zc = 1:
-    // every plane through the prologue's register loads, as in rounds 1-4); otherwise chunks that fill the dispatch rounds
-    const int zc = cv.tile_sel != 0 ? 1 : cart_uu3_zchunk(cv);
-    const int nch = (OWZ + zc - 1) / zc;
-    const unsigned nb = listed ? (unsigned)cv.n_bnd_uu3 : (unsigned)(ntx * nty * nch);
-    if (nb == 0)
-      return PFM_OK;
-    const dim3 grid(xcd_grid(nb)), block(NT3);
-    const bool il = v.layout == PFM_LAYOUT_INTERLEAVED, het = cv.cell_lam != nullptr, res = res_pde != nullptr;
-    UuArgs ka{v, cv, make_mat_scal(p, cv), vals_uu, nullptr, res_pde, zc};
-    // dynamic LDS on top of the kernel's own: the pair launch asks for the allocation of the phase-field kernel
-    auto own_lds = [](const void *fn) {
-      hipFuncAttributes at{};
-      return hipFuncGetAttributes(&at, fn) == hipSuccess ? (int)at.sharedSizeBytes : 0;
+    // k_cart_uu3 by the plan's flags, every instantiation there is, each with its static LDS.  Rows: plain, heterogeneous
+    // material (the residual kernel runs), with the displacement rows of the residual; clocked: blocked, homogeneous.
+    using UuKernel = void (*)(UuArgs);
+    struct UuVariant
+    {
+      UuKernel fn;
+      int own_lds;
+      UuVariant(UuKernel k) : fn(k)
+      {
+        hipFuncAttributes at{};
+        own_lds = hipFuncGetAttributes(&at, reinterpret_cast<const void *>(k)) == hipSuccess ? (int)at.sharedSizeBytes : 0;
+      }
     };
-#define PFM_UU3(NC, HETV, RESV)                                                                                              \
-  do                                                                                                                         \
-    {                                                                                                                        \
-      static const int own = own_lds(reinterpret_cast<const void *>(&k_cart_uu3<NC, false, HETV, RESV>));                    \
-      const int pad = lds_total > 0 ? std::max(0, lds_total - own) : 0;                                                      \
-      hipLaunchKernelGGL((k_cart_uu3<NC, false, HETV, RESV>), grid, block, pad, s, ka);                                      \
-    }                                                                                                                        \
-  while (0)
-    if (getenv("PFM_UU_CLK") && !il && !het) // profiling only
-      {
-        static unsigned long long *d_dbg = nullptr;
-        static size_t nd_cap = 0;
-        const size_t nd = (size_t)xcd_grid(nb) * 32;
-        if (nd > nd_cap)
-          {
-            if (d_dbg)
-              (void)hipFree(d_dbg);
-            if (hipMalloc((void **)&d_dbg, nd * sizeof(unsigned long long)) != hipSuccess)
-              return PFM_ERR_HIP;
-            nd_cap = nd;
-          }
-        (void)hipMemsetAsync(d_dbg, 0, nd * sizeof(unsigned long long), s);
-        ka.dbg = d_dbg;
-        if (res)
-          hipLaunchKernelGGL((k_cart_uu3<3, true, false, true>), grid, block, 0, s, ka);
-        else
-          hipLaunchKernelGGL((k_cart_uu3<3, true>), grid, block, 0, s, ka);
-        std::vector<unsigned long long> hall(nd);
-        (void)hipMemcpy(hall.data(), d_dbg, nd * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        unsigned long long h[32] = {};
-        for (size_t i = 0; i < nd; ++i)
-          h[i % 32] += hall[i];
-        const char *names[8] = {"top barrier", "w*g", "moments", "tables+node c0", "copy c0+node c1", "copy c1+node c2",
-                                "copy c2+landing", "prologue loads (per chunk)"};
-        const double planes = (double)ntx * nty * OWZ;
-        fprintf(stderr, "[k_cart_uu3 phase clock, thread 0, cycles per plane; zc=%d]", zc);
-        for (int i = 0; i < 8; ++i)
-          fprintf(stderr, " %s=%.0f", names[i], (double)h[i] / (i == 7 ? (double)nb : planes));
-        fprintf(stderr, " | wave 7: wait for the requests=%.0f landing=%.0f requests=%.0f\n", (double)h[8] / planes, (double)h[9] / planes,
-                (double)h[10] / planes);
-        fprintf(stderr, "[k_cart_uu3 phase clock] wave 0, component 1: copy-out of component 0=%.0f arithmetic=%.0f barrier=%.0f\n", (double)h[12] / planes,
-                (double)h[13] / planes, (double)h[14] / planes);
-        fprintf(stderr, "[k_cart_uu3 phase clock] component 1 per wave (copy-out of component 0 / arithmetic):");
-        for (int w = 0; w < 8; ++w)
-          fprintf(stderr, " W%d %.0f/%.0f", w, (double)h[16 + 2 * w] / planes, (double)h[17 + 2 * w] / planes);
-        fprintf(stderr, "\n");
-      }
-    else if (il)
-      {
-        if (het)
-          PFM_UU3(4, true, false); // heterogeneous material: the residual kernel runs
-        else if (res)
-          PFM_UU3(4, false, true);
-        else
-          PFM_UU3(4, false, false);
-      }
-    else
-      {
-        if (het)
-          PFM_UU3(3, true, false); // heterogeneous material: the residual kernel runs
-        else if (res)
-          PFM_UU3(3, false, true);
-        else
-          PFM_UU3(3, false, false);
-      }
-#undef PFM_UU3
-    return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
-  }
-  int cart_uu3_zchunk(const CartView &cv)
-  {
-    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
-    const int ntx = (OWX + T3X - 1) / T3X, nty = (OWY + T3Y - 1) / T3Y;
-    return zchunk_of(cv, PFM_ZC_UU3, (long long)ntx * nty, OWZ);
-  }
+    const UuVariant &uu3_variant(const CartPlan &pl)
+    {
+      static const UuVariant plain[2][3] = {{k_cart_uu3<3, false, false, false>, k_cart_uu3<3, false, true, false>, k_cart_uu3<3, false, false, true>},
+                                            {k_cart_uu3<4, false, false, false>, k_cart_uu3<4, false, true, false>, k_cart_uu3<4, false, false, true>}};
+      static const UuVariant clocked[2] = {k_cart_uu3<3, true>, k_cart_uu3<3, true, false, true>};
+      return pl.uu3_clock ? clocked[pl.rows_residual] : plain[pl.interleaved][pl.het ? 1 : pl.rows_residual ? 2 : 0];
+    }
 
-  void cart_uu3_boundary_tiles(const CartView &cv, std::vector<int32_t> &out)
-  {
-    out.clear();
-    const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
-    const int ntx = (OWX + T3X - 1) / T3X, nty = (OWY + T3Y - 1) / T3Y;
-    for (int tk = 0; tk < OWZ; ++tk)
-      for (int tiy = 0; tiy < nty; ++tiy)
-        for (int tix = 0; tix < ntx; ++tix)
-          {
-            const int i0 = cv.o0[0] + tix * T3X, j0 = cv.o0[1] + tiy * T3Y, k = cv.o0[2] + tk;
-            if (cart_range_has_ghost(cv, 0, i0 - 1, i0 + T3X) || cart_range_has_ghost(cv, 1, j0 - 1, j0 + T3Y) ||
-                cart_range_has_ghost(cv, 2, k - 1, k + 1))
-              out.push_back(tix + ntx * (tiy + nty * tk));
-          }
-  }
+    void report_uu3_clock(const KernelClock &clock, size_t nd, const TileGrid &g, int owz)
+    {
+      unsigned long long h[32];
+      clock.sums(nd, 32, h);
+      const char *names[8] = {"top barrier", "w*g", "moments", "tables+node c0", "copy c0+node c1", "copy c1+node c2",
+                              "copy c2+landing", "prologue loads (per chunk)"};
+      const double planes = (double)g.ntx * g.nty * owz;
+      fprintf(stderr, "[k_cart_uu3 phase clock, thread 0, cycles per plane; zc=%d]", g.zc);
+      for (int i = 0; i < 8; ++i)
+        fprintf(stderr, " %s=%.0f", names[i], (double)h[i] / (i == 7 ? (double)g.n_tiles : planes));
+      fprintf(stderr, " | wave 7: wait for the requests=%.0f landing=%.0f requests=%.0f\n", (double)h[8] / planes, (double)h[9] / planes,
+              (double)h[10] / planes);
+      fprintf(stderr, "[k_cart_uu3 phase clock] wave 0, component 1: copy-out of component 0=%.0f arithmetic=%.0f barrier=%.0f\n", (double)h[12] / planes,
+              (double)h[13] / planes, (double)h[14] / planes);
+      fprintf(stderr, "[k_cart_uu3 phase clock] component 1 per wave (copy-out of component 0 / arithmetic):");
+      for (int w = 0; w < 8; ++w)
+        fprintf(stderr, " W%d %.0f/%.0f", w, (double)h[16 + 2 * w] / planes, (double)h[17 + 2 * w] / planes);
+      fprintf(stderr, "\n");
+    }
+  } // namespace
 
-  // entry point used by the debug overlay (pfm_ctx_force_path(ctx, 2)) and by launch_cart_matrix
-  int launch_cart_uu_only(const DevView &v, const CartView &cv, const pfm_params &p, double *vals_uu, hipStream_t s,
-                          void *d_scal)
+  // res_pde (pl.rows_residual): the kernel also writes the displacement rows of the residual (from its matrix rows)
+  int launch_cart_uu3(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *vals_uu, hipStream_t s,
+                      double *res_pde, KernelClock *clock)
   {
-    return launch_cart_uu3(v, cv, p, vals_uu, s, d_scal, nullptr);
+    if (const int rc = ensure_g1())
+      return rc;
+    const TileGrid &g = pl.grid[PFM_ZC_UU3];
+    if (!pl.uu3())
+      return PFM_ERR_UNSUPPORTED;
+    if (g.n_tiles == 0)
+      return PFM_OK;
+    const dim3 grid(xcd_grid(g.n_tiles)), block(NT3);
+    UuArgs ka{v, cv, make_mat_scal(p, cv), vals_uu, nullptr, res_pde, g.zc};
+    const UuVariant &k = uu3_variant(pl);
+    // next to the phase-field kernel: dynamic LDS on top of the kernel's own, up to that kernel's allocation
+    const int pad = pl.pair ? std::max(0, PFM_PAIR_LDS_BYTES - k.own_lds) : 0;
+    const size_t nd = (size_t)grid.x * 32;
+    if (pl.uu3_clock && !(ka.dbg = clock ? clock->reserve(nd, s) : nullptr))
+      return PFM_ERR_HIP;
+    hipLaunchKernelGGL(k.fn, grid, block, pad, s, ka);
+    if (hipGetLastError() != hipSuccess)
+      return PFM_ERR_HIP;
+    if (pl.uu3_clock)
+      report_uu3_clock(*clock, nd, g, cv.o1[2] - cv.o0[2] + 1);
+    return PFM_OK;
   }
 } // namespace pfm

@@ -12,6 +12,7 @@
 //   * cell->get_dof_indices + the Trilinos column search (cracks.cc:2439-2463) become a
 //     one-byte-per-vertex-pair slot table.
 #include "pfm_internal.h"
+#include "pfm_cart_plan.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and constants only: the entry points are bound with dlopen (rccl() below)
@@ -109,8 +110,8 @@ namespace
     double per = 0;
     if (f >> q >> per && q != "max" && per > 0)
       t = std::min(t, std::max(1, (int)(std::stod(q) / per)));
-    if (const char *e = getenv("PFM_HOST_THREADS"))
-      t = std::max(1, atoi(e));
+    if (switches().host_threads)
+      t = switches().host_threads;
     n = std::max(1, std::min(t, 32));
     return n;
   }
@@ -1300,10 +1301,10 @@ namespace
     PatchPlan pl;
     const int32_t N = m->n_nodes, NO = m->n_owned_nodes;
     const int64_t NC = m->n_cells;
-    if (m->dim != 2 || NC == 0 || getenv("PFM_NO_PATCH"))
+    if (m->dim != 2 || NC == 0 || Switches::no_patch())
       return pl;
     // PFM_CTX_TIMING=1: the phases of this classification on stderr (it runs on a thread of its own)
-    const bool ptime = getenv("PFM_CTX_TIMING") != nullptr;
+    const bool ptime = Switches::ctx_timing();
     auto pt0 = std::chrono::steady_clock::now();
     auto pmark = [&](const char *what) {
       if (!ptime)
@@ -1809,7 +1810,7 @@ namespace
     PatchPlan3 pl;
     const int32_t N = m->n_nodes, NO = m->n_owned_nodes;
     const int64_t NC = m->n_cells;
-    if (m->dim != 3 || NC == 0 || getenv("PFM_NO_PATCH"))
+    if (m->dim != 3 || NC == 0 || Switches::no_patch())
       return pl;
     const double *X = m->coords;
     double xmin[3] = {X[0], X[1], X[2]}, xmax[3] = {X[0], X[1], X[2]};
@@ -1948,8 +1949,7 @@ namespace
           }
       }
     // per level: the lattice of the box of its cells, the tables
-    static const long long max_table = getenv("PFM_OVERLAY3_MAX_TABLE") ? atoll(getenv("PFM_OVERLAY3_MAX_TABLE")) : 400000000LL;
-    static const long long min_rows = getenv("PFM_OVERLAY3_MIN_ROWS") ? atoll(getenv("PFM_OVERLAY3_MIN_ROWS")) : 64;
+    const long long max_table = Switches::overlay3_max_table(), min_rows = Switches::overlay3_min_rows();
     for (size_t L = 0; L < lv.size(); ++L)
       {
         long long lo[3] = {LLONG_MAX, LLONG_MAX, LLONG_MAX}, hi[3] = {LLONG_MIN, LLONG_MIN, LLONG_MIN};
@@ -2115,7 +2115,7 @@ namespace
 
   struct PhaseClock
   {
-    const bool on = getenv("PFM_CTX_TIMING") != nullptr;
+    const bool on = Switches::ctx_timing();
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     void mark(const char *what)
     {
@@ -2134,7 +2134,7 @@ namespace
   // stderr hides what libstdc++ or the HIP runtime say before they abort)
   void abort_trace_handler(int)
   {
-    const char *path = getenv("PFM_ABORT_TRACE");
+    const char *path = switches().abort_trace; // (read before the handler was installed)
     const int fd = path ? open(path, O_WRONLY | O_CREAT | O_APPEND, 0644) : 2;
     void *frames[64];
     const int n = backtrace(frames, 64);
@@ -2146,7 +2146,7 @@ namespace
   {
     static std::once_flag once;
     std::call_once(once, [] {
-      if (getenv("PFM_ABORT_TRACE"))
+      if (switches().abort_trace)
         {
           signal(SIGABRT, abort_trace_handler);
           signal(SIGSEGV, abort_trace_handler);
@@ -2322,7 +2322,7 @@ extern "C"
         // reproducible; it costs some thirty small launches per assembly (1.1e6-cell overlay mesh: Jacobian 4.45 -> 5.1 ms,
         // residual only 0.6 -> 1.3 ms), so the default keeps the atomic class.  Needs the records of DevView::cres, i.e.
         // hanging nodes with at most four parents.
-        bool hanging_coloured = dim == 3 && hn_idx && !lattice_ok && getenv("PFM_HANGING_COLOURED") != nullptr;
+        bool hanging_coloured = dim == 3 && hn_idx && !lattice_ok && Switches::hanging_coloured();
         for (int32_t k = 0; k < m->n_hanging && hanging_coloured; ++k)
           hanging_coloured = m->hn_ptr[k + 1] - m->hn_ptr[k] <= 4;
         c->hanging_coloured = hanging_coloured;
@@ -2544,7 +2544,7 @@ extern "C"
                         c->n_hcells = (int64_t)hcells.size();
                         // round 6 default: scratch + ordered gather instead of FP64 atomics (ensure_hang_gather, on first use);
                         // PFM_HANGING_ATOMIC=1 keeps the atomic class, PFM_HANGING_COLOURED=1 the colour classes of round 5
-                        c->hang_gather = !hanging_coloured && getenv("PFM_HANGING_ATOMIC") == nullptr;
+                        c->hang_gather = !hanging_coloured && !Switches::hanging_atomic();
                       }
                   }
               }
@@ -3586,9 +3586,10 @@ extern "C"
     if (c->overlap_lists_ready || c->kernel_path != 1 || c->v.dim != 3)
       return PFM_OK;
     std::vector<int32_t> t_uu, t_res;
-    int zc = 0;
-    cart_uu3_boundary_tiles(c->cv, t_uu);
-    cart_res3_boundary_tiles(c->cv, t_res, zc);
+    pfm::CartView half2 = c->cv; // the grids of the second half, before there are lists
+    half2.tile_sel = 2;
+    cart_tile_grid(half2, PFM_ZC_UU3, cart_n_cu(), &t_uu);
+    const int zc = cart_tile_grid(half2, PFM_ZC_RES3, cart_n_cu(), &t_res).zc;
     const int n_uu = (int)t_uu.size(), n_res = (int)t_res.size();
     if (t_uu.empty())
       t_uu.push_back(0);
@@ -3628,28 +3629,9 @@ extern "C"
   }
 
   // ---- assembly dispatch: one plan (AssemblyPlan), one routine per kernel family ("Assembly dispatch") ----
-  // The A/B switches of the dispatch.  Read once per process, all of them at the first plan: the members (switches()).
-  // Read on every call that gets as far as needing them, so that one process can compare the variants: the functions.
-  struct Switches
-  {
-    const bool jac_sequential = getenv("PFM_JAC_SEQUENTIAL") != nullptr;         // 3-D box: the two Jacobian kernels in turn
-    const bool general_sequential = getenv("PFM_GENERAL_SEQUENTIAL") != nullptr; // the atomic class behind the colour classes
-    const bool levels_concurrent = getenv("PFM_OVERLAY3_CONCURRENT") != nullptr; // 3-D overlay: a stream per level lattice
-    // -1 = lowest, 1 = highest dispatch priority of the side stream (A/B runs of the phase-field kernel of the pair)
-    const int side_prio = getenv("PFM_SIDE_PRIO") ? atoi(getenv("PFM_SIDE_PRIO")) : 0;
-    // PFM_SIDE_STREAM=1: the residual launch of a 3-D box Jacobian on the side stream.  Measured on MI355X at 216^3: no
-    // gain (21.4 vs 21.1 ms per assembly), the kernels do not share CUs usefully; off by default.
-    static bool side_stream() { return getenv("PFM_SIDE_STREAM") != nullptr; }
-    // PFM_CART2D_NO_FILL: k_cart2d_cells writes the zeros of the (u,phi) block with the rows; PFM_CART2D_ONE_LAUNCH: the
-    // single launch of round 5, which does the same
-    static bool cart2d_fill() { return getenv("PFM_CART2D_NO_FILL") == nullptr && getenv("PFM_CART2D_ONE_LAUNCH") == nullptr; }
-    // PFM_NO_FUSED_SCATTER=1: the line-search call scatters the solution with a launch of its own
-    static bool fused_scatter() { return getenv("PFM_NO_FUSED_SCATTER") == nullptr; }
-  };
-
-  static const Switches &switches() { static const Switches s; return s; }
+  // (the A/B switches of the dispatch: pfm_switches.h)
   // the stress split in the matrix (cracks.cc:2294): the general family has it, the row-owner kernels do not
-  static bool stress_split(const pfm_ctx *c) { return c->have_params && c->prm.decompose_stress_matrix > 0 && c->prm.timestep_number > 0; }
+  static bool stress_split(const pfm_ctx *c) { return c->have_params && cart_scheme(c->prm).split; }
 
   // Every decision of one assemble_impl call; what each means stands where it is made (plan_assembly, after_tables).
   struct AssemblyPlan
@@ -3658,6 +3640,7 @@ extern "C"
     bool residual_only = false, split = false, cart = false, patches = false, overlay3 = false, overlay_uu = false, nothing = false;
     bool pair = false, fork = false, levels_concurrent = false, fill_up_block = false, up_block_cleared = false;
     bool gather = false, fork_general = false, atomic_stream = false; // final behind the lazy tables: after_tables
+    CartPlan box; // cart: what the launchers of the cartesian family do (plan_cart)
     void after_tables(const pfm_ctx *c, bool gather_ready);
   };
 
@@ -3668,7 +3651,9 @@ extern "C"
     p.phase = phase;
     p.residual_only = residual_only != 0;
     p.split = stress_split(c);
-    p.cart = c->kernel_path == 1 && !p.split && (residual_only || cart_matrix_supported(c->v.dim)); // assemble_box
+    if (c->kernel_path == 1)
+      p.box = plan_cart(c->v, c->cv, c->prm, residual_only, phase, cart_n_cu());
+    p.cart = c->kernel_path == 1 && p.box.supported; // assemble_box
     // the general family and the overlays are not cut into interior / boundary work: everything in phase 2
     p.nothing = !p.cart && phase == 1;
     // debug: general + cart (u,u).  Path 2 implies no overlay (pfm_ctx_force_path: lattice contexts only, which have no
@@ -3684,7 +3669,7 @@ extern "C"
     // The two Jacobian kernels of a 3-D box next to each other (default): with equal LDS allocations (64 granules of 1280 B
     // each) any freed slot of a CU takes a workgroup of either kernel, the (u,u) and the phase-field workgroups mix and
     // fill each other's stalls: 14.07 -> 13.75 ms per assembly at 216^3 (PFM_JAC_SEQUENTIAL=1: one after the other).
-    p.pair = p.cart && !switches().jac_sequential && cart_jacobian_pair(c->v, c->cv, c->prm, residual_only, phase);
+    p.pair = p.cart && p.box.pair;
     // 2-D boxes never fork: the second launch of k_cart2d_cells (phase-field rows) reads the mean |diagonal| the first one
     // leaves in CartView::cell_avg, so it must follow it on the same stream.  (The fork was measured at 0.262 -> 0.259 ms of
     // kernel time at 1000^2 and was off by default; with an event between the launches nothing of that overlap is left.)
@@ -3729,12 +3714,7 @@ extern "C"
   {
     if (c->side_stream)
       return PFM_OK;
-    const int side_prio = switches().side_prio;
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    const hipError_t es = side_prio == 0 ? hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking)
-                                         : hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, side_prio > 0 ? prio_hi : prio_lo);
-    if (es != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
+    if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)
       return fail(c, PFM_ERR_HIP, "side stream");
     return PFM_OK;
@@ -3798,9 +3778,7 @@ extern "C"
   static int ensure_tables(pfm_ctx *c, const AssemblyPlan &p, bool &gather_ready)
   {
     int rc = PFM_OK;
-    if (p.cart && p.phase != 0 && !c->overlap_lists_ready)
-      rc = ensure_overlap_lists(c); // dropped by pfm_ctx_force_zchunk: the lists of the new residual length
-    if (rc == PFM_OK && !p.cart)
+    if (!p.cart)
       rc = guarded(c, [&] { ensure_general_tables(c); }); // (lattice contexts build them on first use)
     if (rc == PFM_OK && p.patches)
       rc = p.overlay3 ? ensure_overlay3_ready(c) : ensure_patch_ready(c);
@@ -3862,8 +3840,8 @@ extern "C"
     cv.up_block_cleared = p.up_block_cleared ? 1 : 0;
     if (!p.pair)
       cv.patch_idx = nullptr, cv.patch_val = nullptr, cv.patch_count = nullptr, cv.patch_cap = 0;
-    rc = launch_assemble_cart(c->v, cv, c->prm, p.residual_only, d_values, d_res_pde, d_res_tot, c->stream,
-                              p.fork ? c->side_stream : c->stream, c->d_scal, p.phase);
+    rc = launch_assemble_cart(p.box, c->v, cv, c->prm, d_values, d_res_pde, d_res_tot, c->stream, p.fork ? c->side_stream : c->stream,
+                              c->d_scal, &c->clock);
     if (p.fork)
       if (const int rcj = join_from(c, c->side_stream, c->stream, c->ev_join, "join"))
         return rcj;
@@ -3936,7 +3914,9 @@ extern "C"
     for (size_t i = 0; i < nl && rc == PFM_OK; ++i)
       {
         hipStream_t st = par ? c->ov_streams[i] : c->stream;
-        rc = launch_assemble_cart(c->v, c->levels3[i].cv, c->prm, p.residual_only, d_values, d_res_pde, d_res_tot, st, st, c->levels3[i].d_scal, 0);
+        const pfm::CartView &lcv = c->levels3[i].cv; // one plan per level lattice
+        rc = launch_assemble_cart(plan_cart(c->v, lcv, c->prm, p.residual_only, 0, cart_n_cu()), c->v, lcv, c->prm, d_values, d_res_pde,
+                                  d_res_tot, st, st, c->levels3[i].d_scal, &c->clock);
       }
     for (size_t i = 0; par && i < nl; ++i)
       if (const int rcj = join_from(c, c->ov_streams[i], c->stream, c->ov_events[i], "join (overlay levels)"))
@@ -4001,7 +3981,11 @@ extern "C"
         c->scal_dirty = rc != PFM_OK;
       }
     if (rc == PFM_OK && p.overlay_uu)
-      rc = launch_cart_uu_only(c->v, c->cv, c->prm, d_values[0], c->stream, c->d_scal);
+      {
+        CartPlan uu = plan_cart(c->v, c->cv, c->prm, 0, 0, cart_n_cu());
+        uu.rows_residual = uu.pair = false; // (the general family has written the residual)
+        rc = launch_cart_uu3(uu, c->v, c->cv, c->prm, d_values[0], c->stream, nullptr, &c->clock);
+      }
     return PFM_OK;
   }
 
@@ -4016,6 +4000,9 @@ extern "C"
     if (!c->have_params)
       return fail(c, PFM_ERR_BAD_ARG, "pfm_set_params has not been called");
     (void)hipSetDevice(c->device);
+    if (phase != 0) // in front of the plan, whose grids of a second half are those of the lists (pfm_ctx_force_zchunk drops them)
+      if (const int rcl = ensure_overlap_lists(c))
+        return rcl;
     AssemblyPlan plan = plan_assembly(c, residual_only, phase, d_values);
     bool gather_ready = false;
     if (const int rct = ensure_tables(c, plan, gather_ready))
@@ -4110,9 +4097,7 @@ extern "C"
       return PFM_ERR_BAD_ARG;
     if (!c->cart_ok || (kernel == PFM_ZC_RES2) != (c->v.dim == 2))
       return PFM_ERR_UNSUPPORTED;
-    // the launchers' own helpers, on the context's box
-    *planes = kernel == PFM_ZC_UU3 ? cart_uu3_zchunk(c->cv) : kernel == PFM_ZC_PHI4 ? cart_phi4_zchunk(c->cv)
-            : kernel == PFM_ZC_RES3 ? cart_res3_zchunk(c->cv) : cart_res2_zchunk(c->cv);
+    *planes = cart_zchunk(c->cv, kernel); // the launchers' own geometry, on the context's box
     return PFM_OK;
   }
 

@@ -11,6 +11,7 @@
 #include <utility>
 
 #include "../../include/pfm_assemble.h"
+#include "pfm_kernel_clock.h"
 
 namespace pfm
 {
@@ -200,33 +201,22 @@ namespace pfm
                       double *d_buf, int unpack, hipStream_t s);
   int launch_halo_unpack(const DevView &v, const int32_t *d_nodes, int64_t n, const double *d_buf,
                          hipStream_t s);
-  // d_scal: the context's device buffer (PFM_SCAL_BYTES) for per-launch scalar tables.  Kernels read them through
-  // a pointer instead of by-value kernel arguments: a 900-byte argument struct pins so many SGPRs that the
-  // compiler spills them into VGPR lanes (12 % of the instructions of the phase-field kernel were such moves).
-  int launch_assemble_cart(const DevView &v, const CartView &cv, const pfm_params &p, int residual_only,
-                           double *const *d_values, double *d_res_pde, double *d_res_tot, hipStream_t s,
-                           hipStream_t s_residual, void *d_scal, int phase = 0);
-  // true: this assembly is the pair k_cart_uu3<RES> + k_cart_phi4<RES> and may run them on two streams (s, s_residual of
-  // launch_assemble_cart) -- the caller forks / joins and applies the deferred patches (CartView::patch_*)
-  bool cart_jacobian_pair(const DevView &v, const CartView &cv, const pfm_params &p, int residual_only, int phase);
+  // The launchers of the cartesian family: each carries out its part of pl = plan_cart(v, cv, p, ...) (pfm_cart_plan.h).
+  // s_side: the stream the caller forked off s for the phase-field kernel of the pair or for the residual kernel, else s.
+  // d_scal: the MatScal of the current parameters on the device (upload_mat_scal; by value it would pin 900 bytes of
+  // SGPRs in k_cart_phi4).  clock: the context's counters, for a plan that clocks a kernel.
+  struct CartPlan;
+  int launch_assemble_cart(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
+                           double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock);
+  int launch_cart2d(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
+                    double *res_pde, double *res_tot, hipStream_t s);
+  int launch_cart_uu3(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *vals_uu, hipStream_t s,
+                      double *res_pde, KernelClock *clock);
+  int launch_cart_phi4(const CartPlan &pl, const DevView &v, const CartView &cv, double *const *d_values, hipStream_t s,
+                       const void *d_scal, double *res_pde, KernelClock *clock);
   int launch_cart_apply_patches(const CartView &cv, double *vals_uu, hipStream_t s, int *status);
-  bool cart_matrix_supported(int dim);
-  // 2-D boxes: row-owner Jacobian + residual of runs WITHOUT the stress split (pfm_cart2d.hip; PFM_ERR_UNSUPPORTED otherwise)
-  int launch_cart2d(const DevView &v, const CartView &cv, const pfm_params &p, int residual_only, double *const *d_values,
-                    double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_phi);
-  // z-chunk length of a marching kernel: `tiles` columns, `planes` node planes, one redundant cell layer per chunk,
-  // `per_cu` resident workgroups per CU.  Maximises (fill of the last dispatch round) x (useful layers per chunk).
-  int choose_zchunk(long long tiles, int planes, int zc_min, int zc_max, int per_cu);
-  // the chunk length of marching kernel `kernel` (PFM_ZC_*) over `tiles` columns of `planes` planes, as every launcher of
-  // it computes it: cv.zc_force, else the tuning variable (PFM_UU_ZC, PFM_PHI_ZC, PFM_RES_ZC, PFM_RES2_ZC; read once),
-  // else choose_zchunk in the kernel's range.  Forced lengths are clamped to [1, max(planes, 1)].
-  int zchunk_of(const CartView &cv, int kernel, long long tiles, int planes);
-  // ... over the owned box of cv, each with its kernel's tile count; k_cart_uu3 marches single planes instead in the two
-  // halves of an overlapped assembly (launch_cart_uu3)
-  int cart_uu3_zchunk(const CartView &cv);
-  int cart_phi4_zchunk(const CartView &cv);
-  int cart_res3_zchunk(const CartView &cv);
-  int cart_res2_zchunk(const CartView &cv);
+  int cart_n_cu();                                 // CUs of the device (asked once)
+  int cart_zchunk(CartView cv, int kernel);        // chunk length of a whole assembly of cv by marching kernel PFM_ZC_*
   // XCD-aware launch: workgroup i runs on XCD i % 8.  The kernels are launched with a grid rounded up to a multiple
   // of 8 and map blockIdx to (blockIdx % 8) * (grid / 8) + blockIdx / 8, so that every XCD works on one contiguous
   // range of tiles (neighbouring tiles share their halo in that XCD's L2) and the slow boundary tiles are spread over
@@ -237,11 +227,6 @@ namespace pfm
   // the Jacobian launchers expect the MatScal of the current parameters at d_scal (uploaded by pfm_assemble_device
   // after every pfm_set_params, pfm_ctx::scal_dirty)
   int upload_mat_scal(const pfm_params &p, const CartView &cv, void *d_scal, hipStream_t s);
-  int launch_cart_phi4(const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values, hipStream_t s,
-                       const void *d_scal, double *res_pde);
-  // res_pde != nullptr: the kernel also writes the displacement rows of the residual (from its matrix rows, see the kernel)
-  int launch_cart_uu3(const DevView &v, const CartView &cv, const pfm_params &p, double *vals_uu, hipStream_t s,
-                      const void *d_scal, double *res_pde, int lds_total = 0);
   // node graph of a general mesh on the device (pfm_graph.hip)
   struct GraphScratch
   {
@@ -264,11 +249,6 @@ namespace pfm
   int launch_check_row_lengths(const uint8_t *d_mark, const long long *d_ptr, int32_t NO, int want, int *d_bad, hipStream_t s);
   int launch_overlay3_rows(const int32_t *d_node_at, const int32_t *d_row_at, int NX, int NY, int NZ, const long long *d_nadj_ptr,
                            const int32_t *d_nadj, uint32_t *d_nbr_mask, uint8_t *d_row_perm, int *d_bad, hipStream_t s);
-  // host: indices of the tiles of k_cart_uu3 / k_cart_residual3 that read a ghost node (pfm_assemble_overlapped, phase 2)
-  void cart_uu3_boundary_tiles(const CartView &cv, std::vector<int32_t> &out);
-  void cart_res3_boundary_tiles(const CartView &cv, std::vector<int32_t> &out, int &zc);
-  int launch_cart_uu_only(const DevView &v, const CartView &cv, const pfm_params &p, double *vals_uu, hipStream_t s,
-                          void *d_scal);
   // color_ptr[n_classes + 1]: ranges of DevView::color_cells, one launch per class; the LAST class holds the cells with
   // hanging vertices (their rows are distributed to the parents, which other vertices of the same cell may be: atomics)
   int launch_assemble_general(const DevView &v, const pfm_params &p, int residual_only,
@@ -378,6 +358,7 @@ struct pfm_ctx
   double *d_halo_send = nullptr, *d_halo_recv = nullptr; // message buffers of pfm_halo_exchange
   int64_t halo_buf_bytes = 0;                            // their share of device_bytes
   void *d_scal = nullptr; // per-launch scalar tables of the cartesian kernels (PFM_SCAL_BYTES)
+  pfm::KernelClock clock; // counters of the phase clocks of k_cart_uu3 / k_cart_phi4 (profiling)
   int64_t n_flag_u = 0;   // displacement dofs with a constraint flag (capacity of the deferred patch list, CartView::patch_*)
   uint8_t *d_row_perm = nullptr; // CartView::row_perm storage (in allocs)
   bool overlap_lists_ready = false; // CartView::bnd_uu3 / bnd_res3 built
