@@ -13,6 +13,8 @@
 //     one-byte-per-vertex-pair slot table.
 #include "pfm_internal.h"
 #include "pfm_cart_plan.h"
+#include "pfm_host_pool.h"
+#include "pfm_mesh_plan.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and constants only: the entry points are bound with dlopen (rccl() below)
@@ -24,13 +26,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <fstream>
 #include <new>
 #include <mutex>
 #include <thread>
-#include <condition_variable>
-#include <functional>
-#include <pthread.h>
 #include <execinfo.h>
 #include <fcntl.h>
 #include <csignal>
@@ -94,198 +92,6 @@ namespace
       {
         return fail(c, PFM_ERR_NOMEM, "host allocation failed");
       }
-  }
-
-  // Host threads for the O(n_nodes) / O(n_cells) loops of the context build (setup_system of the reference runs them
-  // after every refine_mesh, cracks.cc:4148): the cores this process may use (affinity mask, cgroup quota), at most 32.
-  int host_threads()
-  {
-    static int n = 0;
-    if (n)
-      return n;
-    unsigned hc = std::thread::hardware_concurrency();
-    int t = hc ? (int)hc : 1;
-    std::ifstream f("/sys/fs/cgroup/cpu.max");
-    std::string q;
-    double per = 0;
-    if (f >> q >> per && q != "max" && per > 0)
-      t = std::min(t, std::max(1, (int)(std::stod(q) / per)));
-    if (switches().host_threads)
-      t = switches().host_threads;
-    n = std::max(1, std::min(t, 32));
-    return n;
-  }
-
-  // Worker threads of the context build, kept between calls: a rebuild at 2.7e5 cells runs some twenty parallel loops of
-  // 20-200 us each, and starting 16 threads costs more than such a loop.  One parallel region at a time (a second caller --
-  // the colour and overlay threads of pfm_ctx_create run next to the main thread -- starts its own threads as before).
-  // A forked child has none of the parent's threads: it starts over with an empty pool (pthread_atfork).
-  struct HostPool
-  {
-    std::mutex mx, region;
-    std::condition_variable cv, cv_done;
-    std::vector<std::thread> th;
-    const std::function<void(int)> *job = nullptr;
-    std::atomic<uint64_t> gen{0};
-    std::atomic<int> left{0};
-    int want = 0;
-    std::atomic<bool> stop{false};
-
-    // the loops of a rebuild follow one another within microseconds: a worker (and the caller, for the end of a region) polls
-    // for ~50 us before it sleeps on the condition variable (a sleep and a wake-up cost 30-50 us each with 16 threads)
-    static bool spin_until(const std::function<bool()> &ready)
-    {
-      const auto t0 = std::chrono::steady_clock::now();
-      for (int i = 0;; ++i)
-        {
-          if (ready())
-            return true;
-          __builtin_ia32_pause();
-          if ((i & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(50))
-            return false;
-        }
-    }
-    void worker(int id, uint64_t seen) // seen: the generation at the worker's creation (it answers the ones after it)
-    {
-      for (;;)
-        {
-          if (!spin_until([&] { return stop.load(std::memory_order_acquire) || gen.load(std::memory_order_acquire) != seen; }))
-            {
-              std::unique_lock<std::mutex> lk(mx);
-              cv.wait(lk, [&] { return stop.load() || gen.load() != seen; });
-            }
-          if (stop.load())
-            return;
-          seen = gen.load(std::memory_order_acquire);
-          // EVERY worker answers every region (those beyond `want` without running anything): want and job are then never
-          // rewritten while a worker may still read them
-          if (id < want)
-            (*job)(id);
-          if (left.fetch_sub(1, std::memory_order_acq_rel) == 1)
-            {
-              std::lock_guard<std::mutex> lk(mx);
-              cv_done.notify_one();
-            }
-        }
-    }
-    // f(t) for t = 0 .. nt-1, t = 0 on the calling thread; false when the pool is taken (caller falls back)
-    bool run(int nt, const std::function<void(int)> &f)
-    {
-      std::unique_lock<std::mutex> reg(region, std::try_to_lock);
-      if (!reg.owns_lock())
-        return false;
-      while ((int)th.size() + 1 < nt)
-        {
-          const int id = (int)th.size() + 1;
-          const uint64_t born = gen.load(std::memory_order_acquire);
-          th.emplace_back([this, id, born] { worker(id, born); });
-        }
-      job = &f;
-      want = nt;
-      left.store((int)th.size(), std::memory_order_relaxed);
-      gen.fetch_add(1, std::memory_order_release);
-      {
-        std::lock_guard<std::mutex> lk(mx); // a worker is either before its look at gen or asleep and notified below
-      }
-      cv.notify_all();
-      f(0);
-      if (!spin_until([&] { return left.load(std::memory_order_acquire) == 0; }))
-        {
-          std::unique_lock<std::mutex> lk(mx);
-          cv_done.wait(lk, [&] { return left.load() == 0; });
-        }
-      job = nullptr;
-      return true;
-    }
-    ~HostPool()
-    {
-      stop.store(true);
-      {
-        std::lock_guard<std::mutex> lk(mx);
-      }
-      cv.notify_all();
-      for (auto &t : th)
-        t.join();
-    }
-  };
-  // Three pools: pfm_ctx_create classifies the cells (overlay) and colours them on two threads next to the one that uploads;
-  // each takes the first pool that is free.
-  constexpr int N_POOLS = 3;
-  std::atomic<HostPool *> g_pools{nullptr};
-  HostPool *host_pools()
-  {
-    HostPool *p = g_pools.load(std::memory_order_acquire);
-    if (p)
-      return p;
-    static std::mutex mk;
-    std::lock_guard<std::mutex> lk(mk);
-    p = g_pools.load(std::memory_order_acquire);
-    if (!p)
-      {
-        static bool hooked = false;
-        if (!hooked)
-          {
-            hooked = true;
-            pthread_atfork(nullptr, nullptr, [] { g_pools.store(nullptr, std::memory_order_release); }); // the child's copy is leaked
-            atexit([] { delete[] g_pools.exchange(nullptr); });
-          }
-        p = new HostPool[N_POOLS];
-        g_pools.store(p, std::memory_order_release);
-      }
-    return p;
-  }
-
-  // fn(begin, end) over [0, n) in contiguous chunks, one per thread (at least `grain` items per thread).  An exception
-  // thrown by a worker (bad_alloc in a lambda that grows a vector) is carried to the caller instead of ending the
-  // process in std::terminate.  parallel_chunks: the same with the chunk index, for loops that keep per-chunk results.
-  template <class F>
-  void parallel_chunks(int nt, F &&fn)
-  {
-    if (nt <= 1)
-      {
-        fn(0);
-        return;
-      }
-    std::vector<std::exception_ptr> err((size_t)nt);
-    const std::function<void(int)> body = [&fn, &err](int t) {
-      try
-        {
-          fn(t);
-        }
-      catch (...)
-        {
-          err[(size_t)t] = std::current_exception();
-        }
-    };
-    HostPool *pools = host_pools();
-    bool done = false;
-    for (int q = 0; q < N_POOLS && !done; ++q)
-      done = pools[q].run(nt, body);
-    if (!done)
-      {
-        std::vector<std::thread> th;
-        th.reserve(nt);
-        for (int t = 1; t < nt; ++t)
-          th.emplace_back([&body, t] { body(t); });
-        body(0);
-        for (auto &x : th)
-          x.join();
-      }
-    for (auto &e : err)
-      if (e)
-        std::rethrow_exception(e);
-  }
-  inline int chunks_for(int64_t n, int64_t grain) { return (int)std::min<int64_t>(host_threads(), std::max<int64_t>(1, n / std::max<int64_t>(grain, 1))); }
-  template <class F>
-  void parallel_for(int64_t n, F &&fn, int64_t grain = 16384)
-  {
-    const int nt = chunks_for(n, grain);
-    if (nt <= 1)
-      {
-        fn((int64_t)0, n);
-        return;
-      }
-    parallel_chunks(nt, [&fn, n, nt](int t) { fn(n * t / nt, n * (t + 1) / nt); });
   }
 
   // Host -> device copy of caller-owned (pageable) memory.  hipMemcpy from pageable memory ran at ~3.6 GB/s on the
@@ -437,186 +243,8 @@ namespace
       }
     return d;
   }
-  // a[i] += a[i-1] ... in place (row pointers of 1e7 rows: 24 ms on one core)
-  template <class T>
-  void inclusive_scan_parallel(T *a, int64_t n)
-  {
-    const int nt = chunks_for(n, 65536);
-    if (nt <= 1)
-      {
-        for (int64_t i = 1; i < n; ++i)
-          a[i] += a[i - 1];
-        return;
-      }
-    std::vector<T> tot((size_t)nt);
-    parallel_chunks(nt, [&](int t) {
-      const int64_t b = n * t / nt, e = n * (t + 1) / nt;
-      T s = 0;
-      for (int64_t i = b; i < e; ++i)
-        {
-          s += a[i];
-          a[i] = s;
-        }
-      tot[(size_t)t] = s;
-    });
-    T run = 0;
-    for (int t = 0; t < nt; ++t)
-      {
-        const T x = tot[(size_t)t];
-        tot[(size_t)t] = run;
-        run += x;
-      }
-    parallel_chunks(nt, [&](int t) {
-      const T off = tot[(size_t)t];
-      if (off == 0)
-        return;
-      const int64_t b = n * t / nt, e = n * (t + 1) / nt;
-      for (int64_t i = b; i < e; ++i)
-        a[i] += off;
-    });
-  }
 
-  // Lattice of a uniform Cartesian box: node n <-> lattice index box_of_local[n] (x fastest), cells in deal.II
-  // vertex order, every lattice cell present exactly once.  false whenever any check fails.
   using Lattice = pfm::LatticeHost;
-
-  bool detect_lattice(const pfm_mesh_desc *m, Lattice &L)
-  {
-    const int dim = m->dim, nv = 1 << dim;
-    if (m->n_hanging > 0)
-      return false;
-    int nc[3] = {m->box_cells[0], m->box_cells[1], dim == 3 ? m->box_cells[2] : 1};
-    if (nc[0] <= 0 || nc[1] <= 0 || nc[2] <= 0)
-      return false;
-    const int NX = nc[0] + 1, NY = nc[1] + 1, NZ = dim == 3 ? nc[2] + 1 : 1;
-    const int64_t nn = (int64_t)NX * NY * NZ;
-    if (nn != m->n_nodes || (int64_t)nc[0] * nc[1] * nc[2] != m->n_cells)
-      return false;
-    const int32_t N = m->n_nodes;
-    double x0[3] = {0, 0, 0}, x1[3] = {0, 0, 0}, h[3] = {1, 1, 1};
-    {
-      const int nt = chunks_for(N, 16384);
-      std::vector<double> lo((size_t)nt * 3), hi((size_t)nt * 3);
-      parallel_chunks(nt, [&](int t) {
-        const int64_t nb = (int64_t)N * t / nt, ne = (int64_t)N * (t + 1) / nt;
-        double a[3], b[3];
-        for (int d = 0; d < dim; ++d)
-          a[d] = b[d] = m->coords[(size_t)nb * dim + d];
-        for (int64_t n = nb; n < ne; ++n)
-          for (int d = 0; d < dim; ++d)
-            {
-              const double x = m->coords[(size_t)n * dim + d];
-              a[d] = std::min(a[d], x);
-              b[d] = std::max(b[d], x);
-            }
-        for (int d = 0; d < dim; ++d)
-          {
-            lo[(size_t)t * 3 + d] = a[d];
-            hi[(size_t)t * 3 + d] = b[d];
-          }
-      });
-      for (int d = 0; d < dim; ++d)
-        {
-          x0[d] = lo[d];
-          x1[d] = hi[d];
-          for (int t = 1; t < nt; ++t)
-            {
-              x0[d] = std::min(x0[d], lo[(size_t)t * 3 + d]);
-              x1[d] = std::max(x1[d], hi[(size_t)t * 3 + d]);
-            }
-          h[d] = (x1[d] - x0[d]) / nc[d];
-          if (!(h[d] > 0))
-            return false;
-        }
-    }
-    pfm::raw_vector<int32_t> local_of_box((size_t)nn); // every entry is written below or the mesh is rejected
-    pfm::raw_vector<int32_t> box_of_local((size_t)N);
-    std::atomic<bool> ok{true};
-    parallel_for(N, [&](int64_t nb, int64_t ne) {
-      for (int64_t n = nb; n < ne; ++n)
-        {
-          int64_t idx[3] = {0, 0, 0};
-          for (int d = 0; d < dim; ++d)
-            {
-              const double t = (m->coords[(size_t)n * dim + d] - x0[d]) / h[d];
-              idx[d] = llround(t);
-              if (std::abs(t - (double)idx[d]) > 1e-9 || idx[d] < 0 || idx[d] > nc[d])
-                {
-                  ok = false;
-                  return;
-                }
-            }
-          box_of_local[n] = (int32_t)(idx[0] + (int64_t)NX * (idx[1] + (int64_t)NY * idx[2]));
-        }
-    });
-    if (!ok)
-      return false;
-    // N = nn nodes on nn positions: a bijection unless two nodes share one (duplicated coordinates, e.g. a slit) -- then
-    // one of the two does not find itself at its position (racing writers of one entry: either value shows the clash)
-    parallel_for(N, [&](int64_t nb, int64_t ne) {
-      for (int64_t n = nb; n < ne; ++n)
-        __atomic_store_n(&local_of_box[(size_t)box_of_local[n]], (int32_t)n, __ATOMIC_RELAXED);
-    });
-    parallel_for(N, [&](int64_t nb, int64_t ne) {
-      for (int64_t n = nb; n < ne; ++n)
-        if (local_of_box[(size_t)box_of_local[n]] != (int32_t)n)
-          {
-            ok = false;
-            return;
-          }
-    });
-    if (!ok)
-      return false;
-    // every lattice cell must be present exactly once, vertices in deal.II order
-    pfm::raw_vector<uint8_t> seen((size_t)m->n_cells);
-    parallel_for(m->n_cells, [&](int64_t b, int64_t e) { std::fill(seen.begin() + b, seen.begin() + e, (uint8_t)0); }, 1 << 20);
-    parallel_for(m->n_cells, [&](int64_t cb, int64_t ce) {
-      for (int64_t cell = cb; cell < ce; ++cell)
-        {
-          const int64_t b0 = box_of_local[m->cell_nodes[cell * nv]];
-          const int64_t i = b0 % NX, j = (b0 / NX) % NY, k = b0 / ((int64_t)NX * NY);
-          if (i >= nc[0] || j >= nc[1] || (dim == 3 && k >= nc[2]))
-            {
-              ok = false;
-              return;
-            }
-          for (int a = 0; a < nv; ++a)
-            {
-              const int64_t b = (i + (a & 1)) + (int64_t)NX * ((j + ((a >> 1) & 1)) + (int64_t)NY * (k + ((a >> 2) & 1)));
-              if (local_of_box[b] != m->cell_nodes[cell * nv + a])
-                {
-                  ok = false;
-                  return;
-                }
-            }
-          seen[i + (int64_t)nc[0] * (j + (int64_t)nc[1] * k)] = 1; // distinct cells write distinct bytes unless duplicated
-        }
-    });
-    if (!ok)
-      return false;
-    parallel_for(m->n_cells, [&](int64_t cb, int64_t ce) {
-      for (int64_t cell = cb; cell < ce; ++cell)
-        if (!seen[cell])
-          {
-            ok = false; // n_cells matches the box, so a missing cell means another one is present twice
-            return;
-          }
-    });
-    if (!ok)
-      return false;
-    L.NX = NX;
-    L.NY = NY;
-    L.NZ = NZ;
-    for (int d = 0; d < 3; ++d)
-      {
-        L.nc[d] = nc[d];
-        L.h[d] = h[d];
-      }
-    L.local_of_box.swap(local_of_box);
-    L.box_of_local.swap(box_of_local);
-    return true;
-  }
-
   // Node graph of a lattice mesh, rows = owned nodes, columns ascending by local node id (the canonical order of the
   // ABI, what a host CSR sorted by local column id has).  Arithmetic instead of the generic cell-incidence build: the
   // neighbours of lattice node (i,j,k) are the lattice offsets that stay inside the local box (every cell of the box
@@ -664,25 +292,6 @@ namespace
       lattice_host_ptr(c, NO, L);
     c->h_nadj.clear();
     c->graph_lazy = true; // rows are materialised by ensure_host_graph
-  }
-
-  // neighbours of owned lattice node n in lattice-offset order; returns their number, mask bit o = offset o exists
-  int lattice_row(const Lattice &L, int dim, int64_t n, int32_t (&q)[27], uint32_t &mask)
-  {
-    const int NX = L.NX, NY = L.NY, NZ = L.NZ, no = dim == 3 ? 27 : 9;
-    const int64_t b = L.box_of_local[n];
-    const int i = (int)(b % NX), j = (int)((b / NX) % NY), k = (int)(b / ((int64_t)NX * NY));
-    int deg = 0;
-    mask = 0;
-    for (int o = 0; o < no; ++o)
-      {
-        const int ii = i + (o % 3) - 1, jj = j + ((o / 3) % 3) - 1, kk = k + (dim == 3 ? (o / 9) - 1 : 0);
-        if (ii < 0 || ii >= NX || jj < 0 || jj >= NY || kk < 0 || kk >= NZ)
-          continue;
-        mask |= 1u << o;
-        q[deg++] = L.local_of_box[ii + (int64_t)NX * (jj + (int64_t)NY * kk)];
-      }
-    return deg;
   }
 
   // the canonical rows (ascending local node id) of a lattice context whose host graph has not been materialised
@@ -1007,219 +616,6 @@ int64_t pfm_ctx::block_nnz(int b) const
 
 namespace
 {
-  // PFM_CTX_TIMING=1: wall time of the phases of pfm_ctx_create on stderr (tuning only)
-
-  // ---- cartesian overlay of a general 2-D mesh (DevView::row_patch ..., pfm_kernels.hip: PATCH) -------------------------
-  // Every cell that is an axis-parallel rectangle belongs to the lattice of its size (a refinement level); a node is REGULAR
-  // when it is owned, neither hanging nor a parent, has exactly four incident cells, all of one level, and none of the nine
-  // lattice nodes around it is hanging -- its row is then the plain 9-point row of that level, completed by one workgroup
-  // of the patch kernel.  Blocks of 8 x 8 cells (7 x 7 nodes owned per block) tile each level; the general family keeps
-  // the cells that touch any other row (reduced colour lists), and skips the regular rows.
-  // host-only part (no context access: it runs on its own thread next to the uploads and the node graph build)
-  struct PatchPlan
-  {
-    std::vector<uint8_t> regular, hang; // per node: row of the patch kernel; hanging or duplicated position
-    pfm::raw_vector<int32_t> blk_cells, blk_nodes;
-    std::vector<int32_t> rows_general;
-    int64_t n_regular = 0;
-    int n_blocks = 0;
-  };
-  // Colour classes of the general cell kernel: cells of one class share no node and are assembled by one launch with plain
-  // read-modify-write (device-scope FP64 atomics run at ~3e10 /s on this chip: the scatter of a 2-D Jacobian took 1.1 of
-  // 1.2 ms).  Greedy in cell order over the cells with subset[cell] != 0 (null: all cells); cells with a hanging vertex go to
-  // the last class, which keeps the atomics.  order: the cells by class, ascending within a class; ptr [n_col + 2].
-  struct Colours
-  {
-    std::vector<long long> ptr;
-    pfm::raw_vector<int32_t> order;
-    bool overflow = false;  // more than 62 classes were needed: such cells sit in the atomic class although no vertex hangs
-    bool cancelled = false; // the caller lost interest (cancel): ptr and order are not filled
-  };
-  // the distinct constraint-resolved nodes of a cell (a vertex that does not hang is its own, a hanging one brings its
-  // parents); returns their number, or max_nodes + 1 when there are more
-  template <class NodeOf>
-  int resolved_nodes(int64_t cell, int nv, NodeOf node_of, const int32_t *hn_index, const int64_t *hn_ptr, const int32_t *hn_parents, int32_t *out,
-                     int max_nodes)
-  {
-    int R = 0;
-    for (int a = 0; a < nv; ++a)
-      {
-        const int32_t A = node_of(cell, a);
-        const int32_t k = hn_index ? hn_index[A] : -1;
-        const int64_t rb = k < 0 ? 0 : hn_ptr[k], re = k < 0 ? 1 : hn_ptr[k + 1];
-        for (int64_t r = rb; r < re; ++r)
-          {
-            const int32_t P = k < 0 ? A : hn_parents[r];
-            bool known = false;
-            for (int t = 0; t < R; ++t)
-              known = known || out[t] == P;
-            if (known)
-              continue;
-            if (R == max_nodes)
-              return max_nodes + 1;
-            out[R++] = P;
-          }
-      }
-    return R;
-  }
-
-  // hn_ptr / hn_parents != nullptr (3-D, round 5): a cell at a hanging vertex is coloured like any other, over its
-  // constraint-resolved nodes -- the cell kernel reduces its element matrix and residual to those nodes before it adds
-  // (K' = C^T K C, DevView::cres), so cells of one class that share no resolved node write disjoint entries and need no
-  // atomics: every class adds in a fixed order and the assembly is bitwise reproducible.  Only a cell with more than 16
-  // resolved nodes (or one that finds no colour) stays in the last class.
-  template <class NodeOf>
-  void greedy_colours(int64_t NC, int nv, int32_t N, NodeOf node_of, const int32_t *hn_index, const uint8_t *subset, const std::atomic<bool> *cancel,
-                      Colours &out, const int64_t *hn_ptr = nullptr, const int32_t *hn_parents = nullptr)
-  {
-    constexpr uint8_t NONE = 255, ATOMIC = 254;
-    pfm::raw_vector<uint8_t> col((size_t)NC);
-    pfm::raw_vector<uint64_t> used((size_t)N);
-    parallel_for(N, [&](int64_t b, int64_t e) { std::fill(used.begin() + b, used.begin() + e, (uint64_t)0); });
-    int n_col = 0;
-    for (int64_t cell = 0; cell < NC; ++cell)
-      {
-        if (subset && !subset[cell])
-          {
-            col[cell] = NONE;
-            continue;
-          }
-        if ((cell & 4095) == 0 && cancel && cancel->load(std::memory_order_relaxed))
-          {
-            out.cancelled = true;
-            return;
-          }
-        uint64_t mask = 0;
-        bool hanging = false;
-        int32_t nd[16];
-        int nn = nv;
-        for (int a = 0; a < nv; ++a)
-          {
-            nd[a] = node_of(cell, a);
-            hanging = hanging || (hn_index && hn_index[nd[a]] >= 0);
-          }
-        bool colourable = !hanging;
-        if (hanging && hn_ptr)
-          {
-            nn = resolved_nodes(cell, nv, node_of, hn_index, hn_ptr, hn_parents, nd, 16);
-            colourable = nn <= 16;
-          }
-        if (colourable)
-          for (int a = 0; a < nn; ++a)
-            mask |= used[nd[a]];
-        int k = 63;
-        if (colourable && ~mask != 0)
-          k = __builtin_ctzll(~mask);
-        if (k < 62)
-          {
-            for (int a = 0; a < nn; ++a)
-              used[nd[a]] |= 1ull << k;
-            n_col = std::max(n_col, k + 1);
-            col[cell] = (uint8_t)k;
-          }
-        else
-          {
-            col[cell] = ATOMIC;
-            out.overflow = out.overflow || !hanging || (hn_ptr && colourable); // a cell that should have had a colour and found none
-          }
-      }
-    // counting sort, chunked over the host threads
-    const int nk = n_col + 1;
-    out.ptr.assign((size_t)n_col + 2, 0);
-    const int nt = chunks_for(NC, 65536);
-    std::vector<long long> hist((size_t)nt * nk, 0);
-    parallel_chunks(nt, [&](int t) {
-      long long *hh = hist.data() + (size_t)t * nk;
-      for (int64_t cell = NC * t / nt; cell < NC * (t + 1) / nt; ++cell)
-        if (col[cell] != NONE)
-          ++hh[col[cell] == ATOMIC ? n_col : col[cell]];
-    });
-    for (int k = 0; k < nk; ++k)
-      {
-        long long at = out.ptr[k];
-        for (int t = 0; t < nt; ++t)
-          {
-            const long long cnt = hist[(size_t)t * nk + k];
-            hist[(size_t)t * nk + k] = at;
-            at += cnt;
-          }
-        out.ptr[(size_t)k + 1] = at;
-      }
-    out.order.resize((size_t)std::max<long long>(out.ptr.back(), 1));
-    out.order[0] = 0;
-    parallel_chunks(nt, [&](int t) {
-      long long *fill = hist.data() + (size_t)t * nk;
-      for (int64_t cell = NC * t / nt; cell < NC * (t + 1) / nt; ++cell)
-        if (col[cell] != NONE)
-          out.order[(size_t)fill[col[cell] == ATOMIC ? n_col : col[cell]]++] = (int32_t)cell;
-    });
-  }
-
-  // Cells of the plain classes that share a constraint-resolved node with a cell at a hanging vertex add atomically as well
-  // (DevView::cell_ring): every row the atomic class touches then only ever receives atomic adds, and the class -- 68
-  // latency-bound waves, 15 % of a Jacobian at 2.7e5 cells -- runs next to the others.  false: no such cell (ring empty).
-  template <class NodeOf>
-  bool ring_cells(int64_t NC, int nv, int32_t N, NodeOf node_of, const int32_t *hn_index, const int64_t *hn_ptr, const int32_t *hn_parents,
-                  std::vector<uint8_t> &ring, bool hanging_coloured = false)
-  {
-    ring.clear();
-    if (!hn_index)
-      return false;
-    pfm::raw_vector<uint8_t> touched((size_t)N), at_hanging((size_t)NC);
-    parallel_for(N, [&](int64_t b, int64_t e) { std::fill(touched.begin() + b, touched.begin() + e, (uint8_t)0); });
-    std::atomic<bool> any_atomic{false}, any_ring{false};
-    parallel_for(NC, [&](int64_t cb, int64_t ce) {
-      bool mine = false;
-      for (int64_t cell = cb; cell < ce; ++cell)
-        {
-          bool hanging = false;
-          for (int a = 0; a < nv; ++a)
-            hanging = hanging || hn_index[node_of(cell, a)] >= 0;
-          if (hanging && hanging_coloured)
-            {
-              // (greedy_colours: such a cell sits in a plain class unless it has more than 16 resolved nodes)
-              int32_t tmp[16];
-              hanging = resolved_nodes(cell, nv, node_of, hn_index, hn_ptr, hn_parents, tmp, 16) > 16;
-            }
-          at_hanging[cell] = hanging ? 1 : 0;
-          if (!hanging)
-            continue;
-          mine = true;
-          for (int a = 0; a < nv; ++a)
-            {
-              const int32_t n = node_of(cell, a);
-              touched[n] = 1; // (bytes; racing writers store the same value)
-              const int32_t k = hn_index[n];
-              if (k >= 0)
-                for (long long j = hn_ptr[k]; j < hn_ptr[k + 1]; ++j)
-                  touched[hn_parents[j]] = 1;
-            }
-        }
-      if (mine)
-        any_atomic = true;
-    });
-    if (!any_atomic)
-      return false;
-    ring.resize((size_t)NC);
-    parallel_for(NC, [&](int64_t cb, int64_t ce) {
-      bool mine = false;
-      for (int64_t cell = cb; cell < ce; ++cell)
-        {
-          bool r = false;
-          if (!at_hanging[cell])
-            for (int a = 0; a < nv; ++a)
-              r = r || touched[node_of(cell, a)] != 0;
-          ring[cell] = r ? 1 : 0;
-          mine = mine || r;
-        }
-      if (mine)
-        any_ring = true;
-    });
-    if (!any_ring)
-      ring.clear();
-    return any_ring;
-  }
-
   // The colour lists of the general family over ALL cells, for a context whose overlay made them unnecessary at pfm_ctx_create
   // (full_colours_lazy): from the device copies of the cell table and the hanging-node index, when that family is first run
   // without the overlay (pfm_ctx_force_path, a stress-split assembly of a 3-D overlay context)
@@ -1253,7 +649,7 @@ namespace
       }
     static_assert(sizeof(long long) == sizeof(int64_t), "hanging row pointers");
     Colours col;
-    greedy_colours(NC, nv, v.n_nodes, [&](int64_t cell, int a) { return conn[(size_t)a * NC + cell]; }, v.hn_index ? hn.data() : nullptr, nullptr, nullptr, col,
+    greedy_colours(NC, nv, v.n_nodes, CellView{conn.data(), 1, NC}, v.hn_index ? hn.data() : nullptr, nullptr, nullptr, col,
                    hp.empty() ? nullptr : reinterpret_cast<const int64_t *>(hp.data()), hp.empty() ? nullptr : hpar.data());
     v.color_cells = dev_upload(c, col.order.data(), col.order.size());
     c->color_ptr.swap(col.ptr);
@@ -1266,415 +662,6 @@ namespace
         c->colour_overflow = true;
       }
     c->full_colours_lazy = false;
-  }
-
-  // indices i of [b, e) with pred(i), ascending (chunked over the host threads)
-  template <class P>
-  std::vector<int32_t> parallel_select(int64_t b, int64_t e, P &&pred)
-  {
-    const int64_t n = e - b;
-    const int nt = chunks_for(n, 16384);
-    std::vector<std::vector<int32_t>> part((size_t)nt);
-    parallel_chunks(nt, [&](int t) {
-      std::vector<int32_t> &out = part[(size_t)t];
-      for (int64_t i = b + n * t / nt; i < b + n * (t + 1) / nt; ++i)
-        if (pred(i))
-          out.push_back((int32_t)i);
-    });
-    if (nt == 1)
-      return std::move(part[0]);
-    size_t total = 0;
-    for (auto &q : part)
-      total += q.size();
-    std::vector<int32_t> out;
-    out.reserve(total);
-    for (auto &q : part)
-      out.insert(out.end(), q.begin(), q.end());
-    return out;
-  }
-
-  // Every loop below runs over cells, nodes or blocks in chunks on the host threads (HostPool): the classification is part of
-  // the context rebuild after every refine_mesh.  Tables that several cells write (the cell of which a node is vertex a, the
-  // node at a lattice position) are filled with compare-and-swap: a second claimant marks the entry instead of racing.
-  PatchPlan plan_patches2d(const pfm_mesh_desc *m, const std::vector<int32_t> &hn_index)
-  {
-    PatchPlan pl;
-    const int32_t N = m->n_nodes, NO = m->n_owned_nodes;
-    const int64_t NC = m->n_cells;
-    if (m->dim != 2 || NC == 0 || Switches::no_patch())
-      return pl;
-    // PFM_CTX_TIMING=1: the phases of this classification on stderr (it runs on a thread of its own)
-    const bool ptime = Switches::ctx_timing();
-    auto pt0 = std::chrono::steady_clock::now();
-    auto pmark = [&](const char *what) {
-      if (!ptime)
-        return;
-      const auto t1 = std::chrono::steady_clock::now();
-      fprintf(stderr, "[pfm_ctx_create]     plan: %-22s %6.2f ms\n", what, std::chrono::duration<double, std::milli>(t1 - pt0).count());
-      pt0 = t1;
-    };
-    const double *X = m->coords;
-    double xmin, ymin, xmax, ymax;
-    {
-      const int nt = chunks_for(N, 16384);
-      std::vector<double> bb((size_t)nt * 4);
-      parallel_chunks(nt, [&](int t) {
-        const int64_t nb = (int64_t)N * t / nt, ne = (int64_t)N * (t + 1) / nt;
-        double a0 = X[2 * nb], a1 = a0, b0 = X[2 * nb + 1], b1 = b0;
-        for (int64_t n = nb; n < ne; ++n)
-          {
-            a0 = std::min(a0, X[2 * n]);
-            a1 = std::max(a1, X[2 * n]);
-            b0 = std::min(b0, X[2 * n + 1]);
-            b1 = std::max(b1, X[2 * n + 1]);
-          }
-        double *q = bb.data() + (size_t)t * 4;
-        q[0] = a0, q[1] = a1, q[2] = b0, q[3] = b1;
-      });
-      xmin = bb[0], xmax = bb[1], ymin = bb[2], ymax = bb[3];
-      for (int t = 1; t < nt; ++t)
-        {
-          xmin = std::min(xmin, bb[(size_t)t * 4]);
-          xmax = std::max(xmax, bb[(size_t)t * 4 + 1]);
-          ymin = std::min(ymin, bb[(size_t)t * 4 + 2]);
-          ymax = std::max(ymax, bb[(size_t)t * 4 + 3]);
-        }
-    }
-    const double tol = 1e-9 * std::max(xmax - xmin, ymax - ymin);
-    pmark("bounds");
-    // level of a cell (by its size), lattice position of its lower-left vertex
-    struct Level
-    {
-      double hx, hy;
-      long long ix0, iy0, ix1, iy1; // cell index range
-    };
-    struct Size
-    {
-      double hx, hy;
-    };
-    // the size of an EXACT axis-parallel rectangle in deal.II's vertex order (the patch kernel takes J = diag(hx, hy));
-    // any other cell stays with the general family
-    auto cell_size = [&](int64_t k, double &hx, double &hy, double &x0, double &y0) {
-      const int32_t *cn = m->cell_nodes + 4 * k;
-      x0 = X[2 * cn[0]], y0 = X[2 * cn[0] + 1];
-      const double x1 = X[2 * cn[1]], y1 = X[2 * cn[1] + 1];
-      const double x2 = X[2 * cn[2]], y2 = X[2 * cn[2] + 1], x3 = X[2 * cn[3]], y3 = X[2 * cn[3] + 1];
-      hx = x1 - x0, hy = y2 - y0;
-      return hx > tol && hy > tol && y1 == y0 && x2 == x0 && x3 == x1 && y3 == y2;
-    };
-    auto same_size = [](const Size &a, double hx, double hy) { return std::fabs(a.hx - hx) <= 1e-9 * hx && std::fabs(a.hy - hy) <= 1e-9 * hy; };
-    const int ntc = chunks_for(NC, 8192);
-    std::vector<Level> levels;
-    {
-      // the sizes that occur, in the order of their first cell: per chunk, then merged in chunk order
-      std::vector<std::vector<Size>> found((size_t)ntc);
-      parallel_chunks(ntc, [&](int t) {
-        std::vector<Size> &mine = found[(size_t)t];
-        for (int64_t k = NC * t / ntc; k < NC * (t + 1) / ntc; ++k)
-          {
-            double hx, hy, x0, y0;
-            if (!cell_size(k, hx, hy, x0, y0))
-              continue;
-            bool known = false;
-            for (const Size &q : mine)
-              known = known || same_size(q, hx, hy);
-            if (!known && mine.size() < 100)
-              mine.push_back(Size{hx, hy});
-          }
-      });
-      for (const auto &mine : found)
-        for (const Size &q : mine)
-          {
-            bool known = false;
-            for (const Level &l : levels)
-              known = known || same_size(Size{l.hx, l.hy}, q.hx, q.hy);
-            if (!known && levels.size() < 100)
-              levels.push_back(Level{q.hx, q.hy, LLONG_MAX, LLONG_MAX, LLONG_MIN, LLONG_MIN});
-          }
-    }
-    if (levels.empty())
-      return pl;
-    const int NL = (int)levels.size();
-    pmark("levels");
-    pfm::raw_vector<int8_t> cell_level((size_t)NC); // (written by the loop below: the pages are first touched by its threads)
-    pfm::raw_vector<int32_t> cix((size_t)NC), ciy((size_t)NC);
-    {
-      std::vector<Level> part((size_t)ntc * NL);
-      std::atomic<bool> too_far{false};
-      parallel_chunks(ntc, [&](int t) {
-        Level *mine = part.data() + (size_t)t * NL;
-        for (int l = 0; l < NL; ++l)
-          mine[l] = Level{0, 0, LLONG_MAX, LLONG_MAX, LLONG_MIN, LLONG_MIN};
-        for (int64_t k = NC * t / ntc; k < NC * (t + 1) / ntc; ++k)
-          {
-            cell_level[k] = -1;
-            double hx, hy, x0, y0;
-            if (!cell_size(k, hx, hy, x0, y0))
-              continue;
-            int L = -1;
-            for (int l = 0; l < NL; ++l)
-              if (same_size(Size{levels[l].hx, levels[l].hy}, hx, hy))
-                L = l;
-            if (L < 0)
-              continue;
-            const double fx = (x0 - xmin) / levels[L].hx, fy = (y0 - ymin) / levels[L].hy;
-            const long long ix = std::llround(fx), iy = std::llround(fy);
-            if (std::fabs(fx - (double)ix) > 1e-6 || std::fabs(fy - (double)iy) > 1e-6)
-              continue; // off the level's lattice
-            if (ix > (1 << 30) || iy > (1 << 30))
-              {
-                too_far = true;
-                continue;
-              }
-            cell_level[k] = (int8_t)L;
-            cix[k] = (int32_t)ix;
-            ciy[k] = (int32_t)iy;
-            Level &lv = mine[L];
-            lv.ix0 = std::min(lv.ix0, ix);
-            lv.iy0 = std::min(lv.iy0, iy);
-            lv.ix1 = std::max(lv.ix1, ix);
-            lv.iy1 = std::max(lv.iy1, iy);
-          }
-      });
-      (void)too_far; // such cells keep level -1: general family
-      for (int t = 0; t < ntc; ++t)
-        for (int l = 0; l < NL; ++l)
-          {
-            const Level &q = part[(size_t)t * NL + l];
-            Level &lv = levels[l];
-            lv.ix0 = std::min(lv.ix0, q.ix0);
-            lv.iy0 = std::min(lv.iy0, q.iy0);
-            lv.ix1 = std::max(lv.ix1, q.ix1);
-            lv.iy1 = std::max(lv.iy1, q.iy1);
-          }
-    }
-    // incident cells per node: inc[4 n + a] = the cell of which n is vertex a (-1 none, -2 two cells claim the corner)
-    pmark("cell levels");
-    pfm::raw_vector<int32_t> inc((size_t)N * 4);
-    parallel_for((int64_t)N * 4, [&](int64_t b, int64_t e) { std::fill(inc.begin() + b, inc.begin() + e, -1); });
-    parallel_for(NC, [&](int64_t cb, int64_t ce) {
-      for (int64_t k = cb; k < ce; ++k)
-        for (int a = 0; a < 4; ++a)
-          {
-            int32_t *slot = &inc[(size_t)m->cell_nodes[4 * k + a] * 4 + a];
-            int32_t expect = -1;
-            if (!__atomic_compare_exchange_n(slot, &expect, (int32_t)k, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED))
-              __atomic_store_n(slot, -2, __ATOMIC_RELAXED);
-          }
-    }, 8192);
-    pfm::raw_vector<uint8_t> is_parent((size_t)N), dup((size_t)N);
-    pfm::raw_vector<int8_t> node_level((size_t)N); // of regular nodes: the common level of their four cells
-    std::vector<uint8_t> regular((size_t)N); // (handed over to the plan)
-    parallel_for(N, [&](int64_t b, int64_t e) {
-      std::fill(is_parent.begin() + b, is_parent.begin() + e, (uint8_t)0);
-      std::fill(dup.begin() + b, dup.begin() + e, (uint8_t)0);
-      std::fill(node_level.begin() + b, node_level.begin() + e, (int8_t)-1);
-      std::fill(regular.begin() + b, regular.begin() + e, (uint8_t)0);
-    });
-    if (m->n_hanging > 0)
-      for (int64_t j = 0; j < m->hn_ptr[m->n_hanging]; ++j)
-        is_parent[m->hn_parents[j]] = 1;
-    // two nodes at one lattice position (the lips of a slit, meshes/unit_slit.inp): neither they nor their neighbours are
-    // regular.  One table per level (node at a lattice position), all in one array.
-    {
-      std::vector<long long> off((size_t)NL + 1, 0), Wn((size_t)NL, 0);
-      for (int L = 0; L < NL; ++L)
-        {
-          const Level &lv = levels[L];
-          long long sz = 0;
-          if (lv.ix0 <= lv.ix1)
-            {
-              const long long W = lv.ix1 - lv.ix0 + 2, Hh = lv.iy1 - lv.iy0 + 2;
-              if ((double)W * (double)Hh <= 4.0e8)
-                {
-                  sz = W * Hh;
-                  Wn[L] = W;
-                }
-            }
-          off[(size_t)L + 1] = off[L] + sz;
-        }
-      pfm::raw_vector<int32_t> node_at((size_t)off[NL]);
-      parallel_for(off[NL], [&](int64_t b, int64_t e) { std::fill(node_at.begin() + b, node_at.begin() + e, -1); });
-      parallel_for(NC, [&](int64_t cb, int64_t ce) {
-        for (int64_t k = cb; k < ce; ++k)
-          {
-            const int L = cell_level[k];
-            if (L < 0 || Wn[L] == 0)
-              continue;
-            const Level &lv = levels[L];
-            for (int a = 0; a < 4; ++a)
-              {
-                const int32_t n = m->cell_nodes[4 * k + a];
-                int32_t *slot = &node_at[(size_t)(off[L] + (ciy[k] - lv.iy0 + (a >> 1)) * Wn[L] + (cix[k] - lv.ix0 + (a & 1)))];
-                int32_t seen = -1;
-                if (!__atomic_compare_exchange_n(slot, &seen, n, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED) && seen != n)
-                  dup[n] = dup[seen] = 1; // (bytes, racing writers store the same value)
-              }
-          }
-      }, 8192);
-    }
-    auto hanging = [&](int32_t n) { return (!hn_index.empty() && hn_index[n] >= 0) || dup[n] != 0; };
-    pmark("incident cells, duplicates");
-    int64_t n_regular = 0;
-    {
-      const int nt = chunks_for(NO, 8192);
-      std::vector<int64_t> cnt((size_t)nt, 0);
-      parallel_chunks(nt, [&](int t) {
-        int64_t mine = 0;
-        for (int64_t n = (int64_t)NO * t / nt; n < (int64_t)NO * (t + 1) / nt; ++n)
-          {
-            if (hanging((int32_t)n) || is_parent[n])
-              continue;
-            const int32_t k0 = inc[(size_t)n * 4 + 0], k1 = inc[(size_t)n * 4 + 1], k2 = inc[(size_t)n * 4 + 2], k3 = inc[(size_t)n * 4 + 3];
-            if (k0 < 0 || k1 < 0 || k2 < 0 || k3 < 0)
-              continue; // not exactly four cells, one at each corner
-            const int8_t L = cell_level[k0];
-            if (L < 0 || cell_level[k1] != L || cell_level[k2] != L || cell_level[k3] != L)
-              continue;
-            bool ok = true;
-            for (const int32_t k : {k0, k1, k2, k3})
-              for (int b = 0; b < 4; ++b)
-                ok = ok && !hanging(m->cell_nodes[4 * k + b]);
-            // the four cells really are the 2 x 2 cells around n on the level's lattice
-            ok = ok && cix[k2] == cix[k3] + 1 && ciy[k2] == ciy[k3] && cix[k1] == cix[k3] && ciy[k1] == ciy[k3] + 1 && cix[k0] == cix[k3] + 1 &&
-                 ciy[k0] == ciy[k3] + 1;
-            if (ok)
-              {
-                regular[n] = 1;
-                node_level[n] = L;
-                ++mine;
-              }
-          }
-        cnt[(size_t)t] = mine;
-      });
-      for (const int64_t q : cnt)
-        n_regular += q;
-    }
-    if (n_regular == 0)
-      return pl;
-    pmark("regular nodes");
-    // blocks: block (bx, by) of a level owns the lattice nodes [7 bx, 7 bx + 6] x [7 by, 7 by + 6] and holds the cells
-    // [7 bx - 1, 7 bx + 6] x [7 by - 1, 7 by + 6]; node (i, j) of the lattice = upper-right vertex of cell (i - 1, j - 1)
-    pfm::raw_vector<int32_t> blk_cells, blk_nodes;
-    for (int L = 0; L < NL; ++L)
-      {
-        const Level &lv = levels[L];
-        if (lv.ix0 > lv.ix1)
-          continue;
-        const long long W = lv.ix1 - lv.ix0 + 1, Hh = lv.iy1 - lv.iy0 + 1;
-        if ((double)W * (double)Hh > 4.0e8)
-          continue; // a level whose bounding box is mostly empty: not worth a dense table
-        pfm::raw_vector<int32_t> at((size_t)(W * Hh));
-        parallel_for(W * Hh, [&](int64_t b, int64_t e) { std::fill(at.begin() + b, at.begin() + e, -1); });
-        parallel_for(NC, [&](int64_t cb, int64_t ce) {
-          for (int64_t k = cb; k < ce; ++k)
-            if (cell_level[k] == (int8_t)L)
-              at[(size_t)((ciy[k] - lv.iy0) * W + (cix[k] - lv.ix0))] = (int32_t)k;
-        });
-        auto cell_at = [&](long long i, long long j) -> int32_t {
-          return (i < lv.ix0 || i > lv.ix1 || j < lv.iy0 || j > lv.iy1) ? -1 : at[(size_t)((j - lv.iy0) * W + (i - lv.ix0))];
-        };
-        auto floordiv = [](long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
-        const long long bx0 = floordiv(lv.ix0, 7), bx1 = floordiv(lv.ix1 + 1, 7), by0 = floordiv(lv.iy0, 7), by1 = floordiv(lv.iy1 + 1, 7);
-        const long long nbx = bx1 - bx0 + 1, nblk = nbx * (by1 - by0 + 1);
-        const int nt = chunks_for(nblk, 64);
-        std::vector<std::vector<int32_t>> pc((size_t)nt), pn((size_t)nt);
-        parallel_chunks(nt, [&](int t) {
-          for (long long q = nblk * t / nt; q < nblk * (t + 1) / nt; ++q)
-            {
-              const long long by = by0 + q / nbx, bx = bx0 + q % nbx;
-              int32_t cells[64], nodes[81];
-              bool any = false;
-              for (int i = 0; i < 81; ++i)
-                nodes[i] = -1;
-              for (int cy = 0; cy < 8; ++cy)
-                for (int cx = 0; cx < 8; ++cx)
-                  {
-                    const int32_t k = cell_at(7 * bx - 1 + cx, 7 * by - 1 + cy);
-                    cells[cy * 8 + cx] = k;
-                    if (k >= 0)
-                      for (int a = 0; a < 4; ++a)
-                        nodes[(cx + (a & 1)) + 9 * (cy + (a >> 1))] = m->cell_nodes[4 * k + a];
-                  }
-              for (int hy = 1; hy <= 7; ++hy)
-                for (int hx = 1; hx <= 7; ++hx)
-                  {
-                    const int32_t n = nodes[hx + 9 * hy];
-                    any = any || (n >= 0 && n < NO && regular[n] && node_level[n] == (int8_t)L);
-                  }
-              if (!any)
-                continue;
-              // a regular node of ANOTHER level may sit at a position of this block (coinciding lattices): it is not ours
-              for (int hy = 1; hy <= 7; ++hy)
-                for (int hx = 1; hx <= 7; ++hx)
-                  {
-                    const int32_t n = nodes[hx + 9 * hy];
-                    if (n >= 0 && n < NO && regular[n] && node_level[n] != (int8_t)L)
-                      nodes[hx + 9 * hy] = -1;
-                  }
-              pc[(size_t)t].insert(pc[(size_t)t].end(), cells, cells + 64);
-              pn[(size_t)t].insert(pn[(size_t)t].end(), nodes, nodes + 81);
-            }
-        });
-        {
-          // the chunks' pieces behind one another, copied by the chunks' threads
-          std::vector<size_t> oc((size_t)nt + 1, blk_cells.size()), on((size_t)nt + 1, blk_nodes.size());
-          for (int t = 0; t < nt; ++t)
-            {
-              oc[(size_t)t + 1] = oc[(size_t)t] + pc[(size_t)t].size();
-              on[(size_t)t + 1] = on[(size_t)t] + pn[(size_t)t].size();
-            }
-          blk_cells.resize(oc[(size_t)nt]);
-          blk_nodes.resize(on[(size_t)nt]);
-          parallel_chunks(nt, [&](int t) {
-            std::copy(pc[(size_t)t].begin(), pc[(size_t)t].end(), blk_cells.begin() + (std::ptrdiff_t)oc[(size_t)t]);
-            std::copy(pn[(size_t)t].begin(), pn[(size_t)t].end(), blk_nodes.begin() + (std::ptrdiff_t)on[(size_t)t]);
-          });
-        }
-      }
-    const int n_blocks = (int)(blk_cells.size() / 64);
-    pmark("blocks");
-    if (n_blocks == 0)
-      return pl;
-    // only the rows some block really writes are the patch kernel's (a level without a table above keeps its rows general)
-    {
-      std::vector<uint8_t> covered((size_t)N);
-      parallel_for(N, [&](int64_t b, int64_t e) { std::fill(covered.begin() + b, covered.begin() + e, (uint8_t)0); });
-      const int nt = chunks_for(n_blocks, 64);
-      std::vector<int64_t> cnt((size_t)nt, 0);
-      parallel_chunks(nt, [&](int t) {
-        int64_t mine = 0;
-        for (int64_t b = (int64_t)n_blocks * t / nt; b < (int64_t)n_blocks * (t + 1) / nt; ++b)
-          for (int hy = 1; hy <= 7; ++hy)
-            for (int hx = 1; hx <= 7; ++hx)
-              {
-                const int32_t n = blk_nodes[(size_t)b * 81 + hx + 9 * hy];
-                if (n >= 0 && n < NO && regular[n] && !__atomic_exchange_n(&covered[n], (uint8_t)1, __ATOMIC_RELAXED))
-                  ++mine;
-              }
-        cnt[(size_t)t] = mine;
-      });
-      n_regular = 0;
-      for (const int64_t q : cnt)
-        n_regular += q;
-      regular.swap(covered);
-    }
-    // the rows of the general family (zeroed before every Jacobian; the patch kernel stores its rows whole)
-    pmark("covered");
-    std::vector<int32_t> rows_general = parallel_select(0, NO, [&](int64_t n) { return !regular[n]; });
-    pl.hang.resize((size_t)N);
-    parallel_for(N, [&](int64_t nb, int64_t ne) {
-      for (int64_t n = nb; n < ne; ++n)
-        pl.hang[n] = hanging((int32_t)n) ? 1 : 0;
-    });
-    pl.regular.swap(regular);
-    pl.blk_cells.swap(blk_cells);
-    pl.blk_nodes.swap(blk_nodes);
-    pl.rows_general.swap(rows_general);
-    pmark("rows, flags");
-    pl.n_regular = n_regular;
-    pl.n_blocks = n_blocks;
-    return pl;
   }
 
   // context part: reduced colour lists, uploads (after the colour classes and the node graph exist)
@@ -1722,7 +709,7 @@ namespace
     // its colour classes: greedy over these cells alone (the lists over all cells are made when the general family is first
     // run without the overlay, ensure_full_colours)
     Colours red;
-    greedy_colours(NC, 4, N, [&](int64_t cell, int a) { return m->cell_nodes[4 * cell + a]; }, hn_index, need.data(), nullptr, red);
+    greedy_colours(NC, 4, N, CellView{m->cell_nodes, 4, 1}, hn_index, need.data(), nullptr, red);
     if (red.overflow)
       return; // (a node of more than 62 such cells: no overlay, the caller colours all cells)
     c->color_ptr_reduced.swap(red.ptr);
@@ -1779,274 +766,6 @@ namespace
     c->patch_slots_valid = false;
   }
 
-  // ---- cartesian overlay of a general 3-D mesh (round 5) -------------------------------------------------------------------
-  // The same classification as in 2-D (plan_patches2d), with the row-owner kernels of the CARTESIAN family as the "patch
-  // kernel": every cell that is an exact axis-parallel box belongs to the lattice of its size (a refinement level); a node
-  // is REGULAR when it is owned, neither hanging nor a parent, has exactly eight incident cells, all of one level and at
-  // the eight lattice positions around it, and none of the 27 lattice nodes around it is hanging -- its rows are then the
-  // plain 27-point rows of a uniform box of that level.  Per level one lattice (CartView) over the bounding box of its
-  // regular nodes plus a one-node halo: node_at = the node at each lattice point (-1: none of this level), row_at = the
-  // regular nodes.  k_cart_uu3 / k_cart_phi4 / k_cart_residual3 run on it as on a box and write exactly the rows of row_at;
-  // cells that do not exist at a lattice position contribute only to rows that are not regular, i.e. to nothing that is
-  // written.  The general family keeps the cells that touch any other row (reduced colour lists) and skips the regular rows.
-  struct Level3
-  {
-    double h[3] = {0, 0, 0};
-    long long lo[3] = {0, 0, 0}; // lattice position of the box's first node
-    int dims[3] = {0, 0, 0};     // nodes of the box
-    std::vector<int32_t> node_at, row_at;
-    std::vector<double> lam, mu; // per lattice cell (heterogeneous material), else empty
-    int64_t n_rows = 0;
-  };
-  struct PatchPlan3
-  {
-    std::vector<uint8_t> regular, hang;
-    std::vector<int32_t> rows_general;
-    std::vector<Level3> levels;
-    int64_t n_regular = 0;
-  };
-  PatchPlan3 plan_patches3d(const pfm_mesh_desc *m, const std::vector<int32_t> &hn_index)
-  {
-    PatchPlan3 pl;
-    const int32_t N = m->n_nodes, NO = m->n_owned_nodes;
-    const int64_t NC = m->n_cells;
-    if (m->dim != 3 || NC == 0 || Switches::no_patch())
-      return pl;
-    const double *X = m->coords;
-    double xmin[3] = {X[0], X[1], X[2]}, xmax[3] = {X[0], X[1], X[2]};
-    for (int32_t n = 0; n < N; ++n)
-      for (int d = 0; d < 3; ++d)
-        {
-          xmin[d] = std::min(xmin[d], X[3 * (size_t)n + d]);
-          xmax[d] = std::max(xmax[d], X[3 * (size_t)n + d]);
-        }
-    const double tol = 1e-9 * std::max(xmax[0] - xmin[0], std::max(xmax[1] - xmin[1], xmax[2] - xmin[2]));
-    double amax = 0.0;
-    for (int d = 0; d < 3; ++d)
-      amax = std::max(amax, std::max(std::fabs(xmin[d]), std::fabs(xmax[d])));
-    const double geo_tol = 16.0 * 2.220446049250313e-16 * amax;
-    struct Lv
-    {
-      double h[3];
-      long long clo[3] = {LLONG_MAX, LLONG_MAX, LLONG_MAX}, chi[3] = {LLONG_MIN, LLONG_MIN, LLONG_MIN}; // box of its cells' positions
-    };
-    std::vector<Lv> lv;
-    std::vector<int8_t> cell_level((size_t)NC, -1);
-    std::vector<long long> cpos((size_t)NC * 3, 0);
-    for (int64_t k = 0; k < NC; ++k)
-      {
-        const int32_t *cn = m->cell_nodes + 8 * k;
-        const double *p0 = X + 3 * (size_t)cn[0], *p7 = X + 3 * (size_t)cn[7];
-        const double h[3] = {p7[0] - p0[0], p7[1] - p0[1], p7[2] - p0[2]};
-        bool box = h[0] > tol && h[1] > tol && h[2] > tol;
-        // an axis-parallel box in deal.II's vertex order, up to the rounding of the vertex positions (the kernels take
-        // J = diag(h)): the midpoints a refinement creates are means of 2, 4 or 8 parents and agree only to a few ulp
-        // unless the coordinates are dyadic
-        for (int a = 0; a < 8 && box; ++a)
-          {
-            const double *pa = X + 3 * (size_t)cn[a];
-            box = std::fabs(pa[0] - ((a & 1) ? p7[0] : p0[0])) <= geo_tol && std::fabs(pa[1] - ((a & 2) ? p7[1] : p0[1])) <= geo_tol &&
-                  std::fabs(pa[2] - ((a & 4) ? p7[2] : p0[2])) <= geo_tol;
-          }
-        if (!box)
-          continue;
-        int L = -1;
-        for (size_t l = 0; l < lv.size(); ++l)
-          if (std::fabs(lv[l].h[0] - h[0]) <= 1e-9 * h[0] && std::fabs(lv[l].h[1] - h[1]) <= 1e-9 * h[1] && std::fabs(lv[l].h[2] - h[2]) <= 1e-9 * h[2])
-            L = (int)l;
-        if (L < 0)
-          {
-            if (lv.size() >= 100)
-              continue;
-            lv.push_back(Lv{});
-            for (int d = 0; d < 3; ++d)
-              lv.back().h[d] = h[d];
-            L = (int)lv.size() - 1;
-          }
-        bool on = true;
-        for (int d = 0; d < 3; ++d)
-          {
-            const double f = (p0[d] - xmin[d]) / lv[L].h[d];
-            const long long i = std::llround(f);
-            on = on && std::fabs(f - (double)i) <= 1e-6;
-            cpos[3 * (size_t)k + d] = i;
-          }
-        if (on)
-          {
-            cell_level[k] = (int8_t)L;
-            for (int d = 0; d < 3; ++d)
-              {
-                lv[L].clo[d] = std::min(lv[L].clo[d], cpos[3 * (size_t)k + d]);
-                lv[L].chi[d] = std::max(lv[L].chi[d], cpos[3 * (size_t)k + d]);
-              }
-          }
-      }
-    if (lv.empty())
-      return pl;
-    // incident cells per node: count, common level, the 8 cells by the vertex the node is of them
-    std::vector<uint8_t> n_inc((size_t)N, 0), is_parent((size_t)N, 0);
-    std::vector<int8_t> node_level((size_t)N, -2);
-    std::vector<int32_t> inc((size_t)N * 8, -1);
-    for (int64_t k = 0; k < NC; ++k)
-      for (int a = 0; a < 8; ++a)
-        {
-          const int32_t n = m->cell_nodes[8 * k + a];
-          if (n_inc[n] < 255)
-            ++n_inc[n];
-          const int8_t L = cell_level[k];
-          node_level[n] = (node_level[n] == -2) ? L : (node_level[n] == L ? L : (int8_t)-1);
-          inc[(size_t)n * 8 + a] = (inc[(size_t)n * 8 + a] == -1) ? (int32_t)k : -2;
-        }
-    if (m->n_hanging > 0)
-      for (int64_t j = 0; j < m->hn_ptr[m->n_hanging]; ++j)
-        is_parent[m->hn_parents[j]] = 1;
-    auto hanging = [&](int32_t n) { return !hn_index.empty() && hn_index[n] >= 0; };
-    std::vector<uint8_t> regular((size_t)N, 0);
-    std::vector<long long> npos((size_t)N * 3, 0);
-    // Regular: every cell around the node that the level's box has room for exists, is of the node's level and has no
-    // hanging vertex.  A cell position OUTSIDE the box of the level's cells may be missing: the node then lies on a face of the
-    // level lattice -- for a level that reaches the boundary of the domain, on that boundary -- and the row-owner kernels
-    // treat it like a face node of a uniform box (fewer than 27 neighbours, cells from index ranges).
-    for (int32_t n = 0; n < NO; ++n)
-      {
-        if (n_inc[n] == 0 || node_level[n] < 0 || hanging(n) || is_parent[n])
-          continue;
-        const Lv &l = lv[(size_t)node_level[n]];
-        bool ok = true;
-        long long pn[3] = {0, 0, 0};
-        bool have = false;
-        for (int a = 0; a < 8 && !have; ++a)
-          {
-            const int32_t k = inc[(size_t)n * 8 + a];
-            if (k >= 0)
-              {
-                have = true; // the cell of which n is vertex a lies at pn - (a_x, a_y, a_z)
-                pn[0] = cpos[3 * (size_t)k] + (a & 1), pn[1] = cpos[3 * (size_t)k + 1] + ((a >> 1) & 1), pn[2] = cpos[3 * (size_t)k + 2] + (a >> 2);
-              }
-          }
-        ok = have;
-        for (int a = 0; a < 8 && ok; ++a)
-          {
-            const int32_t k = inc[(size_t)n * 8 + a];
-            const long long cp[3] = {pn[0] - (a & 1), pn[1] - ((a >> 1) & 1), pn[2] - (a >> 2)};
-            if (k == -1)
-              {
-                bool outside = false;
-                for (int d = 0; d < 3; ++d)
-                  outside = outside || cp[d] < l.clo[d] || cp[d] > l.chi[d];
-                ok = outside;
-                continue;
-              }
-            ok = k >= 0 && cpos[3 * (size_t)k] == cp[0] && cpos[3 * (size_t)k + 1] == cp[1] && cpos[3 * (size_t)k + 2] == cp[2];
-            for (int b = 0; b < 8 && ok; ++b)
-              ok = !hanging(m->cell_nodes[8 * (size_t)k + b]);
-          }
-        if (ok)
-          {
-            regular[n] = 1;
-            for (int d = 0; d < 3; ++d)
-              npos[3 * (size_t)n + d] = pn[d];
-          }
-      }
-    // per level: the lattice of the box of its cells, the tables
-    const long long max_table = Switches::overlay3_max_table(), min_rows = Switches::overlay3_min_rows();
-    for (size_t L = 0; L < lv.size(); ++L)
-      {
-        long long lo[3] = {LLONG_MAX, LLONG_MAX, LLONG_MAX}, hi[3] = {LLONG_MIN, LLONG_MIN, LLONG_MIN};
-        int64_t cnt = 0;
-        for (int32_t n = 0; n < NO; ++n)
-          if (regular[n] && node_level[n] == (int8_t)L)
-            {
-              ++cnt;
-              for (int d = 0; d < 3; ++d)
-                {
-                  lo[d] = std::min(lo[d], npos[3 * (size_t)n + d]);
-                  hi[d] = std::max(hi[d], npos[3 * (size_t)n + d]);
-                }
-            }
-        for (int d = 0; d < 3 && cnt; ++d) // the lattice of the level: the nodes of the box of its cells
-          {
-            lo[d] = lv[L].clo[d];
-            hi[d] = lv[L].chi[d] + 1;
-          }
-        const double vol = cnt ? (double)(hi[0] - lo[0] + 1) * (double)(hi[1] - lo[1] + 1) * (double)(hi[2] - lo[2] + 1) : 0.0;
-        if (cnt < min_rows || vol > (double)max_table || vol > 64.0 * (double)cnt)
-          {
-            // too few rows, or a box that is mostly empty (a thin refined band): these rows stay with the general family
-            for (int32_t n = 0; n < NO; ++n)
-              if (regular[n] && node_level[n] == (int8_t)L)
-                regular[n] = 0;
-            continue;
-          }
-        Level3 lev;
-        for (int d = 0; d < 3; ++d)
-          {
-            lev.h[d] = lv[L].h[d];
-            lev.lo[d] = lo[d];
-            lev.dims[d] = (int)(hi[d] - lo[d] + 1);
-          }
-        const long long NX = lev.dims[0], NY = lev.dims[1], NZ = lev.dims[2];
-        lev.node_at.assign((size_t)(NX * NY * NZ), -1);
-        lev.row_at.assign((size_t)(NX * NY * NZ), -1);
-        const bool het = m->cell_lambda && m->cell_mu;
-        if (het)
-          {
-            lev.lam.assign((size_t)((NX - 1) * (NY - 1) * (NZ - 1)), 0.0);
-            lev.mu.assign((size_t)((NX - 1) * (NY - 1) * (NZ - 1)), 0.0);
-          }
-        bool clash = false;
-        for (int64_t k = 0; k < NC; ++k)
-          if (cell_level[k] == (int8_t)L)
-            {
-              const long long ci = cpos[3 * (size_t)k] - lev.lo[0], cj = cpos[3 * (size_t)k + 1] - lev.lo[1], ck = cpos[3 * (size_t)k + 2] - lev.lo[2];
-              if (ci < 0 || ci >= NX - 1 || cj < 0 || cj >= NY - 1 || ck < 0 || ck >= NZ - 1)
-                continue;
-              for (int a = 0; a < 8; ++a)
-                {
-                  int32_t &slot = lev.node_at[(size_t)((ci + (a & 1)) + NX * ((cj + ((a >> 1) & 1)) + NY * (ck + (a >> 2))))];
-                  const int32_t n = m->cell_nodes[8 * (size_t)k + a];
-                  if (slot == -1)
-                    slot = n;
-                  else if (slot != n)
-                    clash = true; // two nodes at one lattice position (a slit): not a mesh for this overlay
-                }
-              if (het)
-                {
-                  lev.lam[(size_t)(ci + (NX - 1) * (cj + (NY - 1) * ck))] = m->cell_lambda[k];
-                  lev.mu[(size_t)(ci + (NX - 1) * (cj + (NY - 1) * ck))] = m->cell_mu[k];
-                }
-            }
-        if (clash)
-          {
-            for (int32_t n = 0; n < NO; ++n)
-              if (regular[n] && node_level[n] == (int8_t)L)
-                regular[n] = 0;
-            continue;
-          }
-        for (int32_t n = 0; n < NO; ++n)
-          if (regular[n] && node_level[n] == (int8_t)L)
-            {
-              const long long i = npos[3 * (size_t)n] - lev.lo[0], j = npos[3 * (size_t)n + 1] - lev.lo[1], kk = npos[3 * (size_t)n + 2] - lev.lo[2];
-              lev.row_at[(size_t)(i + NX * (j + NY * kk))] = n;
-              ++lev.n_rows;
-            }
-        pl.levels.push_back(std::move(lev));
-      }
-    if (pl.levels.empty())
-      return pl;
-    for (int32_t n = 0; n < NO; ++n)
-      {
-        pl.n_regular += regular[n];
-        if (!regular[n])
-          pl.rows_general.push_back(n);
-      }
-    pl.hang.assign((size_t)N, 0);
-    for (int32_t n = 0; n < N; ++n)
-      pl.hang[n] = hanging(n) ? 1 : 0;
-    pl.regular.swap(regular);
-    return pl;
-  }
-
   // context part: reduced colour lists of the general family, uploads of the level lattices
   void finish_patches3d(pfm_ctx *c, const pfm_mesh_desc *m, PatchPlan3 &pl, const int32_t *hn_index)
   {
@@ -2070,7 +789,7 @@ namespace
         }
     });
     Colours red; // (see finish_patches2d)
-    greedy_colours(NC, 8, m->n_nodes, [&](int64_t cell, int a) { return m->cell_nodes[8 * cell + a]; }, hn_index, need.data(), nullptr, red,
+    greedy_colours(NC, 8, m->n_nodes, CellView{m->cell_nodes, 8, 1}, hn_index, need.data(), nullptr, red,
                    c->hanging_coloured ? m->hn_ptr : nullptr, c->hanging_coloured ? m->hn_parents : nullptr);
     if (red.overflow)
       return;
@@ -2113,19 +832,6 @@ namespace
     c->overlay3_rows_valid = false;
   }
 
-  struct PhaseClock
-  {
-    const bool on = Switches::ctx_timing();
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    void mark(const char *what)
-    {
-      if (!on)
-        return;
-      const auto t1 = std::chrono::steady_clock::now();
-      fprintf(stderr, "[pfm_ctx_create] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-      t0 = t1;
-    }
-  };
 } // namespace
 
 namespace
@@ -2285,19 +991,8 @@ extern "C"
           upload_thread = std::thread(upload_mesh);
         // ---- hanging table: node -> k
         std::vector<int32_t> hn_index;
-        if (m->n_hanging > 0)
-          {
-            hn_index.assign(N, -1);
-            for (int32_t k = 0; k < m->n_hanging; ++k)
-              {
-                if (m->hn_nodes[k] < 0 || m->hn_nodes[k] >= N)
-                  return fail(c, PFM_ERR_BAD_ARG, "hn_nodes out of range");
-                hn_index[m->hn_nodes[k]] = k;
-              }
-            for (int64_t j = 0; j < m->hn_ptr[m->n_hanging]; ++j)
-              if (m->hn_parents[j] < 0 || m->hn_parents[j] >= N || hn_index[m->hn_parents[j]] >= 0)
-                return fail(c, PFM_ERR_BAD_ARG, "hanging table must be closed (parents unconstrained)");
-          }
+        if (const char *bad = hanging_index(m, hn_index))
+          return fail(c, PFM_ERR_BAD_ARG, bad);
 
         // ---- node graph over the constraint-resolved cells, rows = owned nodes, columns ascending by local node id
         // (ghost nodes, numbered after the owned ones, come last: the order of a host CSR sorted by local column id).
@@ -2316,7 +1011,7 @@ extern "C"
         // (below, on a thread of its own) turns out non-empty: the overlay needs the classes of the few cells it leaves to
         // the general family only (finish_patches2d / 3d), the lists over all cells are then made on first use.
         const int32_t *hn_idx = hn_index.empty() ? nullptr : hn_index.data();
-        auto node_of = [m, nv](int64_t cell, int a) { return m->cell_nodes[cell * nv + a]; };
+        const CellView node_of{m->cell_nodes, nv, 1};
         // PFM_HANGING_COLOURED=1 (read at every pfm_ctx_create): the 3-D cells at hanging vertices in plain colour classes
         // (greedy_colours) instead of the one class with FP64 atomics -- every assembly of such a mesh is then bitwise
         // reproducible; it costs some thirty small launches per assembly (1.1e6-cell overlay mesh: Jacobian 4.45 -> 5.1 ms,
@@ -2335,46 +1030,8 @@ extern "C"
         auto colour_classes = [&]() {
           try
             {
-              if (lattice_ok)
-                {
-                  // (2-D boxes; a 3-D box sorts its lists on the device when asked, below)  parity of the cell's lattice position
-                  const int64_t NX = lattice.NX, NY = lattice.NY;
-                  pfm::raw_vector<uint8_t> col((size_t)NC);
-                  parallel_for(NC, [&](int64_t cb, int64_t ce) {
-                    for (int64_t cell = cb; cell < ce; ++cell)
-                      {
-                        const int64_t b0 = lattice.box_of_local[m->cell_nodes[cell * nv]];
-                        const int64_t i = b0 % NX, j = (b0 / NX) % NY, k = b0 / (NX * NY);
-                        col[cell] = (uint8_t)((i & 1) + 2 * (j & 1) + 4 * (k & 1));
-                      }
-                  });
-                  const int n_col = dim == 3 ? 8 : 4, nk = n_col + 1;
-                  full.ptr.assign((size_t)n_col + 2, 0);
-                  full.order.resize((size_t)std::max<int64_t>(NC, 1));
-                  const int nt = chunks_for(NC, 65536);
-                  std::vector<long long> hist((size_t)nt * nk, 0);
-                  parallel_chunks(nt, [&](int t) {
-                    long long *hh = hist.data() + (size_t)t * nk;
-                    for (int64_t cell = NC * t / nt; cell < NC * (t + 1) / nt; ++cell)
-                      ++hh[col[cell]];
-                  });
-                  for (int k = 0; k < nk; ++k)
-                    {
-                      long long at = full.ptr[k];
-                      for (int t = 0; t < nt; ++t)
-                        {
-                          const long long cnt = hist[(size_t)t * nk + k];
-                          hist[(size_t)t * nk + k] = at;
-                          at += cnt;
-                        }
-                      full.ptr[(size_t)k + 1] = at;
-                    }
-                  parallel_chunks(nt, [&](int t) {
-                    long long *fill = hist.data() + (size_t)t * nk;
-                    for (int64_t cell = NC * t / nt; cell < NC * (t + 1) / nt; ++cell)
-                      full.order[(size_t)fill[col[cell]]++] = (int32_t)cell;
-                  });
-                }
+              if (lattice_ok) // (2-D boxes; a 3-D box sorts its lists on the device when asked, below)
+                lattice_colours(m, lattice, full);
               else
                 greedy_colours(NC, nv, N, node_of, hn_idx, nullptr, &colour_cancel, full, col_hn_ptr, col_hn_parents);
             }
@@ -2517,35 +1174,19 @@ extern "C"
           {
             // slot table of the cells at hanging vertices (DevView::cslot_h), filled next to cslot by launch_build_cslot
             const int MPH = dim == 3 ? 4 : 2;
-            bool fits = true;
-            for (int32_t k = 0; k < m->n_hanging; ++k)
-              fits = fits && m->hn_ptr[k + 1] - m->hn_ptr[k] <= MPH;
-            if (fits)
+            std::vector<int32_t> hcells;
+            pfm::raw_vector<int32_t> hcell;
+            if (hanging_cells(m, hn_idx, MPH, hcells, hcell))
               {
-                const std::vector<int32_t> hcells = parallel_select(0, NC, [&](int64_t cell) {
-                  bool h = false;
-                  for (int a = 0; a < nv; ++a)
-                    h = h || hn_idx[m->cell_nodes[cell * nv + a]] >= 0;
-                  return h;
-                });
-                if (!hcells.empty())
+                v.hcell = dev_upload(c, hcell.data(), hcell.size());
+                v.cslot_h = dev_alloc<uint8_t>(c, hcells.size() * (size_t)(nv * MPH * nv * MPH));
+                if (dim == 3)
                   {
-                    pfm::raw_vector<int32_t> hcell((size_t)NC);
-                    parallel_for(NC, [&](int64_t b, int64_t e) { std::fill(hcell.begin() + b, hcell.begin() + e, -1); });
-                    parallel_for((int64_t)hcells.size(), [&](int64_t b, int64_t e) {
-                      for (int64_t i = b; i < e; ++i)
-                        hcell[(size_t)hcells[(size_t)i]] = (int32_t)i;
-                    });
-                    v.hcell = dev_upload(c, hcell.data(), hcell.size());
-                    v.cslot_h = dev_alloc<uint8_t>(c, hcells.size() * (size_t)(nv * MPH * nv * MPH));
-                    if (dim == 3)
-                      {
-                        v.cres = dev_alloc<uint8_t>(c, hcells.size() * (size_t)pfm::PFM_CRES_BYTES);
-                        c->n_hcells = (int64_t)hcells.size();
-                        // round 6 default: scratch + ordered gather instead of FP64 atomics (ensure_hang_gather, on first use);
-                        // PFM_HANGING_ATOMIC=1 keeps the atomic class, PFM_HANGING_COLOURED=1 the colour classes of round 5
-                        c->hang_gather = !hanging_coloured && !Switches::hanging_atomic();
-                      }
+                    v.cres = dev_alloc<uint8_t>(c, hcells.size() * (size_t)pfm::PFM_CRES_BYTES);
+                    c->n_hcells = (int64_t)hcells.size();
+                    // round 6 default: scratch + ordered gather instead of FP64 atomics (ensure_hang_gather, on first use);
+                    // PFM_HANGING_ATOMIC=1 keeps the atomic class, PFM_HANGING_COLOURED=1 the colour classes of round 5
+                    c->hang_gather = !hanging_coloured && !Switches::hanging_atomic();
                   }
               }
           }

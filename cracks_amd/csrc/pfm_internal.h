@@ -12,6 +12,7 @@
 
 #include "../../include/pfm_assemble.h"
 #include "pfm_kernel_clock.h"
+#include "pfm_mesh_plan.h"
 
 namespace pfm
 {
@@ -144,39 +145,6 @@ namespace pfm
   {
     return cv.tile_sel != 0 && touches_ghost != (cv.tile_sel == 2);
   }
-
-  // host copy of the lattice tables of a uniform box (kept for pfm_pattern_bind)
-  // std::vector whose resize(n) / vector(n) leaves trivially constructible elements uninitialised: tables of 1e7 entries that
-  // are written once by the host threads are not cleared (and their pages not touched) by one thread first
-  template <class T>
-  struct default_init_allocator : std::allocator<T>
-  {
-    template <class U>
-    struct rebind
-    {
-      using other = default_init_allocator<U>;
-    };
-    using std::allocator<T>::allocator;
-    template <class U>
-    void construct(U *p) noexcept(std::is_nothrow_default_constructible<U>::value)
-    {
-      ::new (static_cast<void *>(p)) U;
-    }
-    template <class U, class... A>
-    void construct(U *p, A &&...a)
-    {
-      ::new (static_cast<void *>(p)) U(std::forward<A>(a)...);
-    }
-  };
-  template <class T>
-  using raw_vector = std::vector<T, default_init_allocator<T>>;
-
-  struct LatticeHost
-  {
-    int NX = 0, NY = 0, NZ = 0, nc[3] = {0, 0, 0};
-    double h[3] = {1, 1, 1};
-    raw_vector<int32_t> local_of_box, box_of_local;
-  };
 
   struct HaloPeer
   {

@@ -858,7 +858,7 @@ namespace pfm
           double inv[dim][dim], det;
           if constexpr (PATCH)
             {
-              // the cells of a patch block are exact axis-parallel rectangles (pfm_host.cpp: build_patches2d)
+              // the cells of a patch block are exact axis-parallel rectangles (pfm_mesh_plan.cpp: plan_patches2d)
               inv[0][0] = p_ihx;
               inv[1][1] = p_ihy;
               inv[0][1] = inv[1][0] = 0.0;
@@ -1297,7 +1297,7 @@ namespace pfm
       // =============================== scatter through the constraints (cracks.cc:2439-2464)
       // 3-D cell at a hanging vertex with a record in DevView::cres: its matrix and residual are reduced to its distinct
       // constraint-resolved nodes in LDS and every value is added ONCE (below).  Such cells sit in plain colour classes
-      // (pfm_host.cpp: greedy_colours over the resolved nodes): plain read-modify-write in a fixed order, bitwise reproducible.
+      // (pfm_mesh_plan.cpp: greedy_colours over the resolved nodes): plain read-modify-write in a fixed order, bitwise reproducible.
       const uint8_t *rec = nullptr;
       int RN = 0xff;
       if constexpr (dim == 3 && !PATCH)

@@ -9,7 +9,7 @@ import topology_cases as T
 from cracks_amd import mesh as M
 from gpu_util import linf_scaled
 
-MAX_COLOURS = 62  # greedy_colours (pfm_host.cpp)
+MAX_COLOURS = 62  # greedy_colours (pfm_mesh_plan.cpp)
 MAX_ROW = 254     # pfm_graph.hip
 HG_DEG = 64       # k_hanging_gather (pfm_kernels.hip)
 

@@ -6,7 +6,10 @@ or of plan_cart must leave this listing as it is):
 
 (`PFM_LIB=<other .so>` selects the other build.)  The run makes, at the sizes of the tests and each behind a warm-up of
 itself: 3-D box Jacobian, residual-only, the line-search entry, the halves 1 and 2 of the overlapped assembly, 2-D box
-Jacobian and residual-only, the 3-D overlay Jacobian.  The listing has one line per dispatch in dispatch order: kernel, grid,
+Jacobian and residual-only, the 3-D overlay Jacobian, and -- their colour-class launch sizes and patch-block counts come
+straight from the mesh analysis of pfm_ctx_create (pfm_mesh_plan.cpp) -- the Jacobian and residual-only of the 2-D mesh with
+hanging nodes of tests/sneddon_2d_1.prm (patch overlay) and of the general-family 3-D fan with a hanging node
+(topology_cases.fan3d_30_hanging).  The listing has one line per dispatch in dispatch order: kernel, grid,
 workgroup, LDS bytes, and the queue as the ordinal of its first appearance."""
 import csv
 import glob
@@ -21,17 +24,19 @@ def run():
     import numpy as np
     import torch
 
+    import cases
+    import topology_cases
     from gpu_util import make_context
     from test_gpu_dispatch import BOX2, BOX3, Buffers, _call, _halves, _line_search
     from test_gpu_cart import box_case
     from test_gpu_overlay3d import refined_block_case
 
-    def steps(c, box3=False, box2=False):
+    def steps(c, box3=False, residual=False):
         ctx = make_context(c)
         ctx.state_set_host(c.sol, c.old, c.oldold)
         bufs = Buffers(ctx)
         todo = [lambda: _call(ctx, bufs, False)]
-        if box3 or box2:
+        if box3 or residual:
             todo.append(lambda: _call(ctx, bufs, True))
         if box3:
             todo += [lambda: _line_search(ctx, bufs, c.sol), lambda: _halves(ctx, bufs, False), lambda: _halves(ctx, bufs, True)]
@@ -43,8 +48,10 @@ def run():
 
     steps(box_case(*BOX3, True), box3=True)
     steps(box_case(*BOX3, False), box3=True)
-    steps(box_case(*BOX2, True), box2=True)
+    steps(box_case(*BOX2, True), residual=True)
     steps(refined_block_case((12, 10, 12), True))
+    steps(cases.kat_sneddon_2d(), residual=True)
+    steps(topology_cases.fan3d_30_hanging(), residual=True)
     print("launch_trace: done")
 
 
