@@ -87,6 +87,7 @@ class Context:
                 self._h = C.c_void_p()
             raise PfmError(rc, "pfm_ctx_create", msg)
         self.n_owned_dofs = self.n_owned * (self.dim + 1)
+        self.split_model = capi.SPLIT_REFERENCE  # what set_split_model last set (pfm_set_split_model)
 
     # -- helpers ---------------------------------------------------------------------
     def _check(self, rc: int, where: str):
@@ -107,6 +108,12 @@ class Context:
     # -- C ABI -----------------------------------------------------------------------
     def set_stream(self, stream_handle: int):
         self._check(self.lib.pfm_ctx_set_stream(self._h, C.c_void_p(stream_handle)), "pfm_ctx_set_stream")
+
+    def set_split_model(self, model: int):
+        """0: the reference's closed form (2-D; a 3-D split assembly is refused), 1: the spectral split of 3-D contexts
+        (cracks_amd/split3d.py).  Before set_params."""
+        self._check(self.lib.pfm_set_split_model(self._h, int(model)), "pfm_set_split_model")
+        self.split_model = int(model)
 
     def set_params(self, prm):
         p = prm if isinstance(prm, PfmParams) else PfmParams.from_any(prm)
@@ -562,6 +569,16 @@ class Assembler:
         self.system_pde_residual, self.system_total_residual = z(), z()
         self.system_pde_matrix: List = []
         self.halo = halo
+
+    @property
+    def split_model(self) -> int:
+        """The law of a stress-split assembly (Context.set_split_model): 0 the reference's closed form, 1 the spectral split of
+        3-D meshes.  Set it before set_params."""
+        return self.ctx.split_model
+
+    @split_model.setter
+    def split_model(self, model: int):
+        self.ctx.set_split_model(model)
 
     def allocate_matrix(self):
         if not self.system_pde_matrix:

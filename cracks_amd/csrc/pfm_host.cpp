@@ -1375,7 +1375,8 @@ extern "C"
       return PFM_ERR_BAD_ARG;
     // the reference gates the split on decompose_stress_matrix alone (cracks.cc:2294): decompose_stress_rhs > 0
     // without it multiplies a zero stress_term_minus, i.e. is a plain assembly and valid in 3-D
-    if (c->v.dim == 3 && p->decompose_stress_matrix > 0 && p->timestep_number > 0)
+    // (pfm_set_split_model: PFM_SPLIT_SPECTRAL is the 3-D law of pfm_split3.h)
+    if (c->v.dim == 3 && c->split_model == PFM_SPLIT_REFERENCE && p->decompose_stress_matrix > 0 && p->timestep_number > 0)
       return fail(c, PFM_ERR_UNSUPPORTED,
                   "stress split is 2-D only in the reference (cracks.cc:1685-1690)");
     c->prm = *p;
@@ -1383,6 +1384,16 @@ extern "C"
     c->scal_dirty = true; // the per-launch scalar tables of the cartesian Jacobian kernels follow the parameters
     for (auto &lv : c->levels3)
       lv.scal_dirty = true;
+    return PFM_OK;
+  }
+
+  int pfm_set_split_model(pfm_ctx *c, int model)
+  {
+    if (!c || (model != PFM_SPLIT_REFERENCE && model != PFM_SPLIT_SPECTRAL))
+      return c ? fail(c, PFM_ERR_BAD_ARG, "unknown split model") : PFM_ERR_BAD_ARG;
+    if (model == PFM_SPLIT_SPECTRAL && c->v.dim != 3)
+      return fail(c, PFM_ERR_UNSUPPORTED, "the spectral split is the 3-D law; 2-D keeps the reference's closed form");
+    c->split_model = model;
     return PFM_OK;
   }
 
@@ -2592,7 +2603,7 @@ extern "C"
       }
     if (rc == PFM_OK && c->n_general_cells > 0)
       rc = launch_assemble_general(general_view(c, p, true), c->prm, p.residual_only, d_values, d_res_pde, d_res_tot,
-                                   p.fork_general ? c->side_stream : c->stream, c->color_ptr_reduced, s_atomic);
+                                   p.fork_general ? c->side_stream : c->stream, c->color_ptr_reduced, s_atomic, c->split_model);
     if (s_atomic)
       if (const int rcj = join_from(c, s_atomic, c->stream, c->ev_atomic, "join (atomic class)"))
         return rcj;
@@ -2611,7 +2622,7 @@ extern "C"
       if (const int rcf = fork_side(c, "fork (general family)"))
         return rcf;
     rc = launch_assemble_general(general_view(c, p, true), c->prm, p.residual_only, d_values, d_res_pde, d_res_tot, c->stream, c->color_ptr,
-                                 (p.fork_general && !c->hanging_coloured) ? c->side_stream : nullptr);
+                                 (p.fork_general && !c->hanging_coloured) ? c->side_stream : nullptr, c->split_model);
     if (p.fork_general)
       if (const int rcj = join_from(c, c->side_stream, c->stream, c->ev_join, "join (general family)"))
         return rcj;

@@ -221,7 +221,8 @@ namespace pfm
   // hanging vertices (their rows are distributed to the parents, which other vertices of the same cell may be: atomics)
   int launch_assemble_general(const DevView &v, const pfm_params &p, int residual_only,
                               double *const *d_values, double *d_res_pde, double *d_res_tot,
-                              hipStream_t s, const std::vector<long long> &color_ptr, hipStream_t s_atomic = nullptr);
+                              hipStream_t s, const std::vector<long long> &color_ptr, hipStream_t s_atomic = nullptr,
+                              int split_model = 0 /* PFM_SPLIT_*: pfm_set_split_model */);
   // the patch kernel of the cartesian overlay (2-D): one workgroup per block of DevView::patch_cells
   int launch_assemble_patches(const DevView &v, const pfm_params &p, int residual_only, double *const *d_values, double *d_res_pde,
                               double *d_res_tot, int n_blocks, hipStream_t s);
@@ -279,6 +280,7 @@ struct pfm_ctx
   pfm::DevView v{};
   pfm_params prm{};
   bool have_params = false;
+  int split_model = 0; // PFM_SPLIT_*: pfm_set_split_model
   int n_blocks = 1;
   int kernel_path = 0;
   int force_phase = 0; // pfm_ctx_force_phase (measurement)

@@ -1,8 +1,8 @@
 // pfm_kernels.hip — gfx950 kernels of the assembly hot path, "general" family.
 //
 // General family = any Q1 quad/hex mesh (MappingQ1 geometry per quadrature point), any
-// constraint set (homogeneous lines + hanging nodes), optional 2-D stress split, optional
-// per-cell Lame coefficients.  It is the reference-faithful fallback; uniform Cartesian
+// constraint set (homogeneous lines + hanging nodes), optional 2-D stress split (the reference's closed form) or 3-D
+// spectral split (pfm_split3.h, pfm_set_split_model), optional per-cell Lame coefficients.  It is the reference-faithful fallback; uniform Cartesian
 // meshes (all BASELINE configs) are served by the row-owner kernels in pfm_cart.hip.
 //
 // Work decomposition: one lane <-> (cell, test vertex a).  The lane integrates the
@@ -18,6 +18,7 @@
 // consecutive banks).
 #include "pfm_internal.h"
 #include "pfm_split.h"
+#include "pfm_split3.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -205,7 +206,7 @@ namespace pfm
     // formulas as every other instantiation.
     template <int dim, bool FULL, bool SPLIT, bool ATOMIC, bool RING = false /* DevView::cell_ring is set */, bool PATCH = false,
               bool SCR = false /* 3-D cells at hanging vertices: reduced matrix / residual into DevView::hs_* instead of the outputs */>
-    __global__ __launch_bounds__(256, (dim == 3 && FULL) ? 2 : 1) void k_assemble_general(DevView v, pfm_params prm, Vals vals,
+    __global__ __launch_bounds__(256, (dim == 3 && FULL && !SPLIT) ? 2 : 1) void k_assemble_general(DevView v, pfm_params prm, Vals vals,
                                                               double *res_pde, double *res_tot,
                                                               int residual_only, long long class_begin, long long class_size)
     {
@@ -213,20 +214,25 @@ namespace pfm
       constexpr int PRW = 81 + 3 + 3; // staged row of a node: 3 row components x 9 offsets x 3 column components, residual, placeholders
       __shared__ double s_row[PATCH ? 49 * PRW : 1];
       constexpr int nv = 1 << dim, nc = dim + 1, nq = (dim == 2 ? 9 : 27), dpc = nv * nc;
-      constexpr bool Q3 = dim == 3 && FULL && !SPLIT; // the trial vertices of a hex shared out among four lanes per test vertex
+      constexpr bool Q3 = dim == 3 && FULL; // the trial vertices of a hex shared out among four lanes per test vertex
       constexpr int NPART = Q3 ? 4 : 1, LPC = nv * NPART /* lanes per cell */, NBL = nv / NPART; // trial vertices [B0, B0 + NBL)
       constexpr int CPB = 256 / LPC; // cells per workgroup
-      constexpr int NSLOT = Q3 ? 8 : 4; // q-points per round of the 3-D exchange buffer
+      // q-points per round of the 3-D exchange buffer (split Jacobian: 16 -- lane (a, part) evaluates q-point a + 8 (part & 1) of
+      // the round, the eigen split and its tangent run twice per hex and round instead of four times)
+      constexpr int NSLOT = Q3 ? (SPLIT ? 16 : 8) : 4;
       __shared__ double s_x[dim][nv][CPB];
       __shared__ double s_u[dim][nv][CPB];
       __shared__ double s_p[3][nv][CPB]; // phi, phi_old, phi_oldold
-      constexpr int QST = 50; // doubles per (q-point slot, cell) of the 3-D exchange buffer: 49 used, stride free of bank conflicts for 16-byte reads
+      // doubles per (q-point slot, cell) of the 3-D exchange buffer: 49 used; spectral split (pfm_split3.h): 72 with the tangent,
+      // 44 without.  Strides of an odd number of 16-byte slots: free of bank conflicts for 16-byte reads and writes
+      constexpr int QST = (dim == 3 && SPLIT) ? (FULL ? 74 : 46) : 50;
       // KRED (the class of the 3-D cells at hanging vertices): the scatter first forms C^T K C over the cell's constraint-resolved
       // nodes in LDS (below); the cell's part of the exchange buffer is the head of a region that holds its 8 x 8 x 13 matrix
       constexpr bool KRED = Q3 && !PATCH; // (round 5, second step: in the plain classes as well, see the scatter)
       constexpr int KCMP = 13;                      // Kuu 3 x 3, Kpu 3, Kpp
-      constexpr int KCELL = KRED ? nv * nv * KCMP : NSLOT * QST; // doubles per cell of s_q
-      __shared__ __attribute__((aligned(16))) double s_q[(dim == 3 && !SPLIT) ? (KRED ? CPB * KCELL : NSLOT * CPB * QST) : 2];
+      constexpr int KCELL = KRED ? (nv * nv * KCMP > NSLOT * QST ? nv * nv * KCMP : NSLOT * QST) : NSLOT * QST; // doubles per cell of s_q
+      static_assert(NSLOT * QST <= KCELL, "the exchange slots of a hex are the head of its KCELL region");
+      __shared__ __attribute__((aligned(16))) double s_q[dim == 3 ? (KRED ? CPB * KCELL : NSLOT * CPB * QST) : 2];
       auto sq_at = [&](int slot, int cell_in_wg) { return KRED ? cell_in_wg * KCELL + slot * QST : (slot * CPB + cell_in_wg) * QST; };
       __shared__ double s_rr[(dim == 3 && !PATCH) ? CPB : 1][nv][nc]; // residual entries of a cell at hanging vertices, by vertex
       __shared__ uint8_t s_icnt[KRED ? CPB : 1][16], s_ia[KRED ? CPB : 1][16][8];
@@ -596,7 +602,7 @@ namespace pfm
                 }
             }
         }
-      else if constexpr (dim == 3 && !SPLIT)
+      else if constexpr (dim == 3)
         {
           // ======================= 3-D: the q-point states are shared out among the lanes of the cell (as in the 2-D split
           // form above, through LDS instead of DPP: a hex has 8 lanes, 49 numbers per q-point).  MappingQ1, the shape
@@ -607,10 +613,19 @@ namespace pfm
           // rows need of it; then the cell's lanes go through the round's q-points together (phase B), each adding to the
           // rows of its own vertex (and, Jacobian, its own two trial vertices).  A cell's lanes sit in one wave and the LDS
           // executes a wave's instructions in order: no barrier between the phases.
+          // SPLIT (spectral split, pfm_split3.h): the same arrangement; phase A adds the eigen split of the q-point and, Jacobian,
+          // its symmetric 6 x 6 tangent, phase B forms the rows as B_a^T D B_b.  The slot is larger (QST above) and the Jacobian
+          // form runs 16 slots per round: phase A, now most of the work, is repeated by two lanes per q-point instead of four.
+          // It is bound to one workgroup per CU (launch bounds): 256 registers and 60 accumulation registers, no scratch.
           constexpr double GX0 = 0.5 - 0.5 * 0.7745966692414834, GX2 = 0.5 + 0.5 * 0.7745966692414834; // make_ref_tables
           constexpr double GW0 = 5.0 / 18.0, GW1 = 8.0 / 18.0;
           // slot layout (doubles): vertex v at 4 v: grad N_v (3), N_v;  32..: the scalars below;  stride QST
           constexpr int O_GW = 32 /* g JxW, c_pu */, O_CDIV = 34 /* c_div, c_pp */, O_CGG = 36 /* c_gg, c_pen */, O_SP = 38 /* sigma+ (6) */, O_RP = 44 /* r_p, r_phi */, O_GPF = 46 /* grad phi (3) */;
+          // SPLIT: the combined residual stress instead of sigma+, the 21 entries of the symmetric 6 x 6 tangent and what the
+          // (phi,u) rows need (Jacobian only: 44 doubles without them)
+          constexpr int O3_S = 32 /* (g sigma+ + d_rhs sigma- - p-term) JxW (6) */, O3_RP = 38 /* r_phi, c_gg */, O3_GPF = 40 /* grad phi (3), c_pp */,
+                        O3_D = 44 /* (g C+ + d_mat C-) JxW, packed upper triangle (21) */, O3_M = 66 /* (phi,u) factors of the six unit directions */;
+          static_assert(!SPLIT || (FULL ? O3_M + 6 : O3_D) <= QST, "slot layout of the split form");
 #pragma unroll 1
           for (int q = 0; q < nq_run; ++q)
             {
@@ -619,7 +634,7 @@ namespace pfm
               if ((q & (NSLOT - 1)) == 0)
                 {
                   // ---------------- phase A: q-point qa of this lane (the idle slots of the last round repeat q-point 26)
-                  const int slot = Q3 ? a : (a & 3);
+                  const int slot = Q3 ? (SPLIT ? a + 8 * (part & 1) : a) : (a & 3);
                   const int qa = min(q + slot, nq - 1);
                   const int qz = (qa * 57) >> 9, qr = qa - 9 * qz, qy = (qr * 11) >> 5, qx = qr - 3 * qy;
                   const double x1 = qx == 0 ? GX0 : (qx == 1 ? 0.5 : GX2), y1 = qy == 0 ? GX0 : (qy == 1 ? 0.5 : GX2),
@@ -674,7 +689,7 @@ namespace pfm
                   inv[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
                   const double JxW = det * wq;
                   double *const o = s_q + sq_at(slot, cl);
-                  const bool writer = Q3 ? part == 0 : a < 4;
+                  const bool writer = Q3 ? (SPLIT ? part < 2 : part == 0) : a < 4;
                   double gu[3][3], gpf[3] = {0.0, 0.0, 0.0}, pf = 0.0, pfo = 0.0, pfoo = 0.0;
 #pragma unroll
                   for (int i = 0; i < 3; ++i)
@@ -733,6 +748,73 @@ namespace pfm
                         E[i][k] = 0.5 * (gu[i][k] + gu[k][i]);
                       trE += E[i][i];
                     }
+                  if constexpr (SPLIT)
+                    {
+                      // spectral split (pfm_split3.h; PFM_SPLIT_SPECTRAL): the eigen split of this q-point and, Jacobian, its
+                      // tangent.  Voigt order 00, 11, 22, 01, 02, 12; the statements of cracks.cc:2294-2432 with
+                      // sigma+-_LinU = C+- : E_LinU put in, g(phi), decompose_stress_* and JxW folded in here
+                      const double Ev[6] = {E[0][0], E[1][1], E[2][2], E[0][1], E[0][2], E[1][2]};
+                      split3::Split3 S;
+                      split3::split_strain<FULL>(Ev, S);
+                      double spv[6], smv[6];
+                      split3::split_stress3(Ev, S, lam, mu, spv, smv);
+                      double spE = 0.0; // scalar_product(stress_term_plus, E)
+#pragma unroll
+                      for (int r = 0; r < 6; ++r)
+                        spE += spv[r] * (r < 3 ? Ev[r] : 2.0 * Ev[r]);
+                      if (writer)
+                        {
+                          const double iso = aB1 * p * pfx * pfx;
+                          double Sr[6]; // (g sigma+ + decompose_stress_rhs sigma- - (alpha - 1) p pfx^2 I) JxW, cracks.cc:2393-2410
+#pragma unroll
+                          for (int r = 0; r < 6; ++r)
+                            Sr[r] = (g * spv[r] + d_rhs * smv[r] - (r < 3 ? iso : 0.0)) * JxW;
+                          const double cpp = (((pf - pfo) < 0.0 ? 0.0 : penal_fac) + (1 - kappa) * spE + Gc / eps - 2.0 * aB1 * p * divu) * JxW;
+                          *reinterpret_cast<double2 *>(o + O3_S) = make_double2(Sr[0], Sr[1]);
+                          *reinterpret_cast<double2 *>(o + O3_S + 2) = make_double2(Sr[2], Sr[3]);
+                          *reinterpret_cast<double2 *>(o + O3_S + 4) = make_double2(Sr[4], Sr[5]);
+                          *reinterpret_cast<double2 *>(o + O3_RP) =
+                            make_double2((penal_fac * pf_minus_old_plus + (1.0 - kappa) * spE * pf - Gc / eps * (1.0 - pf) - 2.0 * aB1 * p * pf * divu) * JxW,
+                                         Gc * eps * JxW);
+                          *reinterpret_cast<double2 *>(o + O3_GPF) = make_double2(gpf[0], gpf[1]);
+                          *reinterpret_cast<double2 *>(o + O3_GPF + 2) = make_double2(gpf[2], cpp);
+                          if constexpr (FULL)
+                            {
+                              // D = (g C+ + d_mat C-) JxW straight from P = dE+/dE (split_tangent3 written out: C+ = lambda h(tr E) 1 1^T
+                              // + 2 mu P, C- = lambda (1 - h(tr E)) 1 1^T + 2 mu (I_s - P); the two tangents are never held at once)
+                              const double cII = lam * (g * S.htr + d_mat * (1.0 - S.htr)) * JxW, c2 = 2 * mu * JxW, cdm = c2 * d_mat, cgd = c2 * (g - d_mat);
+                              double D[22];
+#pragma unroll
+                              for (int r = 0; r < 6; ++r)
+#pragma unroll
+                                for (int k = r; k < 6; ++k)
+                                  D[split3::tri(r, k)] = ((r < 3 && k < 3) ? cII : 0.0) + (r == k ? (r < 3 ? cdm : 0.5 * cdm) : 0.0) + cgd * S.Pp[split3::tri(r, k)];
+                              D[21] = 0.0;
+#pragma unroll
+                              for (int e = 0; e < 22; e += 2)
+                                *reinterpret_cast<double2 *>(o + O3_D + e) = make_double2(D[e], D[e + 1]);
+                              // row (a, phi): (1 - kappa) (sigma+_LinU : E + sigma+ : E_LinU) pf N_a - 2 (alpha - 1) p pf tr(E_LinU) N_a
+                              // for the six unit directions (cracks.cc:2357-2376); sigma+_LinU : E is computed, not taken as sigma+
+                              const double cA = (1 - kappa) * pf * JxW, cB = 2.0 * aB1 * p * pf * JxW;
+                              double Mk[6];
+#pragma unroll
+                              for (int k = 0; k < 6; ++k)
+                                {
+                                  double PE = 0.0; // (P : E)_k; sigma+_LinU : E = lambda h(tr E) tr(E) tr(E_LinU) + 2 mu (P : E) : E_LinU
+#pragma unroll
+                                  for (int r = 0; r < 6; ++r)
+                                    PE += S.Pp[split3::sym(r, k)] * (r < 3 ? Ev[r] : 2.0 * Ev[r]);
+                                  const double spLE = (k < 3 ? lam * S.htr * trE : 0.0) + 2 * mu * PE;
+                                  Mk[k] = cA * (spLE + spv[k]) - (k < 3 ? cB : 0.0);
+                                }
+#pragma unroll
+                              for (int k = 0; k < 6; k += 2)
+                                *reinterpret_cast<double2 *>(o + O3_M + k) = make_double2(Mk[k], Mk[k + 1]);
+                            }
+                        }
+                    }
+                  else
+                    {
                   double sp[3][3], spE = 0.0; // sigma+ = lambda tr(E) I + 2 mu E, sigma- = 0 (cracks.cc:2284-2292)
 #pragma unroll
                   for (int i = 0; i < 3; ++i)
@@ -759,6 +841,7 @@ namespace pfm
                       *reinterpret_cast<double2 *>(o + O_GPF) = make_double2(gpf[0], gpf[1]);
                       o[O_GPF + 2] = gpf[2];
                     }
+                    } // !SPLIT
                   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                   __builtin_amdgcn_wave_barrier();
                   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -767,6 +850,67 @@ namespace pfm
               const double *const i = s_q + sq_at(q & (NSLOT - 1), cl);
               const double2 ga01 = *reinterpret_cast<const double2 *>(i + 4 * a), ga2n = *reinterpret_cast<const double2 *>(i + 4 * a + 2);
               const double gNa[3] = {ga01.x, ga01.y, ga2n.x}, Na = ga2n.y;
+              if constexpr (SPLIT)
+                {
+                  // rows B_a^T D B_b: B_b[.][d] are the engineering strains of trial dof (b, d) in Voigt order 00, 11, 22, 01, 02, 12,
+                  // B_b[.][0] = (gb_x, 0, 0, gb_y, gb_z, 0), B_b[.][1] = (0, gb_y, 0, gb_x, 0, gb_z), B_b[.][2] = (0, 0, gb_z, 0, gb_x, gb_y)
+                  const double2 s01 = *reinterpret_cast<const double2 *>(i + O3_S), s23 = *reinterpret_cast<const double2 *>(i + O3_S + 2),
+                                s45 = *reinterpret_cast<const double2 *>(i + O3_S + 4);
+                  const double2 rp = *reinterpret_cast<const double2 *>(i + O3_RP);
+                  const double2 g01 = *reinterpret_cast<const double2 *>(i + O3_GPF), g2c = *reinterpret_cast<const double2 *>(i + O3_GPF + 2);
+                  if constexpr (FULL)
+                    {
+                      double D[22], Mk[6];
+#pragma unroll
+                      for (int e = 0; e < 22; e += 2)
+                        {
+                          const double2 dd = *reinterpret_cast<const double2 *>(i + O3_D + e);
+                          D[e] = dd.x;
+                          D[e + 1] = dd.y;
+                        }
+#pragma unroll
+                      for (int k = 0; k < 6; k += 2)
+                        {
+                          const double2 mm = *reinterpret_cast<const double2 *>(i + O3_M + k);
+                          Mk[k] = Na * mm.x;
+                          Mk[k + 1] = Na * mm.y;
+                        }
+                      double G[3][6]; // G = B_a^T D
+#pragma unroll
+                      for (int k = 0; k < 6; ++k)
+                        {
+                          G[0][k] = gNa[0] * D[split3::sym(0, k)] + gNa[1] * D[split3::sym(3, k)] + gNa[2] * D[split3::sym(4, k)];
+                          G[1][k] = gNa[1] * D[split3::sym(1, k)] + gNa[0] * D[split3::sym(3, k)] + gNa[2] * D[split3::sym(5, k)];
+                          G[2][k] = gNa[2] * D[split3::sym(2, k)] + gNa[0] * D[split3::sym(4, k)] + gNa[1] * D[split3::sym(5, k)];
+                        }
+                      const double cpp = g2c.y * Na, cgg = rp.y;
+#pragma unroll
+                      for (int bb = 0; bb < NBL; ++bb)
+                        {
+                          const int b = B0 + bb;
+                          const double2 gb01 = *reinterpret_cast<const double2 *>(i + 4 * b), gb2n = *reinterpret_cast<const double2 *>(i + 4 * b + 2);
+                          const double bx = gb01.x, by = gb01.y, bz = gb2n.x, Nb = gb2n.y;
+#pragma unroll
+                          for (int c = 0; c < 3; ++c)
+                            {
+                              Kuu[bb][c][0] += G[c][0] * bx + G[c][3] * by + G[c][4] * bz;
+                              Kuu[bb][c][1] += G[c][1] * by + G[c][3] * bx + G[c][5] * bz;
+                              Kuu[bb][c][2] += G[c][2] * bz + G[c][4] * bx + G[c][5] * by;
+                            }
+                          Kpu[bb][0] += Mk[0] * bx + Mk[3] * by + Mk[4] * bz;
+                          Kpu[bb][1] += Mk[1] * by + Mk[3] * bx + Mk[5] * bz;
+                          Kpu[bb][2] += Mk[2] * bz + Mk[4] * bx + Mk[5] * by;
+                          // trial dof (b, phi): rows (a, c < dim) get exactly 0 (cracks.cc:2333-2337)
+                          Kpp[bb] += cpp * Nb + cgg * (bx * gNa[0] + by * gNa[1] + bz * gNa[2]);
+                        }
+                    }
+                  R[0] -= s01.x * gNa[0] + s23.y * gNa[1] + s45.x * gNa[2];
+                  R[1] -= s23.y * gNa[0] + s01.y * gNa[1] + s45.y * gNa[2];
+                  R[2] -= s45.x * gNa[0] + s45.y * gNa[1] + s23.x * gNa[2];
+                  R[3] -= rp.x * Na + rp.y * (g01.x * gNa[0] + g01.y * gNa[1] + g2c.x * gNa[2]);
+                }
+              else
+                {
               const double2 s01 = *reinterpret_cast<const double2 *>(i + O_SP), s23 = *reinterpret_cast<const double2 *>(i + O_SP + 2),
                             s45 = *reinterpret_cast<const double2 *>(i + O_SP + 4);
               const double sp[3][3] = {{s01.x, s01.y, s23.x}, {s01.y, s23.y, s45.x}, {s23.x, s45.x, s45.y}};
@@ -826,6 +970,7 @@ namespace pfm
                   const double gg = g01.x * gNa[0] + g01.y * gNa[1] + g2 * gNa[2];
                   R[3] -= r01.y * Na + cgg_r * gg;
                 }
+                } // !SPLIT
             }
         }
       else
@@ -2503,7 +2648,7 @@ namespace pfm
 
   int launch_assemble_general(const DevView &v, const pfm_params &p, int residual_only,
                               double *const *d_values, double *res_pde, double *res_tot, hipStream_t s,
-                              const std::vector<long long> &color_ptr, hipStream_t s_atomic)
+                              const std::vector<long long> &color_ptr, hipStream_t s_atomic, int split_model)
   {
     int rc = ensure_tables();
     if (rc)
@@ -2517,7 +2662,9 @@ namespace pfm
     const bool split = (p.decompose_stress_matrix > 0 && p.timestep_number > 0);
     // The reference gates the split on decompose_stress_matrix only (cracks.cc:2294); a
     // non-zero decompose_stress_rhs without it multiplies a zero stress_term_minus.
-    if (v.dim == 3 && split)
+    // In 3-D the reference's closed form is refused (it reads the 2 x 2 corner of the strain, cracks.cc:1683-1690); the
+    // spectral model (pfm_set_split_model, pfm_split3.h) has instantiations of its own.
+    if (v.dim == 3 && split && split_model != PFM_SPLIT_SPECTRAL)
       return PFM_ERR_UNSUPPORTED;
     // cells per workgroup: 32 lanes per hex for the 3-D Jacobian (k_assemble_general: Q3), one lane per vertex otherwise
     const int nv = 1 << v.dim, cpb = (v.dim == 3 && !residual_only) ? 8 : 256 / nv;
@@ -2575,10 +2722,18 @@ namespace pfm
         else
           {
             if (residual_only)
-              PFM_LAUNCH(3, false, false);
+              {
+                if (split)
+                  PFM_LAUNCH(3, false, true);
+                else
+                  PFM_LAUNCH(3, false, false);
+              }
             else
               {
-                PFM_LAUNCH(3, true, false);
+                if (split)
+                  PFM_LAUNCH(3, true, true);
+                else
+                  PFM_LAUNCH(3, true, false);
               }
           }
 #undef PFM_LAUNCH

@@ -112,7 +112,7 @@ namespace pfm_glue_detail
     bool flags_shipped_anywhere = false; // some rank of the communicator wants such bytes (decided collectively in rebuild)
     IndexSet relevant_dofs;              // locally relevant dofs: the lines deal.II's AffineConstraints objects can be asked about
     bool state_complete = false; // all three vectors have been scattered into this context once
-    // Opt-in switches of the host (both off: the behaviour of a plain drop-in).
+    // Opt-in switches of the host (all off: the behaviour of a plain drop-in).
     //   pin_host_matrix:   rebuild() page-locks Epetra's value arrays (pfm_host_register) so that the 30 GB of a 3-D Jacobian
     //                      travel as DMA at the link rate.  The arrays belong to system_pde_matrix, which setup_system()
     //                      reinitialises (cracks.cc:1583, 1653): a host that switches this on MUST call before_setup_system()
@@ -128,8 +128,12 @@ namespace pfm_glue_detail
     //                      the call; if it does write them it calls values_written_by_host() first.  The library's
     //                      copy of the host's values goes with the context (release(), before_setup_system()).  If the
     //                      device cannot hold that copy the values travel through pfm_values_to_host as before.
+    //   split_model:       PFM_SPLIT_SPECTRAL gives a 3-D run the tension / compression split the reference only has in 2-D
+    //                      (pfm_set_split_model; forwarded in front of the parameters at every assemble()).  With the default,
+    //                      PFM_SPLIT_REFERENCE, a 3-D run with decompose_stress_matrix > 0 stops at PFM_ERR_UNSUPPORTED.
     bool pin_host_matrix = false;
     bool delta_values = false;
+    int split_model = PFM_SPLIT_REFERENCE;
     bool residual_to_host = true;
     bool holds_host_pins = false;
     int64_t delta_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // of the last assemble() with delta_values (pfm_values_to_host_delta)
@@ -632,6 +636,7 @@ namespace pfm_glue_detail
       p.timestep_number = (int32_t)P.timestep_number;
       p.outer_solver = P.outer_solver == Problem::OuterSolverType::active_set ? PFM_SOLVER_ACTIVE_SET : PFM_SOLVER_SIMPLE_MONOLITHIC;
       p.use_old_timestep_pf = P.use_old_timestep_pf ? 1 : 0;
+      PFM_CALL(ctx, pfm_set_split_model(ctx, split_model));
       PFM_CALL(ctx, pfm_set_params(ctx, &p));
 
       // constraints_update minus the hanging-node lines: one flag byte per local node (cracks.cc:2442-2463)

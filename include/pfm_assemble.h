@@ -104,6 +104,23 @@ int pfm_ctx_set_stream(pfm_ctx *ctx, void *hip_stream);
 
 /* -- inputs set elsewhere but consumed by assemble_system -------- */
 int pfm_set_params(pfm_ctx *ctx, const pfm_params *prm);
+/* Which law a stress-split assembly (decompose_stress_matrix > 0 && timestep_number > 0, cracks.cc:2294) uses.
+ *   PFM_SPLIT_REFERENCE  the reference's closed form (decompose_stress, cracks.cc:1923-2120): 2-D only -- compiled for
+ *                        dim = 3 it reads the 2 x 2 corner of the strain (cracks.cc:1683-1690) -- so pfm_set_params refuses
+ *                        a split assembly of a 3-D context with PFM_ERR_UNSUPPORTED.  Default.
+ *   PFM_SPLIT_SPECTRAL   3-D contexts: the Miehe-type split through the three eigenpairs of the strain (DESIGN.md §2,
+ *                        cracks_amd/split3d.py); never PFM_ERR_NOT_ORTHOGONAL.  A 3-D box or overlay context runs a split
+ *                        assembly through the general family over all cells and returns to its own kernels with the split
+ *                        off (timestep_number = 0).
+ * Model 1 on a 2-D context: PFM_ERR_UNSUPPORTED (2-D keeps the reference's closed form).  An unknown model:
+ * PFM_ERR_BAD_ARG.  Call it before pfm_set_params; back at model 0 with split parameters still set, a 3-D assembly
+ * returns PFM_ERR_UNSUPPORTED. */
+enum
+{
+  PFM_SPLIT_REFERENCE = 0,
+  PFM_SPLIT_SPECTRAL = 1
+};
+int pfm_set_split_model(pfm_ctx *ctx, int model);
 /* constraints_update minus the hanging nodes: one byte per local node, bit c set <=> dof
  * (node, c) has a homogeneous line (Dirichlet from set_newton_bc cracks.cc:2711-2714, or
  * active set cracks.cc:2878-2879).  Call whenever constraints_update is rebuilt. */

@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Time the 3-D spectral stress split (pfm_set_split_model, PFM_SPLIT_SPECTRAL) next to the unsplit general family on the
+same mesh, in one process:
+
+  a --n^3 box (100^3 by default), the general family over all cells (the split assembly of a box context takes it by
+  itself; the unsplit one is sent there with pfm_ctx_force_path(0)), Jacobian and residual-only assembly, the split off
+  and on alternating round by round.
+
+The state is a shear plus noise, so that the strain has eigenvalues of both signs at every q-point (the split does work
+everywhere).  Kernel time from the library's own events around each assembly (pfm_timing_enable: zeroing of the outputs and
+every colour class), median and minimum over --reps assemblies after --warmup.  The two results are compared with each other
+where they must agree: in a second state of pure tension the split assembly reproduces the unsplit one.  One JSON line.
+
+    python tools/bench_split3d.py [--n 100] [--reps 20] [--warmup 3] [--rounds 3]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=100)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3, help="off / on alternations; the medians of all rounds are reported")
+    ap.add_argument("--layout", choices=["blocked", "interleaved"], default="blocked")
+    args = ap.parse_args()
+
+    import torch
+
+    import oracle_api as O
+    from cracks_amd import capi
+    from cracks_amd import mesh as M
+    from cracks_amd.assembler import Assembler
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_split3d needs the GPU: nothing is measured without it")
+    n = args.n
+    mesh = M.box_mesh(3, n, lo=0.0, hi=float(n))
+    blocked = args.layout == "blocked"
+    lay = M.DofLayout(mesh.n_nodes, 3, blocked=blocked)
+    rng = np.random.default_rng(0)
+    shear = 1e-2 * np.array([[0.9, 0.7, -0.3], [0.1, -0.8, 0.5], [0.4, -0.2, 0.2]])
+    noise = rng.uniform(-2e-4, 2e-4, (mesh.n_nodes, 3))
+    phi = rng.uniform(0.3, 0.9, mesh.n_nodes)
+    sol = lay.pack(mesh.coords @ shear.T + noise, phi)
+    tension = lay.pack(1e-2 * mesh.coords + noise, phi)
+    old = lay.pack(np.zeros((mesh.n_nodes, 3)), rng.uniform(0.3, 0.9, mesh.n_nodes))
+    base = dict(mu=80.77, G_c=2.7, alpha_eps=0.5, constant_k=1e-3, pressure=0.05, timestep=1e-3, time=2e-3, old_timestep=1e-3,
+                old_old_timestep=1e-3, timestep_number=1)
+    prm_off = O.make_params(**{"lambda": 121.15}, **base)
+    prm_on = O.make_params(**{"lambda": 121.15}, decompose_stress_rhs=1.0, decompose_stress_matrix=1.0, **base)
+
+    asm = Assembler(mesh, blocked)
+    assert asm.ctx.kernel_path == 1
+    asm.split_model = capi.SPLIT_SPECTRAL
+    asm.set_constraints(np.zeros(mesh.n_nodes, np.uint8))
+    asm.set_vectors(sol, old, old)
+    asm.allocate_matrix()
+
+    def configure(split):
+        # the unsplit assembly through the general family as well (the box's own kernels are not the yardstick here)
+        asm.ctx.force_path(0)
+        asm.set_params(prm_on if split else prm_off)
+
+    def timed(split, residual_only):
+        configure(split)
+        for _ in range(args.warmup):
+            asm.assemble_system(residual_only)
+        asm.synchronize()
+        asm.ctx.timing_enable(True)
+        for _ in range(args.reps):
+            asm.assemble_system(residual_only)
+        asm.synchronize()
+        ts = asm.ctx.kernel_times_ms()
+        asm.ctx.timing_enable(False)
+        assert ts.size == args.reps
+        return ts
+
+    # agreement where the two must agree: pure tension
+    asm.set_vectors(tension, old, old)
+    outs = []
+    for split in (False, True):
+        configure(split)
+        asm.assemble_system(False)
+        asm.synchronize()
+        outs.append(([m.clone() for m in asm.system_pde_matrix], asm.system_pde_residual.clone()))
+    dev = max(float((a - b).abs().max() / max(1.0, float(b.abs().max()))) for a, b in zip(outs[1][0] + [outs[1][1]], outs[0][0] + [outs[0][1]]))
+    del outs
+    asm.set_vectors(sol, old, old)
+
+    rec = {"metric": "split3d_general_family", "cells": int(mesh.n_cells), "layout": args.layout, "reps": args.reps, "rounds": args.rounds,
+           "pure_tension_deviation_from_unsplit": dev}
+    for residual_only, tag in ((False, "jacobian"), (True, "residual_only")):
+        ts = {False: [], True: []}
+        for _ in range(args.rounds):
+            for split in (False, True):
+                ts[split].append(timed(split, residual_only))
+        off, on = np.concatenate(ts[False]), np.concatenate(ts[True])
+        rec[tag] = {"unsplit_ms": float(np.median(off)), "unsplit_min_ms": float(off.min()),
+                    "unsplit_round_medians_ms": [float(np.median(t)) for t in ts[False]],
+                    "split_ms": float(np.median(on)), "split_min_ms": float(on.min()),
+                    "split_round_medians_ms": [float(np.median(t)) for t in ts[True]],
+                    "ratio": float(np.median(on) / np.median(off)),
+                    "unsplit_ms_per_1e6_cells": float(np.median(off) * 1e6 / mesh.n_cells),
+                    "split_ms_per_1e6_cells": float(np.median(on) * 1e6 / mesh.n_cells)}
+    print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()
