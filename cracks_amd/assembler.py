@@ -357,6 +357,40 @@ class Context:
         self._check(self.lib.pfm_residual_norms(self._h, C.c_void_p(res_ptr), out), "pfm_residual_norms")
         return float(out[0]), float(out[1]), float(out[2])
 
+    # ---- include/pfm_newton.h, the line search
+    LS_NORMS = {"l2": capi.LS_NORM_L2, "linf": capi.LS_NORM_LINF}
+    LS_RESTORES = {"saved": capi.LS_RESTORE_SAVED, "subtract": capi.LS_RESTORE_SUBTRACT}
+
+    def line_search_advance(self, sol_ptr: int, update_ptr: int, saved_ptr: int = 0):
+        """``pfm_line_search_advance``: ``saved = solution`` (``saved_ptr`` != 0), ``solution = solution + update``."""
+        self._check(self.lib.pfm_line_search_advance(self._h, C.c_void_p(sol_ptr), C.c_void_p(update_ptr), C.c_void_p(saved_ptr)),
+                    "pfm_line_search_advance")
+
+    def line_search_retreat(self, restore, damping: float, sol_ptr: int, update_ptr: int, saved_ptr: int = 0, advance: bool = False):
+        """``pfm_line_search_retreat``: the restore of a rejected trial (``"saved"``: ``solution = saved``, ``"subtract"``:
+        ``solution = solution - update``), ``update = update * damping`` and, with ``advance``, the next
+        ``solution = solution + update`` in the same pass.  Every operation is rounded on its own."""
+        mode = self.LS_RESTORES.get(restore, restore)
+        self._check(self.lib.pfm_line_search_retreat(self._h, int(mode), float(damping), C.c_void_p(sol_ptr), C.c_void_p(update_ptr),
+                                                     C.c_void_p(saved_ptr), 1 if advance else 0), "pfm_line_search_retreat")
+
+    def line_search_device(self, sol_ptr: int, update_ptr: int, res_pde_ptr: int, res_tot_ptr: int, reference: float, max_steps: int,
+                           damping: float, norm="l2", restore="saved") -> dict:
+        """``pfm_line_search_device``: the whole line search (cracks.cc:2942-2957 / 3048-3062) on device vectors; contexts
+        without halo peers.  Returns ``steps``, ``accepted``, ``norms`` (l2, linf, sum of squares of the last trial's
+        residual_pde) and ``linf_block`` (displacement, phase field)."""
+        o = capi.PfmLineSearchOpts(int(max_steps), int(self.LS_NORMS.get(norm, norm)), int(self.LS_RESTORES.get(restore, restore)), 0,
+                                   float(damping), float(reference))
+        r = capi.PfmLineSearchResult()
+        self._check(self.lib.pfm_line_search_device(self._h, C.byref(o), C.c_void_p(sol_ptr), C.c_void_p(update_ptr),
+                                                    C.c_void_p(res_pde_ptr), C.c_void_p(res_tot_ptr), C.byref(r)), "pfm_line_search_device")
+        return {"steps": int(r.steps), "accepted": bool(r.accepted), "norms": tuple(float(x) for x in r.norms),
+                "linf_block": tuple(float(x) for x in r.linf_block)}
+
+    def project_back_device(self, sol_ptr: int):
+        """``pfm_project_back_device``: project_back_phase_field (cracks.cc:3111-3137) on the owned phase-field dofs."""
+        self._check(self.lib.pfm_project_back_device(self._h, C.c_void_p(sol_ptr)), "pfm_project_back_device")
+
     def functionals(self, cell_owned: Optional[np.ndarray] = None, cell_lambda=None, cell_mu=None):
         """(bulk energy, crack energy, TCV) of the node state in the context (cracks.cc:3553-3701); optional per-cell
         Lame coefficients for the energy (the reference's heterogeneous case uses other ones than the assembly)."""
@@ -634,6 +668,18 @@ class Assembler:
     def assemble_nl_residual(self, solution_only: bool = False):
         """cracks.cc:2507-2512."""
         self.assemble_system(True, solution_only)
+
+    def line_search(self, update, reference: float, max_steps: int, damping: float, norm: str = "l2", restore: str = "saved") -> dict:
+        """The line search of cracks.cc:2942-2957 (``norm="l2", restore="saved"``) / 3048-3062 (``"linf", "subtract"``) in one
+        library call on ``solution``, ``system_pde_residual`` and ``system_total_residual``; ``update`` is a device vector
+        like ``solution``.  ``solution`` and ``update`` are modified in place; the residuals are those of the last trial.
+        Single-rank assemblers (no halo).  Synchronous."""
+        self.ctx.set_stream(self.torch.cuda.current_stream(self.dev).cuda_stream)
+        if self.halo is not None:
+            raise PfmError(1, "Assembler.line_search", "a rank with ghost peers composes the loop from line_search_advance / _retreat")
+        assert update.dtype == self.torch.float64 and update.is_contiguous() and update.numel() == self.solution.numel()
+        return self.ctx.line_search_device(self.solution.data_ptr(), update.data_ptr(), self.system_pde_residual.data_ptr(),
+                                           self.system_total_residual.data_ptr(), reference, max_steps, damping, norm, restore)
 
     def residual_norm(self, total: bool = False) -> float:
         """constraints_update.set_zero(residual); residual.l2_norm() (cracks.cc:2791-2794, 2947-2949) of the last assembly, without

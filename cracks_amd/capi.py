@@ -36,7 +36,10 @@ EXPORTS = [
     "pfm_cod_buckets", "pfm_point_eval",
     "pfm_refine_flags", "pfm_min_cell_diameter", "pfm_state_transfer",
     "pfm_kelly_indicator", "pfm_indicator_select", "pfm_indicator_count", "pfm_refine_flags_mix",
+    "pfm_line_search_advance", "pfm_line_search_retreat", "pfm_line_search_device", "pfm_project_back_device",
 ]
+LS_NORM_L2, LS_NORM_LINF = 0, 1  # pfm_line_search_opts.norm
+LS_RESTORE_SAVED, LS_RESTORE_SUBTRACT = 0, 1  # pfm_line_search_opts.restore
 
 
 class PfmParams(C.Structure):
@@ -62,6 +65,21 @@ class PfmRefineCriteria(C.Structure):
     _fields_ = [
         ("phi_threshold", C.c_double), ("use_box", C.c_int), ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3),
         ("max_level", C.c_int),
+    ]
+
+
+class PfmLineSearchOpts(C.Structure):
+    """include/pfm_newton.h, pfm_line_search_opts"""
+    _fields_ = [
+        ("max_steps", C.c_int32), ("norm", C.c_int32), ("restore", C.c_int32), ("reserved", C.c_int32),
+        ("damping", C.c_double), ("reference", C.c_double),
+    ]
+
+
+class PfmLineSearchResult(C.Structure):
+    """include/pfm_newton.h, pfm_line_search_result"""
+    _fields_ = [
+        ("steps", C.c_int32), ("accepted", C.c_int32), ("norms", C.c_double * 3), ("linf_block", C.c_double * 2),
     ]
 
 
@@ -170,6 +188,10 @@ def load():
     lib.pfm_indicator_count.argtypes = [vp, vp, vp, C.c_double, C.POINTER(i64)]
     lib.pfm_refine_flags_mix.argtypes = [vp, C.POINTER(PfmRefineCriteria), C.c_double, C.c_uint, vp, vp, vp, C.POINTER(i64),
                                          C.POINTER(C.c_double)]
+    lib.pfm_line_search_advance.argtypes = [vp, vp, vp, vp]
+    lib.pfm_line_search_retreat.argtypes = [vp, i32, C.c_double, vp, vp, vp, i32]
+    lib.pfm_line_search_device.argtypes = [vp, C.POINTER(PfmLineSearchOpts), vp, vp, vp, vp, C.POINTER(PfmLineSearchResult)]
+    lib.pfm_project_back_device.argtypes = [vp, vp]
     _LIB = lib
     return lib
 

@@ -371,7 +371,8 @@ struct pfm_ctx
   bool hang_gather = false;       // decided at pfm_ctx_create (PFM_HANGING_ATOMIC=1: off)
   bool hang_gather_ready = false; // tables and scratch exist
   bool colour_overflow = false;   // cells without a hanging vertex sit in the last class (a node of more than 62 cells)
-  pfm::DevBuf buf_norm_partial; // pfm_residual_norms: [2048][2] block partials + the 3 results
+  pfm::DevBuf buf_norm_partial; // pfm_residual_norms: [2048][2] block partials + the 3 results; pfm_line_search_device: [2048][3] + 5
+  pfm::DevBuf buf_ls_saved;     // saved_solution of pfm_line_search_device (SAVED mode): one dof vector, from its first use on
   pfm::DevBuf buf_partial;      // 3-wide reductions of pfm_newton.hip / pfm_postproc.hip: [blocks][3] partials + the 3 results
   pfm::DevBuf buf_cell_owned;   // the owned-cell mask of the entry that runs (upload_mask, pfm_entry.h)
   pfm::DevBuf buf_func_mat;     // per-cell Lame override of pfm_functionals_material

@@ -240,7 +240,6 @@ namespace pfm
 
     // ---- norms of a residual vector with the constrained lines zeroed (constraints_update.set_zero, cracks.cc:2791-2794,
     // 2947-2949): thread <-> owned node, grid-stride over a grid that depends on n_owned only; fixed-order reductions
-    constexpr int NORM_BLOCKS_MAX = 2048;
     template <int dim>
     __global__ __launch_bounds__(256) void k_residual_norms(DevView v, const double *__restrict__ res, double *__restrict__ partial /* [gridDim.x][2] */)
     {

@@ -15,6 +15,10 @@
 
 namespace pfm
 {
+  // largest first-stage grid of the residual norms (pfm_residual_norms and the norm stage of pfm_line_search_device, which
+  // reproduces its sums bit for bit): longer vectors are walked grid-stride
+  constexpr int NORM_BLOCKS_MAX = 2048;
+
   // operators: op(a, b, k) combines two values of component k, init(k) is the neutral element the folds start from
   template <class T>
   struct Sum

@@ -177,6 +177,43 @@ def compute_load_2d(mesh, layout, sol, lam, mu, boundary_id=3, component=0):
 
 
 @dataclass
+class LineSearchOpts:
+    """pfm_line_search_opts without the norm, which is the caller's ``residual_norm_of``."""
+    max_steps: int
+    damping: float
+    reference: float  # newton_residual: a trial is accepted iff its norm < reference (strict; NaN never accepts)
+    restore: str = "saved"  # "saved": solution = saved_solution (cracks.cc:2955); "subtract": solution -= newton_update (3059)
+
+
+def line_search_numpy(residual_norm_of: Callable[[np.ndarray], float], solution: np.ndarray, update: np.ndarray,
+                      opts: LineSearchOpts) -> dict:
+    """The line search of cracks.cc:2942-2957 / 3048-3062, statement for statement -- the host statement of
+    ``pfm_line_search_device`` (include/pfm_newton.h) and the reference of its tests.  ``residual_norm_of(solution)`` stands
+    for ``assemble_nl_residual(); constraints_update.set_zero(residual); residual.l2_norm()`` (or ``linfty_norm()``).
+
+    Every ``+``, ``-`` and ``*`` is one numpy operation on doubles, hence rounded on its own; in ``"subtract"`` mode
+    ``(s + u) - u`` is in general not ``s`` and the drift stays, as in the reference.  The inputs are not modified.  Returns
+    ``steps`` (the reference's line_search_step at loop exit), ``accepted``, ``trial`` (the norm of the LAST trial, also
+    when the search is exhausted and ``solution`` has been restored), ``solution`` and ``update``."""
+    if opts.max_steps < 1 or opts.restore not in ("saved", "subtract") or not np.isfinite(opts.damping):
+        raise ValueError("max_steps >= 1, restore 'saved' or 'subtract' and a finite damping expected")
+    sol = np.array(solution, np.float64)
+    upd = np.array(update, np.float64)
+    saved = sol.copy()
+    step, accepted, trial = 0, False, float("nan")
+    while step < opts.max_steps:
+        sol = sol + upd
+        trial = float(residual_norm_of(sol))
+        if trial < opts.reference:
+            accepted = True
+            break
+        sol = saved.copy() if opts.restore == "saved" else sol - upd
+        upd = upd * opts.damping
+        step += 1
+    return {"steps": step, "accepted": accepted, "trial": trial, "solution": sol, "update": upd}
+
+
+@dataclass
 class ProblemSetup:
     mesh: M.Mesh
     layout: M.DofLayout
@@ -280,16 +317,23 @@ class ActiveSetDriver:
             update = cu.distribute(update)
             saved = self.solution.copy()
             ls = 0
-            while ls < s.max_line_search:
-                self.solution = self.solution + update
-                _, res_pde, res_tot = self._assemble(True, cu)
-                residual_relevant = res_tot.copy()
-                new_newton_residual = float(np.linalg.norm(cu.set_zero(res_pde)))
-                if new_newton_residual < newton_residual:
-                    break
-                self.solution = saved.copy()
-                update = update * s.line_search_damping
-                ls += 1
+            if hasattr(self.asm, "line_search"):
+                # the same loop in one device call (pfm_line_search_device) on the state the Jacobian assembly above left
+                # in the context: parameters, constraint flags, old and old_old solution
+                r = self.asm.line_search(self.solution, update, newton_residual, s.max_line_search, s.line_search_damping)
+                ls, new_newton_residual = r["steps"], r["norms"][0]
+                self.solution, update, residual_relevant = r["solution"], r["update"], r["residual_total"]
+            else:
+                while ls < s.max_line_search:
+                    self.solution = self.solution + update
+                    _, res_pde, res_tot = self._assemble(True, cu)
+                    residual_relevant = res_tot.copy()
+                    new_newton_residual = float(np.linalg.norm(cu.set_zero(res_pde)))
+                    if new_newton_residual < newton_residual:
+                        break
+                    self.solution = saved.copy()
+                    update = update * s.line_search_damping
+                    ls += 1
             row = NewtonRow(newton_step + 1, int(active.sum()), n_cycling, new_newton_residual,
                             new_newton_residual / newton_residual if newton_residual else 0.0, ls, 1)
             rec.newton.append(row)
@@ -359,12 +403,31 @@ class ActiveSetDriver:
 class GpuAssembler:
     """Assembler protocol on top of the HIP library (host-pointer entry point ``pfm_assemble``)."""
 
-    def __init__(self, mesh, layout, cell_lambda=None, cell_mu=None):
+    def __init__(self, mesh, layout, cell_lambda=None, cell_mu=None, device_line_search=False):
         from .assembler import Context
 
         self.mesh, self.layout = mesh, layout
         self.ctx = Context(mesh, layout.blocked, cell_lambda=cell_lambda, cell_mu=cell_mu)
         self._pat = None
+        if device_line_search:  # ActiveSetDriver.newton_active_set takes an assembler's `line_search` when it has one
+            self.line_search = self._line_search_device
+
+    def _line_search_device(self, sol, update, reference, max_steps, damping, norm="l2", restore="saved"):
+        """``pfm_line_search_device`` on device copies of ``sol`` and ``update``, with the parameters, constraint flags and
+        old / old_old solution the last ``assemble`` left in the context.  Returns the result of
+        ``Context.line_search_device`` plus the host arrays ``solution``, ``update``, ``residual_pde``, ``residual_total``."""
+        import torch
+
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to("cuda")
+        d_sol, d_upd = dev(sol), dev(update)
+        d_pde, d_tot = torch.empty_like(d_sol), torch.empty_like(d_sol)
+        torch.cuda.synchronize()  # the context runs on its own stream
+        r = self.ctx.line_search_device(d_sol.data_ptr(), d_upd.data_ptr(), d_pde.data_ptr(), d_tot.data_ptr(), reference, max_steps,
+                                        damping, norm, restore)
+        self.ctx.sync_status()  # (the restore of an exhausted search is asynchronous)
+        for name, t in (("solution", d_sol), ("update", d_upd), ("residual_pde", d_pde), ("residual_total", d_tot)):
+            r[name] = t.cpu().numpy()
+        return r
 
     def _global_matrix(self, values):
         import scipy.sparse as sp

@@ -99,6 +99,9 @@ namespace pfm_glue_detail
     double *d_vec[3] = {nullptr, nullptr, nullptr}, *d_res[2] = {nullptr, nullptr}, *d_val[4] = {nullptr, nullptr, nullptr, nullptr};
     int64_t nnz[4] = {0, 0, 0, 0};
     std::vector<double> h_vec[3], h_res[2];
+    // line_search(): newton_update and, for the stepwise form, saved_solution on the device; host staging
+    double *d_upd = nullptr, *d_saved = nullptr;
+    std::vector<double> h_upd, h_tmp;
     std::vector<uint8_t> flags;
     // cells shipped by other ranks (hanging-node closure) and what is needed to keep their nodes' flags current
     struct ShippedCell
@@ -119,7 +122,9 @@ namespace pfm_glue_detail
     //                      at the top of setup_system() -- rebuild() refuses to run over a context that still holds locks.
     //   residual_to_host:  false = a residual-only assemble() leaves both residual vectors on the device and the caller asks
     //                      for what the line search reads, residual_l2_norm() (cracks.cc:2946-2949): 24 bytes instead of
-    //                      2 x 8 n_dofs per call.
+    //                      2 x 8 n_dofs per call.  P.system_total_residual is then STALE: the next active-set test
+    //                      (cracks.cc:2837-2886) reads it, so that host calls fetch_total_residual() in front of the test
+    //                      (line_search() does it by itself).
     //   delta_values:      assemble() hands the matrix values over with pfm_values_to_host_delta: only the chunks whose bits
     //                      differ from what the last assemble() left in Epetra's arrays cross the link (within a time step
     //                      the displacement rows do not change without the stress split: about a third of the bytes
@@ -131,6 +136,13 @@ namespace pfm_glue_detail
     //   split_model:       PFM_SPLIT_SPECTRAL gives a 3-D run the tension / compression split the reference only has in 2-D
     //                      (pfm_set_split_model; forwarded in front of the parameters at every assemble()).  With the default,
     //                      PFM_SPLIT_REFERENCE, a 3-D run with decompose_stress_matrix > 0 stops at PFM_ERR_UNSUPPORTED.
+    //   line_search_stepwise: line_search() runs the host loop of a rank with ghost peers (vector statements, scatter + halo +
+    //                      assembly, pfm_residual_norms, MPI sum / max) also where pfm_line_search_device would do: the two
+    //                      forms give the same vectors and the same result (tests/test_gpu_glue_line_search.py).
+    //   active_set_on_device: the host evaluates the active set with pfm_active_set_device on d_res[1]; together with
+    //                      residual_to_host == false, line_search() then leaves system_total_residual on the device.
+    bool line_search_stepwise = false;
+    bool active_set_on_device = false;
     bool pin_host_matrix = false;
     bool delta_values = false;
     int split_model = PFM_SPLIT_REFERENCE;
@@ -179,6 +191,12 @@ namespace pfm_glue_detail
           if (p)
             (void)hipFree(p);
           p = nullptr;
+        }
+      for (double **p : {&d_upd, &d_saved})
+        {
+          if (*p)
+            (void)hipFree(*p);
+          *p = nullptr;
         }
     }
 
@@ -447,10 +465,13 @@ namespace pfm_glue_detail
         AssertThrow(hipMalloc((void **)&p, sizeof(double) * std::max<size_t>(nd, 1)) == hipSuccess, ExcMessage("hipMalloc (vectors)"));
       for (double *&p : d_res)
         AssertThrow(hipMalloc((void **)&p, sizeof(double) * std::max<size_t>(nd, 1)) == hipSuccess, ExcMessage("hipMalloc (residuals)"));
+      AssertThrow(hipMalloc((void **)&d_upd, sizeof(double) * std::max<size_t>(nd, 1)) == hipSuccess, ExcMessage("hipMalloc (newton_update)"));
       for (auto &h : h_vec)
         h.assign(nd, 0.0);
       for (auto &h : h_res)
         h.assign(nd, 0.0);
+      h_upd.assign(nd, 0.0);
+      h_tmp.assign(nd, 0.0);
       flags.assign((size_t)n_nodes, 0);
     }
 
@@ -722,6 +743,115 @@ namespace pfm_glue_detail
       return std::sqrt(Utilities::MPI::sum(out[2], P.mpi_com));
     }
 
+    // system_total_residual of the last residual assembly (assemble(residual_only) with residual_to_host == false, or the
+    // last trial of line_search()) from its device copy: one transfer.  The active-set test of cracks.cc:2837-2886 reads it
+    // (residual_relevant); a host that left the residuals on the device calls this before that test -- or evaluates the
+    // test on the device too (pfm_active_set_device on d_res[1]) and sets active_set_on_device.
+    template <class Problem>
+    void fetch_total_residual(Problem &P)
+    {
+      const size_t nd = (size_t)n_owned * (dim + 1);
+      AssertThrow(hipMemcpy(h_res[1].data(), d_res[1], sizeof(double) * nd, hipMemcpyDeviceToHost) == hipSuccess, ExcMessage("D2H"));
+      scatter_owned(h_res[1], P.system_total_residual);
+    }
+
+    // The line search of newton_active_set() (cracks.cc:2942-2957: use_linfty = false, restore_subtract = false) and of
+    // newton_iteration() (cracks.cc:3048-3062: true, true) with the vectors on the device.  To be called behind the
+    // assemble() of the Jacobian (or of a residual): parameters, constraint flags, old_solution and old_old_solution are
+    // those of that call.  P.newton_update is uploaded once; P.solution is the context's copy of that assemble() unless the
+    // host has changed it since (compared on the host, uploaded if so).  A rank without peers makes one library call
+    // (pfm_line_search_device); a rank with peers runs the same loop here, the ghost import between the scatter and the
+    // assembly, the norms summed over the ranks.  Afterwards P.solution comes back with one transfer (the accepted trial, or
+    // the restored solution of an exhausted search) and, through fetch_total_residual(), system_total_residual of the LAST
+    // trial (the reference's residual_relevant = system_total_residual, cracks.cc:2947) -- unless residual_to_host == false
+    // and active_set_on_device is set.  P.newton_update and P.system_pde_residual are not written: the reference reads
+    // neither behind the loop.  Returns steps (line_search_step), accepted, the norms and block maxima of the last trial;
+    // new_newton_residual is result.norms[use_linfty ? 1 : 0].
+    template <class Problem>
+    pfm_line_search_result line_search(Problem &P, const double newton_residual, const unsigned int max_steps, const double damping,
+                                       const bool use_linfty = false, const bool restore_subtract = false)
+    {
+      AssertThrow(ctx && state_complete, ExcMessage("PfmGlue::line_search: call assemble() first"));
+      AssertThrow(max_steps >= 1 && std::isfinite(damping), ExcMessage("PfmGlue::line_search: max_steps >= 1 and a finite damping expected"));
+      const size_t nd = (size_t)n_owned * (dim + 1);
+      gather_owned(P.newton_update, h_upd);
+      AssertThrow(hipMemcpy(d_upd, h_upd.data(), sizeof(double) * nd, hipMemcpyHostToDevice) == hipSuccess, ExcMessage("H2D"));
+      gather_owned(P.solution, h_tmp);
+      if (h_tmp != h_vec[0]) // the host has written the solution since the last assemble()
+        {
+          h_vec[0].swap(h_tmp);
+          AssertThrow(hipMemcpy(d_vec[0], h_vec[0].data(), sizeof(double) * nd, hipMemcpyHostToDevice) == hipSuccess, ExcMessage("H2D"));
+        }
+      const int restore = restore_subtract ? PFM_LS_RESTORE_SUBTRACT : PFM_LS_RESTORE_SAVED;
+      pfm_line_search_result r{};
+      if (!comm && peer_ranks.empty() && !line_search_stepwise)
+        {
+          pfm_line_search_opts o{};
+          o.max_steps = (int32_t)max_steps;
+          o.norm = use_linfty ? PFM_LS_NORM_LINF : PFM_LS_NORM_L2;
+          o.restore = restore;
+          o.damping = damping;
+          o.reference = newton_residual;
+          PFM_CALL(ctx, pfm_line_search_device(ctx, &o, d_vec[0], d_upd, d_res[0], d_res[1], &r));
+        }
+      else
+        {
+          if (!restore_subtract && !d_saved)
+            AssertThrow(hipMalloc((void **)&d_saved, sizeof(double) * std::max<size_t>(nd, 1)) == hipSuccess, ExcMessage("hipMalloc (saved_solution)"));
+          unsigned int step = 0;
+          for (; step < max_steps; ++step)
+            {
+              if (step == 0)
+                PFM_CALL(ctx, pfm_line_search_advance(ctx, d_vec[0], d_upd, restore_subtract ? nullptr : d_saved));
+              else
+                PFM_CALL(ctx, pfm_line_search_retreat(ctx, restore, damping, d_vec[0], d_upd, d_saved, /*advance=*/1));
+              PFM_CALL(ctx, pfm_state_set_solution(ctx, d_vec[0], /*on_device=*/1));
+              if (comm)
+                PFM_CALL(ctx, pfm_halo_exchange(ctx, comm, peer_ranks.data()));
+              PFM_CALL(ctx, pfm_assemble_device(ctx, /*residual_only=*/1, d_val, d_res[0], d_res[1]));
+              double out[3] = {0.0, 0.0, 0.0};
+              PFM_CALL(ctx, pfm_residual_norms(ctx, d_res[0], out));
+              r.norms[2] = Utilities::MPI::sum(out[2], P.mpi_com);
+              r.norms[0] = std::sqrt(r.norms[2]);
+              r.norms[1] = Utilities::MPI::max(out[1], P.mpi_com);
+              if (r.norms[use_linfty ? 1 : 0] < newton_residual) // strict; a NaN never accepts
+                {
+                  r.accepted = 1;
+                  break;
+                }
+            }
+          if (!r.accepted)
+            PFM_CALL(ctx, pfm_line_search_retreat(ctx, restore, damping, d_vec[0], d_upd, d_saved, /*advance=*/0));
+          r.steps = (int32_t)step;
+          // the block maxima of the last trial (cracks.cc:3070-3071): pfm_residual_norms has no such output, so the residual
+          // makes one trip per search (not per trial) and the lines are zeroed here
+          AssertThrow(hipMemcpy(h_res[0].data(), d_res[0], sizeof(double) * nd, hipMemcpyDeviceToHost) == hipSuccess, ExcMessage("D2H"));
+          double mx[2] = {0.0, 0.0};
+          for (int32_t n = 0; n < n_owned; ++n)
+            {
+              const gidx g = phi_dof_of_node[(size_t)n];
+              if (relevant_dofs.is_element(g) && P.constraints_hanging_nodes.is_constrained(g))
+                continue;
+              for (unsigned int comp = 0; comp <= (unsigned int)dim; ++comp)
+                if (!((flags[(size_t)n] >> comp) & 1u))
+                  {
+                    const size_t i = !blocked ? (size_t)n * (dim + 1) + comp
+                                              : (comp < (unsigned int)dim ? (size_t)n * dim + comp : (size_t)n_owned * dim + (size_t)n);
+                    mx[comp < (unsigned int)dim ? 0 : 1] = std::fmax(mx[comp < (unsigned int)dim ? 0 : 1], std::fabs(h_res[0][i]));
+                  }
+            }
+          r.linf_block[0] = Utilities::MPI::max(mx[0], P.mpi_com);
+          r.linf_block[1] = Utilities::MPI::max(mx[1], P.mpi_com);
+        }
+      const int rc = pfm_sync_status(ctx);
+      AssertThrow(rc == PFM_OK, ExcMessage(pfm_last_error(ctx)));
+      AssertThrow(hipMemcpy(h_vec[0].data(), d_vec[0], sizeof(double) * nd, hipMemcpyDeviceToHost) == hipSuccess, ExcMessage("D2H"));
+      scatter_owned(h_vec[0], P.solution);
+      if (residual_to_host || !active_set_on_device)
+        fetch_total_residual(P);
+      return r;
+    }
+
     // global dof of (local node, component)
     // deal.II-knowledge (A) -- verify on a real install: loop over the cells, for every vertex v and component comp
     //   Assert(global_dof_of(P, node_of_phi_dof.at(cell->vertex_dof_index(v, dim)), comp) == cell->vertex_dof_index(v, comp)).
@@ -784,5 +914,10 @@ namespace pfm_glue_detail
 //   assemble_system(bool ro):  pfm_glue.assemble(*this, ro);  if (!direct_solver && !ro) { AMG set-up, cracks.cc:2477-2497 }
 //   line search (cracks.cc:2946-2949) with pfm_glue.residual_to_host = false:
 //                              assemble_nl_residual();  new_newton_residual = pfm_glue.residual_l2_norm(*this);
+//                              (system_total_residual stays on the device: pfm_glue.fetch_total_residual(*this) in front of the
+//                               next active-set test, cracks.cc:2837-2886, which reads it)
+//   the whole loop (cracks.cc:2942-2957 / 3048-3062):
+//                              const auto ls = pfm_glue.line_search(*this, newton_residual, max_no_line_search_steps, line_search_damping);
+//                              line_search_step = ls.steps;  new_newton_residual = ls.norms[0];  residual_relevant = system_total_residual;
 
 #endif // PFM_WITH_DEALII

@@ -265,6 +265,73 @@ int pfm_refine_flags_mix(pfm_ctx *ctx, const pfm_refine_criteria *crit, double t
                          const uint8_t *cell_owned, const uint8_t *cell_level, uint8_t *flags, int64_t *n_flagged,
                          double *threshold);
 
+/* ---- the Newton line search (pfm_linesearch.hip): cracks.cc:2942-2957 (active-set Newton) and 3048-3062 (plain Newton),
+ *   for (step = 0; step < max_steps; ++step)
+ *     { solution += newton_update;  assemble_nl_residual();  set_zero;  norm;  if (norm < newton_residual) break;
+ *       solution = saved_solution  |  solution -= newton_update;   newton_update *= line_search_damping; }
+ * with the vectors on the device.  All vectors are device dof vectors over the owned dofs in the context's layout.
+ *
+ * Rounding is part of the contract: every +, - and * below is ONE IEEE double operation rounded on its own, never a fused
+ * multiply-add, so that the results equal an unfused host statement (numpy, the reference's vector classes) bit for bit and
+ * a host can reproduce `solution` from the step count alone.  In SUBTRACT mode fl(fl(s + u) - u) is in general not s: that
+ * drift is the reference's behaviour (cracks.cc:3059) and is kept. */
+enum { PFM_LS_NORM_L2 = 0, PFM_LS_NORM_LINF = 1 };              /* cracks.cc:2949 / 3054 */
+enum { PFM_LS_RESTORE_SAVED = 0, PFM_LS_RESTORE_SUBTRACT = 1 }; /* solution = saved_solution (2955) / solution -= newton_update (3059) */
+
+typedef struct pfm_line_search_opts {
+  int32_t max_steps;   /* >= 1 */
+  int32_t norm;        /* PFM_LS_NORM_* */
+  int32_t restore;     /* PFM_LS_RESTORE_* */
+  int32_t reserved;    /* 0 */
+  double  damping;     /* finite */
+  double  reference;   /* newton_residual the trial must beat: accepted iff trial < reference (strict; NaN never accepts) */
+} pfm_line_search_opts;
+
+typedef struct pfm_line_search_result {
+  int32_t steps;        /* the reference's line_search_step at loop exit: 0 .. max_steps */
+  int32_t accepted;     /* 1 iff the loop left through the break */
+  double  norms[3];     /* pfm_residual_norms of the LAST trial's residual_pde: l2, linf, sum of squares */
+  double  linf_block[2];/* linf of its displacement dofs / phase-field dofs, lines zeroed (cracks.cc:3070-3071) */
+} pfm_line_search_result;
+
+/* The vector statements, one pass over the vectors each, for any context (a partitioned one too: owned dofs only),
+ * asynchronous on the context's stream.
+ *   advance:            saved = solution (d_saved != NULL);  solution = solution + update
+ *   retreat, SAVED:     solution = saved;              update = update * damping;  advance != 0: solution = saved + update
+ *   retreat, SUBTRACT:  solution = solution - update;  update = update * damping;  advance != 0: solution = solution + update
+ * (the update of the `advance` half is the damped one: the fused pass is the tail of one rejected trial and the head of the
+ * next).  PFM_ERR_BAD_ARG with nothing launched: a NULL solution or update, an unknown restore mode, a non-finite damping,
+ * SAVED mode without d_saved. */
+int pfm_line_search_advance(pfm_ctx *ctx, double *d_solution, const double *d_update, double *d_saved /* NULL or out */);
+int pfm_line_search_retreat(pfm_ctx *ctx, int restore, double damping, double *d_solution, double *d_update,
+                            const double *d_saved /* SAVED mode */, int advance);
+
+/* The whole loop in one call: trial 0 is `advance`, trial k > 0 the fused `retreat(advance = 1)`; every trial then runs
+ * pfm_assemble_nl_residual_device(d_solution, d_residual_pde, d_residual_total) as it is and the norm stage, and the
+ * compare is made on the host (one synchronisation per trial); a rejected last trial is followed by `retreat(advance = 0)`.
+ *   out->norms are bitwise what pfm_residual_norms returns for d_residual_pde (same grid, same reduction order), and
+ *   max(out->linf_block) == out->norms[1] exactly.  The trial value is norms[0] (L2) or norms[1] (LINF); a NaN trial is
+ *   never accepted.
+ * On exhaustion (steps == max_steps, accepted == 0) d_solution is restored per mode and d_update has been damped max_steps
+ * times, but d_residual_pde, d_residual_total, norms and linf_block are those of the LAST TRIAL, not of the restored
+ * solution -- what the reference leaves behind (residual_relevant, new_newton_residual of cracks.cc:2947-2949).
+ * The context's node state is whatever the last pfm_assemble_nl_residual_device left, i.e. the last trial's solution, also
+ * after an exhausted search: a caller that next uses an entry reading the node state (functionals, refinement flags, a
+ * Jacobian through pfm_assemble_device) calls pfm_state_set_solution(d_solution) first, as it must after that entry today.
+ * The saved_solution of SAVED mode is a buffer of the context, allocated at the first use and counted in
+ * pfm_ctx_device_bytes; PFM_ERR_NOMEM with nothing touched if it cannot be allocated.
+ * Contexts without halo peers only (PFM_ERR_BAD_ARG with peers, like pfm_assemble_nl_residual_device: such a rank composes
+ * the loop from the two statements above, its ghost import, the assembly and pfm_residual_norms).
+ * PFM_ERR_BAD_ARG with nothing launched and nothing written: max_steps < 1, an unknown norm or restore, a non-finite
+ * damping, a NULL pointer. */
+int pfm_line_search_device(pfm_ctx *ctx, const pfm_line_search_opts *opts, double *d_solution, double *d_update,
+                           double *d_residual_pde, double *d_residual_total, pfm_line_search_result *out);
+
+/* project_back_phase_field (cracks.cc:3111-3137) on the owned phase-field dofs of a device vector in the context's layout:
+ * x := std::max(0.0, std::min(x, 1.0)), i.e. NaN -> +0.0, -0.0 -> +0.0, -inf -> +0.0, +inf -> 1.0; displacement dofs are
+ * untouched.  Any context; asynchronous on the context's stream. */
+int pfm_project_back_device(pfm_ctx *ctx, double *d_solution);
+
 #ifdef __cplusplus
 }
 #endif
