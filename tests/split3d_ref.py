@@ -1,12 +1,21 @@
 """numpy reference of a 3-D assembly with the spectral stress split: element matrices and residuals with the statements of
-cracks.cc:2248-2432, the law of cracks_amd/split3d.py in the place of decompose_stress, then a plain sum over the cells (no
-constraints, no hanging nodes).  Q1 hexes, MappingQ1, QGauss(3); everything vectorised over (cell, q-point).
+cracks.cc:2248-2432, the law of cracks_amd/split3d.py in the place of decompose_stress, then the distribution of
+cracks.cc:2439-2464.  Q1 hexes, MappingQ1, QGauss(3); everything vectorised over (cell, q-point).
+
+``element_matrices`` returns what a cell hands to the distribution: its 32 x 32 local matrix and 32-vector in cell-dof order
+(vertex, component).  ``distribute_matrix`` / ``distribute_vector`` restate the oracle's functions of the same names
+(oracle/oracle.cpp; AffineConstraints::distribute_local_to_global with zero inhomogeneities) for a closed ConstraintSet:
+constrained rows and columns expanded over their entries with w_R w_C, a placeholder |local(i,i)| -- the mean |diagonal| of
+the local matrix when that is zero -- on the diagonal of a constrained row; the vector overload without placeholders.
+Without a constraint set both are a plain sum over the cells.
 
 ``assemble`` returns the matrix over all dofs of the layout (scipy CSR, entries summed), the residual and the strains at the
-q-points (for the conditions the tests put on their inputs)."""
+q-points (for the conditions the tests put on their inputs); ``assemble_residuals`` the two vectors of the residual-only call.
+tests/test_split3d_ref_cpu.py pins the distribution to the oracle with the split off."""
 import numpy as np
 import scipy.sparse as sp
 
+from cracks_amd import mesh as M
 from cracks_amd.split3d import spectral_split, spectral_tangent
 
 _GX = 0.5 + 0.5 * np.array([-0.7745966692414834, 0.0, 0.7745966692414834])
@@ -35,8 +44,9 @@ def nodal(lay, vec):
     return np.stack([vec[lay.dof(n, c)] for c in range(3)], axis=1), vec[lay.dof(n, 3)]
 
 
-def assemble(mesh, lay, prm, sol, old, oldold, cell_lambda=None, cell_mu=None, split=None, jacobian=True):
-    """split: None = what the parameters say (decompose_stress_matrix > 0 and timestep_number > 0)."""
+def element_matrices(mesh, lay, prm, sol, old, oldold, cell_lambda=None, cell_mu=None, split=None, jacobian=True):
+    """(Ke [cell, 32, 32] or None, Re [cell, 32], E [cell, q, 3, 3]); local index = 4 * vertex + component.
+    split: None = what the parameters say (decompose_stress_matrix > 0 and timestep_number > 0)."""
     assert mesh.dim == 3
     if split is None:
         split = prm.decompose_stress_matrix > 0 and prm.timestep_number > 0
@@ -91,12 +101,9 @@ def assemble(mesh, lay, prm, sol, old, oldold, cell_lambda=None, cell_mu=None, s
     Ru = -np.einsum("cq,cqij,cqaj->cai", JxW, S, G)
     rphi = pen * pf_plus + (1 - kap) * spE * pf - Gc / eps * (1 - pf) - 2 * aB1 * p * pf * divu
     Rp = -(np.einsum("cq,cq,qa->ca", JxW, rphi, N) + Gc * eps * np.einsum("cq,cqd,cqad->ca", JxW, gpf, G))
-    res = np.zeros(lay.n_dofs)
-    for c in range(3):
-        np.add.at(res, lay.dof(cells, c), Ru[:, :, c])
-    np.add.at(res, lay.dof(cells, 3), Rp)
+    Re = np.concatenate([Ru, Rp[:, :, None]], axis=2).reshape(nc, 32)
     if not jacobian:
-        return None, res, E
+        return None, Re, E
     # ---- matrix, cracks.cc:2308-2389: sigma+-_LinU = C+- : E_LinU, E_LinU of trial dof (b, d) = sym(e_d (x) grad N_b)
     if split:
         Cp, Cm = spectral_tangent(E, lam_q, mu_q)
@@ -113,27 +120,105 @@ def assemble(mesh, lay, prm, sol, old, oldold, cell_lambda=None, cell_mu=None, s
     pen_on = np.where((pf - pfo) < 0.0, 0.0, 1.0)  # the shadowed variable of cracks.cc:2311-2315
     cpp = pen * pen_on + (1 - kap) * spE + Gc / eps - 2 * aB1 * p * divu
     Kpp = np.einsum("cq,cq,qa,qb->cab", JxW, cpp, N, N) + Gc * eps * np.einsum("cq,cqad,cqbd->cab", JxW, G, G)
-    rows, cols, vals = [], [], []
-    dofs = [lay.dof(cells, c) for c in range(4)]  # [c, v]
-    for i in range(3):
-        for d in range(3):
-            rows.append(np.broadcast_to(dofs[i][:, :, None], (nc, 8, 8)).ravel())
-            cols.append(np.broadcast_to(dofs[d][:, None, :], (nc, 8, 8)).ravel())
-            vals.append(Kuu[:, :, i, :, d].ravel())
-    for d in range(3):
-        rows.append(np.broadcast_to(dofs[3][:, :, None], (nc, 8, 8)).ravel())
-        cols.append(np.broadcast_to(dofs[d][:, None, :], (nc, 8, 8)).ravel())
-        vals.append(Kpu[:, :, :, d].ravel())
-        # trial phase-field dofs do not enter the displacement rows (cracks.cc:2333-2337): structural zeros of the pattern
-        rows.append(np.broadcast_to(dofs[d][:, :, None], (nc, 8, 8)).ravel())
-        cols.append(np.broadcast_to(dofs[3][:, None, :], (nc, 8, 8)).ravel())
-        vals.append(np.zeros(nc * 64))
-    rows.append(np.broadcast_to(dofs[3][:, :, None], (nc, 8, 8)).ravel())
-    cols.append(np.broadcast_to(dofs[3][:, None, :], (nc, 8, 8)).ravel())
-    vals.append(Kpp.ravel())
+    # trial phase-field dofs do not enter the displacement rows (cracks.cc:2333-2337): zeros
+    Ke = np.zeros((nc, 8, 4, 8, 4))
+    Ke[:, :, :3, :, :3] = Kuu
+    Ke[:, :, 3, :, :3] = Kpu
+    Ke[:, :, 3, :, 3] = Kpp
+    return Ke.reshape(nc, 32, 32), Re, E
+
+
+def _expand(cs, dofs):
+    """local index, global dof and weight of every term of the constraint expansion of a cell's dofs"""
+    loc, glob, w = [], [], []
+    for i, g in enumerate(dofs):
+        if cs.flag[g]:
+            for k in range(cs.ptr[g], cs.ptr[g + 1]):
+                loc.append(i), glob.append(int(cs.col[k])), w.append(float(cs.w[k]))
+        else:
+            loc.append(i), glob.append(int(g)), w.append(1.0)
+    return np.asarray(loc, np.int64), np.asarray(glob, np.int64), np.asarray(w)
+
+
+def _touched(cs, cell_dofs):
+    """cells with a constrained dof; the others take the vectorised sum"""
+    if cs is None:
+        return np.zeros(cell_dofs.shape[0], bool)
+    return cs.flag.astype(bool)[cell_dofs].any(axis=1)
+
+
+def distribute_vector(lay, cells, Re, cs=None):
+    """oracle.cpp distribute_vector over all cells: a constrained row's value goes to its entries with their weights (a
+    line without entries drops it); no placeholders."""
+    cell_dofs = lay.cell_dofs(np.asarray(cells)).astype(np.int64)
+    hit = _touched(cs, cell_dofs)
+    res = np.zeros(lay.n_dofs)
+    np.add.at(res, cell_dofs[~hit], Re[~hit])
+    for c in np.nonzero(hit)[0]:
+        loc, glob, w = _expand(cs, cell_dofs[c])
+        np.add.at(res, glob, w * Re[c, loc])
+    return res
+
+
+def distribute_matrix(mesh, lay, Ke, Re, cs=None):
+    """oracle.cpp distribute_matrix over all cells -> (CSR, vector).  With a constraint set the matrix lives on the pattern
+    of mesh.dof_sparsity (entries the distribution does not reach are stored zeros), as the oracle's does."""
+    cell_dofs = lay.cell_dofs(mesh.cells).astype(np.int64)
+    hit = _touched(cs, cell_dofs)
+    free = cell_dofs[~hit]
+    nf = free.shape[0]
+    rows = [np.broadcast_to(free[:, :, None], (nf, 32, 32)).ravel()]
+    cols = [np.broadcast_to(free[:, None, :], (nf, 32, 32)).ravel()]
+    vals = [Ke[~hit].ravel()]
+    res = np.zeros(lay.n_dofs)
+    np.add.at(res, free, Re[~hit])
+    for c in np.nonzero(hit)[0]:
+        d, K = cell_dofs[c], Ke[c]
+        loc, glob, w = _expand(cs, d)
+        np.add.at(res, glob, w * Re[c, loc])
+        m = glob.size
+        rows.append(np.repeat(glob, m))
+        cols.append(np.tile(glob, m))
+        vals.append(((w[:, None] * w[None, :]) * K[np.ix_(loc, loc)]).ravel())
+        diag = np.abs(np.diagonal(K))
+        con = np.nonzero(cs.flag[d])[0]
+        rows.append(d[con])
+        cols.append(d[con])
+        vals.append(np.where(diag[con] != 0.0, diag[con], diag.mean()))
+    if cs is not None:
+        rp, ci = M.dof_sparsity(mesh, lay)
+        rows.append(np.repeat(np.arange(lay.n_dofs, dtype=np.int64), np.diff(rp)))
+        cols.append(ci.astype(np.int64))
+        vals.append(np.zeros(ci.size))
     A = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(lay.n_dofs,) * 2).tocsr()
     A.sort_indices()
+    if cs is not None:
+        assert A.nnz == ci.size, "the distribution left the pattern"
+    return A, res
+
+
+def assemble(mesh, lay, prm, sol, old, oldold, cell_lambda=None, cell_mu=None, split=None, jacobian=True, cu=None, ch=None):
+    """assemble_system(residual_only = not jacobian) -> (A or None, residual_pde, E).  cu: constraints_update merged with
+    the hanging-node constraints and closed, as the oracle takes it (oracle_api.assemble); both matrix and residual are
+    distributed with it; ch, the hanging-node constraints alone, enters residual_total only (assemble_residuals).
+    cu = ch = None: the plain sum over the cells."""
+    Ke, Re, E = element_matrices(mesh, lay, prm, sol, old, oldold, cell_lambda, cell_mu, split, jacobian)
+    if not jacobian:
+        return None, distribute_vector(lay, mesh.cells, Re, cu), E
+    A, res = distribute_matrix(mesh, lay, Ke, Re, cu)
     return A, res, E
+
+
+def residual_total(lay, cells, prm, Re, cu, ch):
+    """the second vector of the residual-only call, oracle.cpp assemble (cracks.cc:2439-2464): the active-set scheme
+    (outer_solver 0) distributes it with the hanging-node constraints alone, every other scheme with constraints_update"""
+    return distribute_vector(lay, cells, Re, ch if prm.outer_solver == 0 else cu)
+
+
+def assemble_residuals(mesh, lay, prm, sol, old, oldold, cell_lambda=None, cell_mu=None, split=None, cu=None, ch=None):
+    """assemble_system(residual_only = true) -> (residual_pde, residual_total, E)"""
+    _, Re, E = element_matrices(mesh, lay, prm, sol, old, oldold, cell_lambda, cell_mu, split, jacobian=False)
+    return distribute_vector(lay, mesh.cells, Re, cu), residual_total(lay, mesh.cells, prm, Re, cu, ch), E
 
 
 def eigen_margin(E):
