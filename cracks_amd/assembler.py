@@ -110,8 +110,9 @@ class Context:
         self._check(self.lib.pfm_ctx_set_stream(self._h, C.c_void_p(stream_handle)), "pfm_ctx_set_stream")
 
     def set_split_model(self, model: int):
-        """0: the reference's closed form (2-D; a 3-D split assembly is refused), 1: the spectral split of 3-D contexts
-        (cracks_amd/split3d.py).  Before set_params."""
+        """0: the reference's closed form (2-D; a 3-D split assembly is refused), 1: the spectral split of 3-D contexts,
+        3: their volumetric-deviatoric split (capi.SPLIT_*; both laws in cracks_amd/split3d.py; 2 is unassigned).  Before
+        set_params; a living context may change between 1 and 3 at any time."""
         self._check(self.lib.pfm_set_split_model(self._h, int(model)), "pfm_set_split_model")
         self.split_model = int(model)
 
@@ -607,7 +608,7 @@ class Assembler:
     @property
     def split_model(self) -> int:
         """The law of a stress-split assembly (Context.set_split_model): 0 the reference's closed form, 1 the spectral split of
-        3-D meshes.  Set it before set_params."""
+        3-D meshes, 3 their volumetric-deviatoric split.  Set it before set_params."""
         return self.ctx.split_model
 
     @split_model.setter

@@ -18,7 +18,7 @@ STATUS_NAMES = {0: "PFM_OK", 1: "PFM_ERR_BAD_ARG", 2: "PFM_ERR_HIP", 3: "PFM_ERR
                 4: "PFM_ERR_NONFINITE", 5: "PFM_ERR_UNSUPPORTED", 6: "PFM_ERR_NOMEM", 7: "PFM_ERR_COMM", 8: "PFM_ERR_INTERNAL"}
 COMM_ID_BYTES = 128
 LAYOUT_INTERLEAVED, LAYOUT_BLOCKED = 0, 1
-SPLIT_REFERENCE, SPLIT_SPECTRAL = 0, 1  # pfm_set_split_model
+SPLIT_REFERENCE, SPLIT_SPECTRAL, SPLIT_VOLDEV = 0, 1, 3  # pfm_set_split_model (2 is unassigned)
 
 # every symbol include/pfm_assemble.h declares
 EXPORTS = [

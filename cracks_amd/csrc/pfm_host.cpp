@@ -1375,7 +1375,7 @@ extern "C"
       return PFM_ERR_BAD_ARG;
     // the reference gates the split on decompose_stress_matrix alone (cracks.cc:2294): decompose_stress_rhs > 0
     // without it multiplies a zero stress_term_minus, i.e. is a plain assembly and valid in 3-D
-    // (pfm_set_split_model: PFM_SPLIT_SPECTRAL is the 3-D law of pfm_split3.h)
+    // (pfm_set_split_model: PFM_SPLIT_SPECTRAL and PFM_SPLIT_VOLDEV are the 3-D laws of pfm_split3.h)
     if (c->v.dim == 3 && c->split_model == PFM_SPLIT_REFERENCE && p->decompose_stress_matrix > 0 && p->timestep_number > 0)
       return fail(c, PFM_ERR_UNSUPPORTED,
                   "stress split is 2-D only in the reference (cracks.cc:1685-1690)");
@@ -1389,10 +1389,12 @@ extern "C"
 
   int pfm_set_split_model(pfm_ctx *c, int model)
   {
-    if (!c || (model != PFM_SPLIT_REFERENCE && model != PFM_SPLIT_SPECTRAL))
+    if (!c || (model != PFM_SPLIT_REFERENCE && model != PFM_SPLIT_SPECTRAL && model != PFM_SPLIT_VOLDEV))
       return c ? fail(c, PFM_ERR_BAD_ARG, "unknown split model") : PFM_ERR_BAD_ARG;
     if (model == PFM_SPLIT_SPECTRAL && c->v.dim != 3)
       return fail(c, PFM_ERR_UNSUPPORTED, "the spectral split is the 3-D law; 2-D keeps the reference's closed form");
+    if (model == PFM_SPLIT_VOLDEV && c->v.dim != 3)
+      return fail(c, PFM_ERR_UNSUPPORTED, "the volumetric-deviatoric split is a 3-D law; 2-D keeps the reference's closed form");
     c->split_model = model;
     return PFM_OK;
   }
@@ -2316,8 +2318,9 @@ extern "C"
     // family alone): assemble_overlay
     p.overlay3 = !p.cart && c->v.dim == 3 && !c->levels3.empty() && c->kernel_path != 0 && !p.nothing && !p.split;
     p.patches = (!p.cart && c->v.dim == 2 && c->n_patch_blocks > 0 && c->kernel_path != 0 && !p.nothing) || p.overlay3;
-    // 3-D cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*) -- wanted
-    p.gather = !p.cart && c->v.dim == 3 && c->hang_gather && !p.split && !p.nothing;
+    // 3-D cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*) -- wanted.  A split
+    // assembly keeps it under PFM_SPLIT_VOLDEV, whose kernel is the unsplit form; the spectral instantiations have no SCR form
+    p.gather = !p.cart && c->v.dim == 3 && c->hang_gather && (!p.split || c->split_model == PFM_SPLIT_VOLDEV) && !p.nothing;
     // The two Jacobian kernels of a 3-D box next to each other (default): with equal LDS allocations (64 granules of 1280 B
     // each) any freed slot of a CU takes a workgroup of either kernel, the (u,u) and the phase-field workgroups mix and
     // fill each other's stalls: 14.07 -> 13.75 ms per assembly at 216^3 (PFM_JAC_SEQUENTIAL=1: one after the other).

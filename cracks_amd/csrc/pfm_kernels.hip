@@ -2,7 +2,7 @@
 //
 // General family = any Q1 quad/hex mesh (MappingQ1 geometry per quadrature point), any
 // constraint set (homogeneous lines + hanging nodes), optional 2-D stress split (the reference's closed form) or 3-D
-// spectral split (pfm_split3.h, pfm_set_split_model), optional per-cell Lame coefficients.  It is the reference-faithful fallback; uniform Cartesian
+// spectral or volumetric-deviatoric split (pfm_split3.h, pfm_set_split_model), optional per-cell Lame coefficients.  It is the reference-faithful fallback; uniform Cartesian
 // meshes (all BASELINE configs) are served by the row-owner kernels in pfm_cart.hip.
 //
 // Work decomposition: one lane <-> (cell, test vertex a).  The lane integrates the
@@ -204,12 +204,21 @@ namespace pfm
     // separated phases (phase = vertex index: a node receives exactly one cell per phase, the order of the adds is fixed) --
     // masked and written ONCE: no colour classes, no read-modify-write of global memory, no atomics.  Same q-loop, same
     // formulas as every other instantiation.
-    template <int dim, bool FULL, bool SPLIT, bool ATOMIC, bool RING = false /* DevView::cell_ring is set */, bool PATCH = false,
+    // The sixth parameter is PATCH in 2-D and VOLDEV in 3-D (neither exists in the other dimension): VOLDEV (PFM_SPLIT_VOLDEV,
+    // pfm_split3.h) is the unsplit 3-D form, SPLIT = false, with the isotropic tangent of the volumetric-deviatoric split,
+    // coefficients per q-point.  A parameter of its own would rename every instantiation, and the compiler's resource lines of
+    // the existing ones are only comparable -- and were identical -- while their names stay.  The slot is used up with this:
+    // a further 3-D law needs a parameter of its own (and renames them).  Its Jacobian form keeps the two workgroups per CU of
+    // the unsplit one: two loop invariants spill (20 bytes of scratch, one reload per round of 8 q-points); bound to one
+    // workgroup per CU nothing spills and the kernel is 50 % slower (profiles/split_voldev/README.md).
+    template <int dim, bool FULL, bool SPLIT, bool ATOMIC, bool RING = false /* DevView::cell_ring is set */, bool PATCH_OR_VOLDEV = false,
               bool SCR = false /* 3-D cells at hanging vertices: reduced matrix / residual into DevView::hs_* instead of the outputs */>
     __global__ __launch_bounds__(256, (dim == 3 && FULL && !SPLIT) ? 2 : 1) void k_assemble_general(DevView v, pfm_params prm, Vals vals,
                                                               double *res_pde, double *res_tot,
                                                               int residual_only, long long class_begin, long long class_size)
     {
+      constexpr bool PATCH = dim == 2 && PATCH_OR_VOLDEV, VOLDEV = dim == 3 && PATCH_OR_VOLDEV;
+      static_assert(!VOLDEV || !SPLIT, "the volumetric-deviatoric law is a form of the unsplit kernel");
       static_assert(!PATCH || (dim == 2 && !ATOMIC && !RING), "the patch form exists in 2-D");
       constexpr int PRW = 81 + 3 + 3; // staged row of a node: 3 row components x 9 offsets x 3 column components, residual, placeholders
       __shared__ double s_row[PATCH ? 49 * PRW : 1];
@@ -617,10 +626,17 @@ namespace pfm
           // its symmetric 6 x 6 tangent, phase B forms the rows as B_a^T D B_b.  The slot is larger (QST above) and the Jacobian
           // form runs 16 slots per round: phase A, now most of the work, is repeated by two lanes per q-point instead of four.
           // It is bound to one workgroup per CU (launch bounds): 256 registers and 60 accumulation registers, no scratch.
+          // VOLDEV (volumetric-deviatoric split, pfm_split3.h): not a SPLIT form.  Its tangent is isotropic at every q-point, so it
+          // is the unsplit arrangement -- 8 slots per round, stride 50, two workgroups per CU, every scatter class, SCR included --
+          // with sigma+ of that law, one more tangent weight in the slot and sigma- folded into the residual's pressure term.
           constexpr double GX0 = 0.5 - 0.5 * 0.7745966692414834, GX2 = 0.5 + 0.5 * 0.7745966692414834; // make_ref_tables
           constexpr double GW0 = 5.0 / 18.0, GW1 = 8.0 / 18.0;
           // slot layout (doubles): vertex v at 4 v: grad N_v (3), N_v;  32..: the scalars below;  stride QST
           constexpr int O_GW = 32 /* g JxW, c_pu */, O_CDIV = 34 /* c_div, c_pp */, O_CGG = 36 /* c_gg, c_pen */, O_SP = 38 /* sigma+ (6) */, O_RP = 44 /* r_p, r_phi */, O_GPF = 46 /* grad phi (3) */;
+          // VOLDEV (volumetric-deviatoric split, pfm_split3.h): this layout with sigma+ of that law at O_SP, decompose_stress_rhs sigma-
+          // (a multiple of I) inside r_p, and the one tangent weight the unsplit form does not have in the free double of the slot
+          constexpr int O_AW = 49 /* a JxW of the tangent a I(x)I + 2 b I_s; b JxW = mu g JxW as in the unsplit form */;
+          static_assert(!VOLDEV || O_AW < QST, "slot layout of the volumetric-deviatoric form");
           // SPLIT: the combined residual stress instead of sigma+, the 21 entries of the symmetric 6 x 6 tangent and what the
           // (phi,u) rows need (Jacobian only: 44 doubles without them)
           constexpr int O3_S = 32 /* (g sigma+ + d_rhs sigma- - p-term) JxW (6) */, O3_RP = 38 /* r_phi, c_gg */, O3_GPF = 40 /* grad phi (3), c_pp */,
@@ -816,6 +832,28 @@ namespace pfm
                   else
                     {
                   double sp[3][3], spE = 0.0; // sigma+ = lambda tr(E) I + 2 mu E, sigma- = 0 (cracks.cc:2284-2292)
+                  double rp_minus = 0.0;      // VOLDEV: decompose_stress_rhs sigma- = rp_minus I
+                  if constexpr (VOLDEV)
+                    {
+                      // volumetric-deviatoric split (pfm_split3.h; PFM_SPLIT_VOLDEV): sigma+ takes the place of the unsplit stress in
+                      // every statement below, sigma- is a multiple of I and joins the pressure term of the residual, and the
+                      // tangent g C+ + d_mat C- = a I(x)I + 2 b I_s has b = mu g and a of its own (slot 49)
+                      const split3::VolDev S = split3::voldev(trE, lam, mu);
+#pragma unroll
+                      for (int i = 0; i < 3; ++i)
+#pragma unroll
+                        for (int k = 0; k < 3; ++k)
+                          {
+                            sp[i][k] = split3::voldev_sigma_plus(S, mu, E[i][k], i == k);
+                            spE += sp[i][k] * E[i][k];
+                          }
+                      rp_minus = d_rhs * S.sm_iso;
+                      if constexpr (FULL)
+                        if (writer)
+                          o[O_AW] = split3::voldev_tangent_a(S, lam, mu, g, d_mat) * JxW;
+                    }
+                  else
+                    {
 #pragma unroll
                   for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -824,6 +862,7 @@ namespace pfm
                         sp[i][k] = lam * trE * (i == k ? 1.0 : 0.0) + 2 * mu * E[i][k];
                         spE += sp[i][k] * E[i][k];
                       }
+                    }
                   if (writer)
                     {
                       const bool pen_on = !((pf - pfo) < 0.0); // shadowed variable, cracks.cc:2311-2315
@@ -835,7 +874,8 @@ namespace pfm
                       *reinterpret_cast<double2 *>(o + O_SP + 2) = make_double2(sp[0][2], sp[1][1]);
                       *reinterpret_cast<double2 *>(o + O_SP + 4) = make_double2(sp[1][2], sp[2][2]);
                       *reinterpret_cast<double2 *>(o + O_RP) =
-                        make_double2(aB1 * p * pfx * pfx * JxW, (penal_fac * pf_minus_old_plus + (1.0 - kappa) * spE * pf - Gc / eps * (1.0 - pf) -
+                        make_double2(VOLDEV ? (aB1 * p * pfx * pfx - rp_minus) * JxW : aB1 * p * pfx * pfx * JxW,
+                                     (penal_fac * pf_minus_old_plus + (1.0 - kappa) * spE * pf - Gc / eps * (1.0 - pf) -
                                                                  2.0 * aB1 * p * pf * divu) *
                                                                   JxW);
                       *reinterpret_cast<double2 *>(o + O_GPF) = make_double2(gpf[0], gpf[1]);
@@ -923,7 +963,10 @@ namespace pfm
 #pragma unroll
                   for (int c = 0; c < 3; ++c)
                     {
-                      LA[c] = lam * gw * gNa[c];
+                      if constexpr (VOLDEV)
+                        LA[c] = i[O_AW] * gNa[c];
+                      else
+                        LA[c] = lam * gw * gNa[c];
                       MA[c] = mu * gw * gNa[c];
                     }
                   const double mgw = mu * gw;
@@ -2663,9 +2706,11 @@ namespace pfm
     // The reference gates the split on decompose_stress_matrix only (cracks.cc:2294); a
     // non-zero decompose_stress_rhs without it multiplies a zero stress_term_minus.
     // In 3-D the reference's closed form is refused (it reads the 2 x 2 corner of the strain, cracks.cc:1683-1690); the
-    // spectral model (pfm_set_split_model, pfm_split3.h) has instantiations of its own.
-    if (v.dim == 3 && split && split_model != PFM_SPLIT_SPECTRAL)
+    // spectral model (pfm_set_split_model, pfm_split3.h) has instantiations of its own, the volumetric-deviatoric model as well
+    // (VOLDEV: the unsplit form, so its cells at hanging vertices keep the scratch).
+    if (v.dim == 3 && split && split_model != PFM_SPLIT_SPECTRAL && split_model != PFM_SPLIT_VOLDEV)
       return PFM_ERR_UNSUPPORTED;
+    const bool voldev = v.dim == 3 && split && split_model == PFM_SPLIT_VOLDEV;
     // cells per workgroup: 32 lanes per hex for the 3-D Jacobian (k_assemble_general: Q3), one lane per vertex otherwise
     const int nv = 1 << v.dim, cpb = (v.dim == 3 && !residual_only) ? 8 : 256 / nv;
     const int n_classes = (int)color_ptr.size() - 1;
@@ -2702,7 +2747,31 @@ namespace pfm
                            residual_only, c0, cn);                                                                           \
     }                                                                                                                        \
   while (0)
-        if (v.dim == 2)
+#define PFM_LAUNCH_VOLDEV(FULLV)                                                                                             \
+  do                                                                                                                         \
+    {                                                                                                                        \
+      if (atomic && v.hs_K)                                                                                                  \
+        hipLaunchKernelGGL((k_assemble_general<3, FULLV, false, true, false, true, true>), grid, block, 0, s, v, p, vals,    \
+                           res_pde, res_tot, residual_only, c0, cn);                                                         \
+      else if (atomic)                                                                                                       \
+        hipLaunchKernelGGL((k_assemble_general<3, FULLV, false, true, false, true>), grid, block, 0, s, v, p, vals, res_pde, \
+                           res_tot, residual_only, c0, cn);                                                                  \
+      else if (v.cell_ring)                                                                                                  \
+        hipLaunchKernelGGL((k_assemble_general<3, FULLV, false, false, true, true>), grid, block, 0, s, v, p, vals, res_pde, \
+                           res_tot, residual_only, c0, cn);                                                                  \
+      else                                                                                                                   \
+        hipLaunchKernelGGL((k_assemble_general<3, FULLV, false, false, false, true>), grid, block, 0, s, v, p, vals, res_pde,\
+                           res_tot, residual_only, c0, cn);                                                                  \
+    }                                                                                                                        \
+  while (0)
+        if (voldev)
+          {
+            if (residual_only)
+              PFM_LAUNCH_VOLDEV(false);
+            else
+              PFM_LAUNCH_VOLDEV(true);
+          }
+        else if (v.dim == 2)
           {
             if (residual_only)
               {
@@ -2736,6 +2805,7 @@ namespace pfm
                   PFM_LAUNCH(3, true, false);
               }
           }
+#undef PFM_LAUNCH_VOLDEV
 #undef PFM_LAUNCH
       }
     return check_launch();

@@ -9,6 +9,8 @@
 //   dE+[H] = sum_i h(l_i) (n_i^T H n_i) n_i n_i^T + sum_{i != j} theta_ij (n_i^T H n_j) n_i n_j^T
 //   theta_ij = (max(l_i, 0) - max(l_j, 0)) / (l_i - l_j),  = h(l_i) when l_i == l_j in floating point
 //
+// At the end of the file: the volumetric-deviatoric split (PFM_SPLIT_VOLDEV), which needs none of the above.
+//
 // Plain C++ without hardware estimates: the same statements compile for the device and, alone, for the CPU
 // (tests/cpp/split3_main.cpp).  Voigt order 00, 11, 22, 01, 02, 12; a direction H enters with its shears DOUBLED (the
 // columns of B_b in the kernel are engineering strains), a stress leaves with plain components: the tangents are symmetric.
@@ -169,6 +171,71 @@ namespace pfm
             const double P = S.Pp[tri(r, k)];
             Cp[tri(r, k)] = lam * S.htr * one + 2 * mu * P;
             Cm[tri(r, k)] = lam * (1.0 - S.htr) * one + 2 * mu * (ids - P);
+          }
+    }
+
+    // ---- volumetric-deviatoric split (PFM_SPLIT_VOLDEV; cracks_amd/split3d.py: voldev_split, voldev_tangent)
+    //
+    //   K = lambda + 2 mu / 3,  tr+ = max(tr E, 0),  tr- = tr E - tr+,  h = h(tr E)
+    //   sigma+ = K tr+ I + 2 mu (E - (tr E / 3) I)            sigma- = K tr- I
+    //   C+ = K h I (x) I + 2 mu (I_s - 1/3 I (x) I)           C- = K (1 - h) I (x) I
+    //
+    // No eigenpairs: sigma+ = sp_iso I + 2 mu E, sigma- = sm_iso I, and g C+ + d_mat C- = a I (x) I + 2 (mu g) I_s is the
+    // tangent of an isotropic material (voldev_tangent_a).  Finite for finite input; no division but the constant 1/3.
+    struct VolDev
+    {
+      double sp_iso; // K tr+ - (2 mu / 3) tr E
+      double sm_iso; // K tr-
+      double h;      // h(tr E)
+    };
+
+    PFM_HD VolDev voldev(double trE, double lam, double mu)
+    {
+      const double K = lam + 2.0 * mu / 3.0, trp = fmax(trE, 0.0);
+      VolDev S;
+      S.sp_iso = K * trp - (2.0 * mu / 3.0) * trE;
+      S.sm_iso = K * (trE - trp);
+      S.h = trE < 0.0 ? 0.0 : 1.0;
+      return S;
+    }
+
+    // a of  g C+ + d_mat C- = a I (x) I + 2 b I_s,  b = mu g
+    PFM_HD double voldev_tangent_a(const VolDev &S, double lam, double mu, double g, double d_mat)
+    {
+      return lam * (g * S.h + d_mat * (1.0 - S.h)) - (2.0 * mu / 3.0) * (1.0 - S.h) * (g - d_mat);
+    }
+
+    // one component of sigma+ = sp_iso I + 2 mu E: e the component of E, diag whether it sits on the diagonal.  The kernel
+    // and voldev_stress3 both form sigma+ through this statement, and sigma- as sm_iso on the diagonal.
+    PFM_HD double voldev_sigma_plus(const VolDev &S, double mu, double e, bool diag) { return (diag ? S.sp_iso : 0.0) + 2 * mu * e; }
+
+    // sigma+ and sigma- (Voigt, plain components)
+    PFM_HD void voldev_stress3(const double E[6], double lam, double mu, double sp[6], double sm[6])
+    {
+      const VolDev S = voldev(E[0] + E[1] + E[2], lam, mu);
+#pragma unroll
+      for (int r = 0; r < 6; ++r)
+        {
+          sp[r] = voldev_sigma_plus(S, mu, E[r], r < 3);
+          sm[r] = r < 3 ? S.sm_iso : 0.0;
+        }
+    }
+
+    // C+ and C-, packed upper triangles in the form of split_tangent3: g = 1, d_mat = 0 is C+, g = 0, d_mat = 1 is C-.
+    // (For the host program and as documentation: the kernel keeps only voldev_tangent_a and b = mu g per q-point.)
+    PFM_HD void voldev_tangent3(const double E[6], double lam, double mu, double Cp[21], double Cm[21])
+    {
+      const VolDev S = voldev(E[0] + E[1] + E[2], lam, mu);
+      const double ap = voldev_tangent_a(S, lam, mu, 1.0, 0.0), am = voldev_tangent_a(S, lam, mu, 0.0, 1.0);
+#pragma unroll
+      for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int k = r; k < 6; ++k)
+          {
+            const double one = (r < 3 && k < 3) ? 1.0 : 0.0;       // I (x) I
+            const double ids = r == k ? (r < 3 ? 1.0 : 0.5) : 0.0; // symmetric identity, doubled-shear columns
+            Cp[tri(r, k)] = ap * one + 2 * mu * ids;
+            Cm[tri(r, k)] = am * one;
           }
     }
   } // namespace split3

@@ -1,4 +1,5 @@
-"""Spectral tension / compression split of the stress in 3-D, in plain numpy.
+"""Tension / compression splits of the stress in 3-D, in plain numpy: the spectral split (below) and the
+volumetric-deviatoric split (``voldev_split``, ``voldev_tangent``: ``PFM_SPLIT_VOLDEV``, the law in their docstrings).
 
 Like ``kelly_numpy`` this is both the statement of the law and the reference the device code
 (``csrc/pfm_split3.h``, the 3-D SPLIT instantiations of ``k_assemble_general``) is tested against.
@@ -73,6 +74,41 @@ def spectral_tangent(E, lam, mu):
     Is = 0.5 * (np.einsum("ac,bd->abcd", I, I) + np.einsum("ad,bc->abcd", I, I))
     htr = np.where(np.trace(E, axis1=-2, axis2=-1) < 0.0, 0.0, 1.0)[..., None, None, None, None]
     return lam * htr * II + 2 * mu * P, lam * (1.0 - htr) * II + 2 * mu * (Is - P)
+
+
+def voldev_split(E, lam, mu):
+    """(sigma+, sigma-) of the volumetric-deviatoric split (``PFM_SPLIT_VOLDEV``; Amor, Marigo, Maurini):
+
+        K = lam + 2 mu / 3          tr+ = max(tr E, 0)          tr- = tr E - tr+
+        sigma+ = K tr+ I + 2 mu (E - (tr E / 3) I)              sigma- = K tr- I
+
+    lam, mu scalars or arrays of the batch shape, as in ``spectral_split``."""
+    E = np.asarray(E, dtype=np.float64)
+    lam = np.asarray(lam, dtype=np.float64)[..., None, None]
+    mu = np.asarray(mu, dtype=np.float64)[..., None, None]
+    K = lam + 2 * mu / 3
+    tr = np.trace(E, axis1=-2, axis2=-1)[..., None, None]
+    trp = np.maximum(tr, 0.0)
+    I = np.eye(3)
+    return K * trp * I + 2 * mu * (E - tr / 3 * I), K * (tr - trp) * I
+
+
+def voldev_tangent(E, lam, mu):
+    """(C+, C-) of the volumetric-deviatoric split, tensors [..., 3, 3, 3, 3] as in ``spectral_tangent``:
+
+        C+ = K h(tr E) I (x) I + 2 mu (I_s - 1/3 I (x) I)       C- = K (1 - h(tr E)) I (x) I
+
+    with h(0) = 1.  Both are isotropic: g C+ + d C- = a I (x) I + 2 b I_s with
+    a = lam (g h + d (1 - h)) - (2 mu / 3) (1 - h) (g - d) and b = mu g, which is the form the kernel keeps per q-point."""
+    E = np.asarray(E, dtype=np.float64)
+    lam = np.asarray(lam, dtype=np.float64)[..., None, None, None, None]
+    mu = np.asarray(mu, dtype=np.float64)[..., None, None, None, None]
+    K = lam + 2 * mu / 3
+    I = np.eye(3)
+    II = np.einsum("ab,cd->abcd", I, I)
+    Is = 0.5 * (np.einsum("ac,bd->abcd", I, I) + np.einsum("ad,bc->abcd", I, I))
+    h = np.where(np.trace(E, axis1=-2, axis2=-1) < 0.0, 0.0, 1.0)[..., None, None, None, None]
+    return K * h * II + 2 * mu * (Is - II / 3), K * (1.0 - h) * II
 
 
 def voigt6(S):

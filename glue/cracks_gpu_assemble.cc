@@ -133,7 +133,9 @@ namespace pfm_glue_detail
     //                      the call; if it does write them it calls values_written_by_host() first.  The library's
     //                      copy of the host's values goes with the context (release(), before_setup_system()).  If the
     //                      device cannot hold that copy the values travel through pfm_values_to_host as before.
-    //   split_model:       PFM_SPLIT_SPECTRAL gives a 3-D run the tension / compression split the reference only has in 2-D
+    //   split_model:       PFM_SPLIT_SPECTRAL or PFM_SPLIT_VOLDEV gives a 3-D run the tension / compression split the reference
+    //                      only has in 2-D: through the eigenpairs of the strain, or volumetric-deviatoric (no eigen-solve,
+    //                      bitwise reproducible on meshes with hanging nodes as well)
     //                      (pfm_set_split_model; forwarded in front of the parameters at every assemble()).  With the default,
     //                      PFM_SPLIT_REFERENCE, a 3-D run with decompose_stress_matrix > 0 stops at PFM_ERR_UNSUPPORTED.
     //   line_search_stepwise: line_search() runs the host loop of a rank with ghost peers (vector statements, scatter + halo +

@@ -112,13 +112,23 @@ int pfm_set_params(pfm_ctx *ctx, const pfm_params *prm);
  *                        cracks_amd/split3d.py); never PFM_ERR_NOT_ORTHOGONAL.  A 3-D box or overlay context runs a split
  *                        assembly through the general family over all cells and returns to its own kernels with the split
  *                        off (timestep_number = 0).
- * Model 1 on a 2-D context: PFM_ERR_UNSUPPORTED (2-D keeps the reference's closed form).  An unknown model:
- * PFM_ERR_BAD_ARG.  Call it before pfm_set_params; back at model 0 with split parameters still set, a 3-D assembly
- * returns PFM_ERR_UNSUPPORTED. */
+ *   PFM_SPLIT_VOLDEV     3-D contexts: the volumetric-deviatoric split of Amor, Marigo and Maurini (DESIGN.md §2,
+ *                        cracks_amd/split3d.py: voldev_split): sigma+ = K max(tr E, 0) I + 2 mu dev E, sigma- = K min(tr E, 0) I,
+ *                        K = lambda + 2 mu / 3.  No eigen-solve, an isotropic tangent per q-point; never
+ *                        PFM_ERR_NOT_ORTHOGONAL.  Routed like model 1.  Unlike model 1, the cells at hanging vertices keep
+ *                        the scratch + ordered gather, so a model-3 assembly is bitwise reproducible run to run
+ *                        (PFM_HANGING_ATOMIC=1: the atomic class).  The tangent is discontinuous at tr E = 0 (h(0) = 1, zero
+ *                        counts as tension) and follows the sign of the trace the device computes: where tr E is zero up to
+ *                        rounding (a pure shear on a general mesh) that sign, and with it the matrix, is not determined.
+ * Model 1 or 3 on a 2-D context: PFM_ERR_UNSUPPORTED (2-D keeps the reference's closed form).  An unknown model:
+ * PFM_ERR_BAD_ARG -- the value 2 is unassigned and stays refused.  Call it before pfm_set_params; back at model 0 with
+ * split parameters still set, a 3-D assembly returns PFM_ERR_UNSUPPORTED.  A living context may change between models 1
+ * and 3 at any time: the next assembly uses the new law. */
 enum
 {
   PFM_SPLIT_REFERENCE = 0,
-  PFM_SPLIT_SPECTRAL = 1
+  PFM_SPLIT_SPECTRAL = 1,
+  PFM_SPLIT_VOLDEV = 3
 };
 int pfm_set_split_model(pfm_ctx *ctx, int model);
 /* constraints_update minus the hanging nodes: one byte per local node, bit c set <=> dof

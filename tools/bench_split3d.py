@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Time the 3-D spectral stress split (pfm_set_split_model, PFM_SPLIT_SPECTRAL) next to the unsplit general family on the
-same mesh, in one process:
+"""Time the 3-D stress splits (pfm_set_split_model: PFM_SPLIT_SPECTRAL, PFM_SPLIT_VOLDEV) next to the unsplit general family on
+the same mesh, in one process:
 
   a --n^3 box (100^3 by default), the general family over all cells (the split assembly of a box context takes it by
   itself; the unsplit one is sent there with pfm_ctx_force_path(0)), Jacobian and residual-only assembly, the split off
@@ -11,7 +11,10 @@ everywhere).  Kernel time from the library's own events around each assembly (pf
 every colour class), median and minimum over --reps assemblies after --warmup.  The two results are compared with each other
 where they must agree: in a second state of pure tension the split assembly reproduces the unsplit one.  One JSON line.
 
-    python tools/bench_split3d.py [--n 100] [--reps 20] [--warmup 3] [--rounds 3]
+--model names the law (default: spectral, output as before).  With several models (--model spectral voldev) every round runs
+the unsplit arm and one arm per model, alternating; the keys of a model's arm then carry its name instead of "split".
+
+    python tools/bench_split3d.py [--n 100] [--reps 20] [--warmup 3] [--rounds 3] [--model {spectral,voldev} ...]
 """
 import argparse
 import json
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3, help="off / on alternations; the medians of all rounds are reported")
     ap.add_argument("--layout", choices=["blocked", "interleaved"], default="blocked")
+    ap.add_argument("--model", choices=["spectral", "voldev"], nargs="+", default=["spectral"], help="the split law(s) to time")
     args = ap.parse_args()
 
     import torch
@@ -62,7 +66,9 @@ def main():
 
     asm = Assembler(mesh, blocked)
     assert asm.ctx.kernel_path == 1
-    asm.split_model = capi.SPLIT_SPECTRAL
+    models = {"spectral": capi.SPLIT_SPECTRAL, "voldev": capi.SPLIT_VOLDEV}
+    arms = list(dict.fromkeys(args.model))  # None below: the unsplit arm
+    asm.split_model = models[arms[0]]
     asm.set_constraints(np.zeros(mesh.n_nodes, np.uint8))
     asm.set_vectors(sol, old, old)
     asm.allocate_matrix()
@@ -70,6 +76,8 @@ def main():
     def configure(split):
         # the unsplit assembly through the general family as well (the box's own kernels are not the yardstick here)
         asm.ctx.force_path(0)
+        if split:
+            asm.split_model = models[split]
         asm.set_params(prm_on if split else prm_off)
 
     def timed(split, residual_only):
@@ -89,30 +97,36 @@ def main():
     # agreement where the two must agree: pure tension
     asm.set_vectors(tension, old, old)
     outs = []
-    for split in (False, True):
+    for split in [None] + arms:
         configure(split)
         asm.assemble_system(False)
         asm.synchronize()
         outs.append(([m.clone() for m in asm.system_pde_matrix], asm.system_pde_residual.clone()))
-    dev = max(float((a - b).abs().max() / max(1.0, float(b.abs().max()))) for a, b in zip(outs[1][0] + [outs[1][1]], outs[0][0] + [outs[0][1]]))
+    dev = max(float((a - b).abs().max() / max(1.0, float(b.abs().max()))) for o in outs[1:] for a, b in zip(o[0] + [o[1]], outs[0][0] + [outs[0][1]]))
     del outs
     asm.set_vectors(sol, old, old)
 
     rec = {"metric": "split3d_general_family", "cells": int(mesh.n_cells), "layout": args.layout, "reps": args.reps, "rounds": args.rounds,
            "pure_tension_deviation_from_unsplit": dev}
+    if arms != ["spectral"]:
+        rec["models"] = arms
     for residual_only, tag in ((False, "jacobian"), (True, "residual_only")):
-        ts = {False: [], True: []}
+        ts = {split: [] for split in [None] + arms}
         for _ in range(args.rounds):
-            for split in (False, True):
+            for split in [None] + arms:
                 ts[split].append(timed(split, residual_only))
-        off, on = np.concatenate(ts[False]), np.concatenate(ts[True])
+        off = np.concatenate(ts[None])
         rec[tag] = {"unsplit_ms": float(np.median(off)), "unsplit_min_ms": float(off.min()),
-                    "unsplit_round_medians_ms": [float(np.median(t)) for t in ts[False]],
-                    "split_ms": float(np.median(on)), "split_min_ms": float(on.min()),
-                    "split_round_medians_ms": [float(np.median(t)) for t in ts[True]],
-                    "ratio": float(np.median(on) / np.median(off)),
-                    "unsplit_ms_per_1e6_cells": float(np.median(off) * 1e6 / mesh.n_cells),
-                    "split_ms_per_1e6_cells": float(np.median(on) * 1e6 / mesh.n_cells)}
+                    "unsplit_round_medians_ms": [float(np.median(t)) for t in ts[None]]}
+        for m in arms:
+            on, key = np.concatenate(ts[m]), ("split" if len(arms) == 1 else m)
+            rec[tag].update({f"{key}_ms": float(np.median(on)), f"{key}_min_ms": float(on.min()),
+                             f"{key}_round_medians_ms": [float(np.median(t)) for t in ts[m]],
+                             ("ratio" if len(arms) == 1 else f"{key}_ratio"): float(np.median(on) / np.median(off))})
+        rec[tag]["unsplit_ms_per_1e6_cells"] = float(np.median(off) * 1e6 / mesh.n_cells)
+        for m in arms:
+            key = "split" if len(arms) == 1 else m
+            rec[tag][f"{key}_ms_per_1e6_cells"] = float(np.median(np.concatenate(ts[m])) * 1e6 / mesh.n_cells)
     print(json.dumps(rec))
 
 
