@@ -346,6 +346,46 @@ class Context:
                     "pfm_active_set_device")
         return int(counts[0]), int(counts[1]), int(counts[2])
 
+    # ---- include/pfm_newton.h, the active-set update of a rank with ghost peers
+    def active_set_owned_device(self, res_tot_ptr: int, mass_ptr: int, c: float, sol_ptr: int, old_ptr: int, cycle_ptr: int):
+        """``pfm_active_set_owned_device``: ``active_set_device`` without the distribution of the hanging nodes, on any
+        context (a partitioned one with hanging nodes too); returns (active, cycling, changed) of this rank."""
+        counts = (C.c_int64 * 3)()
+        self._check(self.lib.pfm_active_set_owned_device(self._h, C.c_void_p(res_tot_ptr), C.c_void_p(mass_ptr), C.c_double(c),
+                                                         C.c_void_p(sol_ptr), C.c_void_p(old_ptr), C.c_void_p(cycle_ptr), counts),
+                    "pfm_active_set_owned_device")
+        return int(counts[0]), int(counts[1]), int(counts[2])
+
+    def halo_pack_flags_all(self, buf_ptr: int):
+        """``pfm_halo_pack_flags_all``: the flag bytes of the send nodes, one byte per node, peer k at byte send_ptr[k]."""
+        self._check(self.lib.pfm_halo_pack_flags_all(self._h, C.c_void_p(buf_ptr)), "pfm_halo_pack_flags_all")
+
+    def halo_unpack_flags_all(self, buf_ptr: int):
+        """``pfm_halo_unpack_flags_all``: bit ``dim`` of the received bytes into the flag bytes of the ghost nodes."""
+        self._check(self.lib.pfm_halo_unpack_flags_all(self._h, C.c_void_p(buf_ptr)), "pfm_halo_unpack_flags_all")
+
+    def halo_exchange_flags(self, comm_handle: int, peer_ranks):
+        """``pfm_halo_exchange_flags``: pack -> RCCL send/recv of the flag bytes -> unpack inside the library."""
+        pr = np.ascontiguousarray(peer_ranks, np.int32)
+        self._check(self.lib.pfm_halo_exchange_flags(self._h, C.c_void_p(comm_handle),
+                                                     capi.np_ptr(pr, np.int32) if pr.size else None), "pfm_halo_exchange_flags")
+
+    def distribute_hanging_device(self, sol_ptr: int = 0):
+        """``pfm_distribute_hanging_device``: the hanging nodes of the node state, owned and ghost, from their parents'
+        node values; owned ones also into the device dof vector ``sol_ptr`` (0: node arrays only)."""
+        self._check(self.lib.pfm_distribute_hanging_device(self._h, C.c_void_p(sol_ptr)), "pfm_distribute_hanging_device")
+
+    def active_set_exchange(self, comm_handle: int, peer_ranks, res_tot_ptr: int, mass_ptr: int, c: float, sol_ptr: int, old_ptr: int,
+                            cycle_ptr: int):
+        """``pfm_active_set_exchange``: cracks.cc:2826-2890 on a rank with ghost peers in one collective call (``comm_handle``
+        0 and no ``peer_ranks`` on a context without peers); returns (active, cycling, changed) of this rank."""
+        pr = np.ascontiguousarray(peer_ranks if peer_ranks is not None else [], np.int32)
+        counts = (C.c_int64 * 3)()
+        self._check(self.lib.pfm_active_set_exchange(self._h, C.c_void_p(comm_handle), capi.np_ptr(pr, np.int32) if pr.size else None,
+                                                     C.c_void_p(res_tot_ptr), C.c_void_p(mass_ptr), C.c_double(c), C.c_void_p(sol_ptr),
+                                                     C.c_void_p(old_ptr), C.c_void_p(cycle_ptr), counts), "pfm_active_set_exchange")
+        return int(counts[0]), int(counts[1]), int(counts[2])
+
     def get_constraints(self) -> np.ndarray:
         flags = np.empty(self.n_nodes, np.uint8)
         self._check(self.lib.pfm_get_constraints(self._h, capi.np_ptr(flags, np.uint8)), "pfm_get_constraints")

@@ -37,6 +37,8 @@ EXPORTS = [
     "pfm_refine_flags", "pfm_min_cell_diameter", "pfm_state_transfer",
     "pfm_kelly_indicator", "pfm_indicator_select", "pfm_indicator_count", "pfm_refine_flags_mix",
     "pfm_line_search_advance", "pfm_line_search_retreat", "pfm_line_search_device", "pfm_project_back_device",
+    "pfm_active_set_owned_device", "pfm_halo_pack_flags_all", "pfm_halo_unpack_flags_all", "pfm_halo_exchange_flags",
+    "pfm_distribute_hanging_device", "pfm_active_set_exchange",
 ]
 LS_NORM_L2, LS_NORM_LINF = 0, 1  # pfm_line_search_opts.norm
 LS_RESTORE_SAVED, LS_RESTORE_SUBTRACT = 0, 1  # pfm_line_search_opts.restore
@@ -192,6 +194,12 @@ def load():
     lib.pfm_line_search_retreat.argtypes = [vp, i32, C.c_double, vp, vp, vp, i32]
     lib.pfm_line_search_device.argtypes = [vp, C.POINTER(PfmLineSearchOpts), vp, vp, vp, vp, C.POINTER(PfmLineSearchResult)]
     lib.pfm_project_back_device.argtypes = [vp, vp]
+    lib.pfm_active_set_owned_device.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp, C.POINTER(i64)]
+    lib.pfm_halo_pack_flags_all.argtypes = [vp, vp]
+    lib.pfm_halo_unpack_flags_all.argtypes = [vp, vp]
+    lib.pfm_halo_exchange_flags.argtypes = [vp, vp, vp]
+    lib.pfm_distribute_hanging_device.argtypes = [vp, vp]
+    lib.pfm_active_set_exchange.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, C.POINTER(i64)]
     _LIB = lib
     return lib
 

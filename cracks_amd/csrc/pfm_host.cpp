@@ -12,6 +12,7 @@
 //   * cell->get_dof_indices + the Trilinos column search (cracks.cc:2439-2463) become a
 //     one-byte-per-vertex-pair slot table.
 #include "pfm_internal.h"
+#include "../../include/pfm_newton.h"
 #include "pfm_cart_plan.h"
 #include "pfm_host_pool.h"
 #include "pfm_mesh_plan.h"
@@ -2114,8 +2115,11 @@ extern "C"
     return PFM_OK;
   }
 
-  // pack -> grouped send/receive -> unpack, on `st` (the context's stream, or its side stream for the overlapped form)
-  static int halo_exchange_on(pfm_ctx *c, void *comm, const int *peer_ranks, hipStream_t st)
+  // pack -> grouped send/receive -> unpack, on `st` (the context's stream, or its side stream for the overlapped form).
+  // what: HALO_VALUES = the node values (pfm_halo_exchange), HALO_FLAGS = the flag bytes (pfm_halo_exchange_flags), or both
+  // in one group (pfm_active_set_exchange)
+  enum { HALO_VALUES = 1, HALO_FLAGS = 2 };
+  static int halo_exchange_on(pfm_ctx *c, void *comm, const int *peer_ranks, hipStream_t st, int what = HALO_VALUES)
   {
     const RcclApi &R = rccl();
     if (!R.ok)
@@ -2137,11 +2141,18 @@ extern "C"
       h->cm = nullptr;
       return fail(c, code, msg + (h->owned ? " (communicator aborted)" : " (wrapped communicator left to the host, handle disabled)"));
     };
-    int rc = ensure_halo_buffers(c);
+    const bool values = what & HALO_VALUES, flags = what & HALO_FLAGS;
+    int rc = values ? ensure_halo_buffers(c) : PFM_OK;
+    if (rc == PFM_OK && flags)
+      rc = reserve_flag_halo_buffers(c);
     if (rc)
       return abort_comm(rc, "halo buffers");
     const int rec = PFM_HALO_DOUBLES_PER_NODE(c->v.dim);
-    rc = launch_halo_all(c->v, c->d_send_all, c->d_send_ptr, (int)c->peers.size(), c->n_send_all, c->d_halo_send, 0, st);
+    uint8_t *f_send = c->buf_flag_send.as<uint8_t>(), *f_recv = c->buf_flag_recv.as<uint8_t>();
+    if (values)
+      rc = launch_halo_all(c->v, c->d_send_all, c->d_send_ptr, (int)c->peers.size(), c->n_send_all, c->d_halo_send, 0, st);
+    if (rc == PFM_OK && flags)
+      rc = launch_halo_flags_all(c->v, c->d_send_all, c->n_send_all, f_send, 0, st);
     if (rc)
       return abort_comm(rc, "halo pack launch failed");
     ncclResult_t r = R.GroupStart();
@@ -2149,10 +2160,14 @@ extern "C"
     for (size_t k = 0; k < c->peers.size() && r == ncclSuccess; ++k)
       {
         const HaloPeer &p = c->peers[k];
-        if (p.n_recv)
+        if (values && p.n_recv)
           r = R.Recv(c->d_halo_recv + rec * ro, (size_t)(rec * p.n_recv), ncclDouble, peer_ranks[k], cm, st);
-        if (p.n_send && r == ncclSuccess)
+        if (values && p.n_send && r == ncclSuccess)
           r = R.Send(c->d_halo_send + rec * so, (size_t)(rec * p.n_send), ncclDouble, peer_ranks[k], cm, st);
+        if (flags && p.n_recv && r == ncclSuccess)
+          r = R.Recv(f_recv + ro, (size_t)p.n_recv, ncclUint8, peer_ranks[k], cm, st);
+        if (flags && p.n_send && r == ncclSuccess)
+          r = R.Send(f_send + so, (size_t)p.n_send, ncclUint8, peer_ranks[k], cm, st);
         so += p.n_send;
         ro += p.n_recv;
       }
@@ -2165,7 +2180,10 @@ extern "C"
         // communicator so that no rank waits for a message that will never come, and report
         return abort_comm(PFM_ERR_COMM, std::string("RCCL: ") + R.GetErrorString(r));
       }
-    rc = launch_halo_all(c->v, c->d_recv_all, c->d_recv_ptr, (int)c->peers.size(), c->n_recv_all, c->d_halo_recv, 1, st);
+    if (values)
+      rc = launch_halo_all(c->v, c->d_recv_all, c->d_recv_ptr, (int)c->peers.size(), c->n_recv_all, c->d_halo_recv, 1, st);
+    if (rc == PFM_OK && flags)
+      rc = launch_halo_flags_all(c->v, c->d_recv_all, c->n_recv_all, f_recv, 1, st);
     if (rc)
       return fail(c, rc, "halo unpack launch failed");
     return PFM_OK;
@@ -2179,6 +2197,35 @@ extern "C"
       return PFM_OK;
     (void)hipSetDevice(c->device);
     return halo_exchange_on(c, comm, peer_ranks, c->stream);
+  }
+
+  int pfm_halo_exchange_flags(pfm_ctx *c, void *comm, const int *peer_ranks)
+  {
+    if (!c || (!c->peers.empty() && (!comm || !peer_ranks)))
+      return PFM_ERR_BAD_ARG;
+    if (c->peers.empty())
+      return PFM_OK;
+    (void)hipSetDevice(c->device);
+    return halo_exchange_on(c, comm, peer_ranks, c->stream, HALO_FLAGS);
+  }
+
+  // cracks.cc:2826-2890 on a rank with ghost peers (include/pfm_newton.h): owned update -> scatter -> values and flags in
+  // one group -> distribution of the hanging nodes, owned and ghost
+  int pfm_active_set_exchange(pfm_ctx *c, void *comm, const int *peer_ranks, const double *d_residual_total, const double *d_mass,
+                              double c_const, double *d_solution, const double *d_old_solution, int32_t *d_cycle_counter,
+                              int64_t *counts)
+  {
+    if (!c || !d_residual_total || !d_mass || !d_solution || !d_old_solution || !d_cycle_counter || !counts ||
+        (!c->peers.empty() && (!comm || !peer_ranks)))
+      return PFM_ERR_BAD_ARG;
+    int rc = pfm_active_set_owned_device(c, d_residual_total, d_mass, c_const, d_solution, d_old_solution, d_cycle_counter, counts);
+    if (rc == PFM_OK)
+      rc = pfm_state_set_solution(c, d_solution, 1);
+    if (rc == PFM_OK && !c->peers.empty())
+      rc = halo_exchange_on(c, comm, peer_ranks, c->stream, HALO_VALUES | HALO_FLAGS);
+    if (rc == PFM_OK)
+      rc = pfm_distribute_hanging_device(c, d_solution);
+    return rc;
   }
 
   // cartesian overlay: the slots of the regular rows follow the order of the node-graph rows (pfm_pattern_bind may change it);

@@ -169,6 +169,10 @@ namespace pfm
                       double *d_buf, int unpack, hipStream_t s);
   int launch_halo_unpack(const DevView &v, const int32_t *d_nodes, int64_t n, const double *d_buf,
                          hipStream_t s);
+  // pfm_newton.hip: the flag bytes of a concatenated halo list, one byte per entry (pfm_halo_pack_flags_all / _unpack_)
+  int launch_halo_flags_all(const DevView &v, const int32_t *d_nodes, int64_t n_total, uint8_t *d_buf, int unpack, hipStream_t s);
+  // pfm_ctx::buf_flag_send / buf_flag_recv for the registered lists (grow-only, counted in device_bytes)
+  int reserve_flag_halo_buffers(pfm_ctx *c);
   // The launchers of the cartesian family: each carries out its part of pl = plan_cart(v, cv, p, ...) (pfm_cart_plan.h).
   // s_side: the stream the caller forked off s for the phase-field kernel of the pair or for the residual kernel, else s.
   // d_scal: the MatScal of the current parameters on the device (upload_mat_scal; by value it would pin 900 bytes of
@@ -361,6 +365,9 @@ struct pfm_ctx
   uint8_t *d_cell_ring_reduced = nullptr;
   // scratch of the Newton-side sweeps (pfm_newton.hip): the 3 counts of pfm_active_set_device
   pfm::DevBuf buf_counts;
+  pfm::DevBuf buf_hn_nodes;      // pfm_distribute_hanging_device: node of entry k of the hanging table (-1: none), built at its first call
+  bool hn_nodes_ready = false;
+  pfm::DevBuf buf_flag_send, buf_flag_recv; // message buffers of pfm_halo_exchange_flags, one byte per halo node
   // gather tables of the cells at hanging vertices (DevView::hs_*): destination rows, their entry lists (hc * 32 + index:
   // index < 16 = resolved node i of cell hc, 16 + a = the hanging vertex a's own row), ascending per row
   int32_t *d_hg_rows = nullptr;

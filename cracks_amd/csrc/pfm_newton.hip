@@ -4,6 +4,8 @@
 //   pfm_diag_mass_device    assemble_diag_mass_matrix                 cracks.cc:2514-2562
 //   pfm_active_set_device   active-set predicate + cycle counter      cracks.cc:2837-2886, 2903-2909
 //                           + constraints_hanging_nodes.distribute    cracks.cc:2888-2890
+//   pfm_active_set_owned_device, pfm_halo_pack_flags_all / _unpack_flags_all, pfm_distribute_hanging_device
+//                           the same block in the pieces of a rank with ghost peers (pfm_active_set_exchange, pfm_host.cpp)
 //   pfm_functionals         compute_energy, compute_tcv               cracks.cc:3615-3701, 3553-3611
 //
 // All three work on any Q1 mesh (MappingQ1 geometry per cell) with the node state / tables of the context.  The Q1
@@ -144,6 +146,17 @@ namespace pfm
         }
     }
 
+    // line k of the hanging table: sum_j hn_weights[j] * value_of(parent j), in table order -- the one expression behind
+    // both distributions below, so that they leave the same bits
+    template <class ValueOf>
+    __device__ __forceinline__ double hanging_sum(const DevView &v, int k, ValueOf value_of)
+    {
+      double s = 0.0;
+      for (long long j = v.hn_ptr[k]; j < v.hn_ptr[k + 1]; ++j)
+        s += v.hn_weights[j] * value_of(v.hn_parents[j]);
+      return s;
+    }
+
     // constraints_hanging_nodes.distribute(solution): thread <-> (hanging node, component)
     template <int dim>
     __global__ __launch_bounds__(256) void k_distribute_hanging(DevView v, double *__restrict__ solution)
@@ -152,11 +165,56 @@ namespace pfm
       const int P = (int)(gid / (dim + 1)), c = (int)(gid % (dim + 1));
       if (P >= v.n_owned || v.hn_index[P] < 0)
         return;
-      const int k = v.hn_index[P];
-      double s = 0.0;
-      for (long long j = v.hn_ptr[k]; j < v.hn_ptr[k + 1]; ++j)
-        s += v.hn_weights[j] * solution[dof_of<dim>(v, v.hn_parents[j], c)];
-      solution[dof_of<dim>(v, P, c)] = s;
+      solution[dof_of<dim>(v, P, c)] = hanging_sum(v, v.hn_index[P], [&](int parent) { return solution[dof_of<dim>(v, parent, c)]; });
+    }
+
+    // hn_nodes[k] = the node of line k of the hanging table (the context keeps node -> k only): thread <-> local node
+    __global__ __launch_bounds__(256) void k_hanging_nodes(DevView v, int32_t *__restrict__ hn_nodes)
+    {
+      const int P = blockIdx.x * blockDim.x + threadIdx.x;
+      if (P < v.n_nodes && v.hn_index[P] >= 0)
+        hn_nodes[v.hn_index[P]] = P;
+    }
+
+    // the same distribution where a parent may be a ghost: on the node arrays of the solution, over ALL local hanging nodes
+    // (a ghost one is recomputed from its parents, which are local); owned ones are also written to the dof vector.
+    // thread <-> (line of the hanging table, component).  Parents never hang: the reads and the writes are disjoint.
+    template <int dim>
+    __global__ __launch_bounds__(256) void k_distribute_hanging_state(DevView v, const int32_t *__restrict__ hn_nodes, int n_hanging,
+                                                                      double *__restrict__ solution /* or nullptr */)
+    {
+      const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+      const int k = (int)(gid / (dim + 1)), c = (int)(gid % (dim + 1));
+      if (k >= n_hanging)
+        return;
+      const int P = hn_nodes[k];
+      if (P < 0)
+        return; // a line whose node another line of the table overrides
+      double *field = c == dim ? v.phi : (c == 0 ? v.u[0] : (c == 1 ? v.u[1] : v.u[2]));
+      const double s = hanging_sum(v, k, [&](int parent) { return field[parent]; });
+      field[P] = s;
+      if (solution && P < v.n_owned)
+        solution[dof_of<dim>(v, P, c)] = s;
+    }
+
+    // flag bytes of the nodes of a concatenated halo list, one byte per entry: the message of peer k starts at byte ptr[k],
+    // so entry j of the list is byte j of the buffer and no peer has to be looked up (k_halo_all needs its peer for the
+    // field-major layout inside a message).  UNPACK merges the active-set line of the phase field (bit dim) only.
+    template <bool UNPACK>
+    __global__ __launch_bounds__(256) void k_halo_flags_all(int dim, uint8_t *__restrict__ node_flags, const int32_t *__restrict__ nodes,
+                                                            long long n_total, uint8_t *__restrict__ buf)
+    {
+      const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+      if (j >= n_total)
+        return;
+      const int node = nodes[j];
+      if constexpr (UNPACK)
+        {
+          const unsigned m = 1u << dim;
+          node_flags[node] = (uint8_t)((node_flags[node] & ~m) | (buf[j] & m));
+        }
+      else
+        buf[j] = node_flags[node];
     }
 
     // ---- energies and total crack volume: thread <-> cell, QGauss(3)^dim, MappingQ1; fixed-order reduction
@@ -277,6 +335,26 @@ namespace pfm
         out[1] = r;
     }
   } // namespace
+
+  int launch_halo_flags_all(const DevView &v, const int32_t *d_nodes, int64_t n_total, uint8_t *d_buf, int unpack, hipStream_t s)
+  {
+    if (n_total <= 0)
+      return PFM_OK;
+    const unsigned nb = (unsigned)((n_total + 255) / 256);
+    uint8_t *flags = const_cast<uint8_t *>(v.node_flags);
+    if (unpack)
+      hipLaunchKernelGGL(k_halo_flags_all<true>, dim3(nb), dim3(256), 0, s, v.dim, flags, d_nodes, (long long)n_total, d_buf);
+    else
+      hipLaunchKernelGGL(k_halo_flags_all<false>, dim3(nb), dim3(256), 0, s, v.dim, flags, d_nodes, (long long)n_total, d_buf);
+    return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
+  }
+
+  int reserve_flag_halo_buffers(pfm_ctx *c)
+  {
+    if (int rc = dev_buf_reserve(c, c->buf_flag_send, (size_t)c->n_send_all, "flag halo send buffer"))
+      return rc;
+    return dev_buf_reserve(c, c->buf_flag_recv, (size_t)c->n_recv_all, "flag halo receive buffer");
+  }
 } // namespace pfm
 
 using namespace pfm;
@@ -298,13 +376,10 @@ extern "C"
     return hipGetLastError() == hipSuccess ? PFM_OK : fail(c, PFM_ERR_HIP, "k_diag_mass launch");
   }
 
-  int pfm_active_set_device(pfm_ctx *c, const double *d_residual_total, const double *d_mass, double c_const,
-                            double *d_solution, const double *d_old_solution, int32_t *d_cycle_counter, int64_t *counts)
+  // k_active_set over the owned nodes; distribute: followed by k_distribute_hanging on d_solution (every parent owned)
+  static int active_set_sweep(pfm_ctx *c, const double *d_residual_total, const double *d_mass, double c_const, double *d_solution,
+                              const double *d_old_solution, int32_t *d_cycle_counter, int64_t *counts, bool distribute)
   {
-    if (!c || !d_residual_total || !d_mass || !d_solution || !d_old_solution || !d_cycle_counter || !counts)
-      return PFM_ERR_BAD_ARG;
-    if (c->v.n_owned != c->v.n_nodes && c->v.hn_index)
-      return fail(c, PFM_ERR_UNSUPPORTED, "hanging nodes on a partitioned mesh");
     (void)hipSetDevice(c->device);
     if (int rc = dev_buf_reserve(c, c->buf_counts, 3 * sizeof(unsigned long long), "counts"))
       return rc;
@@ -316,7 +391,7 @@ extern "C"
     if (nb)
       PFM_LAUNCH_DIM(c->v.dim, k_active_set, dim3(nb), dim3(256), c->stream, c->v, flags, d_residual_total, d_mass, c_const,
                      d_solution, d_old_solution, d_cycle_counter, d_counts);
-    if (c->v.hn_index && nb)
+    if (distribute && c->v.hn_index && nb)
       {
         // we might have changed values of the solution, so fix the hanging nodes (cracks.cc:2888-2890)
         const long long n = (long long)c->v.n_owned * (c->v.dim + 1);
@@ -333,6 +408,67 @@ extern "C"
     counts[1] = (int64_t)h[1];
     counts[2] = h[2] != 0; // number of waves that saw a change -> flag
     return PFM_OK;
+  }
+
+  int pfm_active_set_device(pfm_ctx *c, const double *d_residual_total, const double *d_mass, double c_const,
+                            double *d_solution, const double *d_old_solution, int32_t *d_cycle_counter, int64_t *counts)
+  {
+    if (!c || !d_residual_total || !d_mass || !d_solution || !d_old_solution || !d_cycle_counter || !counts)
+      return PFM_ERR_BAD_ARG;
+    if (c->v.n_owned != c->v.n_nodes && c->v.hn_index)
+      return fail(c, PFM_ERR_UNSUPPORTED, "hanging nodes on a partitioned mesh");
+    return active_set_sweep(c, d_residual_total, d_mass, c_const, d_solution, d_old_solution, d_cycle_counter, counts, true);
+  }
+
+  int pfm_active_set_owned_device(pfm_ctx *c, const double *d_residual_total, const double *d_mass, double c_const,
+                                  double *d_solution, const double *d_old_solution, int32_t *d_cycle_counter, int64_t *counts)
+  {
+    if (!c || !d_residual_total || !d_mass || !d_solution || !d_old_solution || !d_cycle_counter || !counts)
+      return PFM_ERR_BAD_ARG;
+    return active_set_sweep(c, d_residual_total, d_mass, c_const, d_solution, d_old_solution, d_cycle_counter, counts, false);
+  }
+
+  int pfm_halo_pack_flags_all(pfm_ctx *c, uint8_t *d_buf_all)
+  {
+    if (!c || (!d_buf_all && c->n_send_all))
+      return PFM_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    const int rc = launch_halo_flags_all(c->v, c->d_send_all, c->n_send_all, d_buf_all, 0, c->stream);
+    return rc ? fail(c, rc, "k_halo_flags_all launch") : PFM_OK;
+  }
+
+  int pfm_halo_unpack_flags_all(pfm_ctx *c, const uint8_t *d_buf_all)
+  {
+    if (!c || (!d_buf_all && c->n_recv_all))
+      return PFM_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    const int rc = launch_halo_flags_all(c->v, c->d_recv_all, c->n_recv_all, const_cast<uint8_t *>(d_buf_all), 1, c->stream);
+    return rc ? fail(c, rc, "k_halo_flags_all launch") : PFM_OK;
+  }
+
+  int pfm_distribute_hanging_device(pfm_ctx *c, double *d_solution)
+  {
+    if (!c)
+      return PFM_ERR_BAD_ARG;
+    if (!c->v.hn_index || c->n_hanging <= 0)
+      return PFM_OK;
+    (void)hipSetDevice(c->device);
+    if (!c->hn_nodes_ready)
+      {
+        if (int rc = dev_buf_reserve(c, c->buf_hn_nodes, sizeof(int32_t) * (size_t)c->n_hanging, "hanging nodes"))
+          return rc;
+        if (hipMemsetAsync(c->buf_hn_nodes.p, 0xff, sizeof(int32_t) * (size_t)c->n_hanging, c->stream) != hipSuccess)
+          return fail(c, PFM_ERR_HIP, "hanging nodes memset");
+        hipLaunchKernelGGL(k_hanging_nodes, dim3((unsigned)((c->v.n_nodes + 255) / 256)), dim3(256), 0, c->stream, c->v,
+                           c->buf_hn_nodes.as<int32_t>());
+        if (hipGetLastError() != hipSuccess)
+          return fail(c, PFM_ERR_HIP, "k_hanging_nodes launch");
+        c->hn_nodes_ready = true;
+      }
+    const long long n = (long long)c->n_hanging * (c->v.dim + 1);
+    PFM_LAUNCH_DIM(c->v.dim, k_distribute_hanging_state, dim3((unsigned)((n + 255) / 256)), dim3(256), c->stream, c->v,
+                   c->buf_hn_nodes.as<int32_t>(), (int)c->n_hanging, d_solution);
+    return hipGetLastError() == hipSuccess ? PFM_OK : fail(c, PFM_ERR_HIP, "k_distribute_hanging_state launch");
   }
 
   int pfm_get_constraints(pfm_ctx *c, uint8_t *node_flags)

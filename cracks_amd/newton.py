@@ -213,6 +213,127 @@ def line_search_numpy(residual_norm_of: Callable[[np.ndarray], float], solution:
     return {"steps": step, "accepted": accepted, "trial": trial, "solution": sol, "update": upd}
 
 
+def _copy_along_halo(lps, r, k, src_of_rank):
+    """what rank ``r`` receives from its k-th peer: ``src_of_rank[s]`` at the peer's send nodes for ``r``, in list order"""
+    s = lps[r].peers[k]
+    ks = lps[s].peers.index(r)
+    nodes = lps[s].send_nodes[int(lps[s].send_ptr[ks]):int(lps[s].send_ptr[ks + 1])]
+    assert nodes.size == int(lps[r].recv_ptr[k + 1] - lps[r].recv_ptr[k])
+    return src_of_rank[s][nodes]
+
+
+def active_set_partitioned_numpy(lps, c: float, res_phi, mass, u, phi, phi_old, cyc, flags) -> dict:
+    """The active-set block of cracks.cc:2826-2890, 2903-2909 on the ``LocalProblem``s of ``partition.py``, rank by rank --
+    the host statement of ``pfm_active_set_exchange`` (include/pfm_newton.h) and the reference of its tests.  All arguments
+    but ``c`` are lists with one array per rank:
+
+      ``res_phi[r]``, ``mass[r]``, ``phi_old[r]``, ``cyc[r]``   over the owned nodes of rank r (phase-field residual_total,
+                                                                diag_mass, old solution, cycle counter)
+      ``u[r]`` [n_local, dim], ``phi[r]`` [n_local]             the node arrays of the solution; only the owned entries are
+                                                                read before the exchange
+      ``flags[r]`` [n_local] uint8                              the flag bytes (bit c: dof (node, c) has a constraint line)
+
+    1. owned nodes that do not hang: the criterion ``res / mass + c (phi - phi_old) <= 0 and cyc < 5`` keeps a dof inactive,
+       every operation one numpy operation on doubles (rounded on its own); an active dof gets ``phi = phi_old`` and bit
+       ``dim`` of its flag byte, a dof that leaves the set increments its counter;
+    2. the exchange: ``u``, ``phi`` and bit ``dim`` of the flag byte of every ghost node are copied from its owner, along
+       ``send_nodes`` / ``recv_nodes``; the displacement bits of ghost bytes stay;
+    3. every local hanging node, owned or ghost, becomes ``sum_j w_j parent_j`` of the local arrays, added in table order.
+
+    The inputs are not modified.  Returns the lists ``u``, ``phi``, ``cyc``, ``flags`` and ``counts`` (per rank: active,
+    cycling, changed -- the caller sums them as Utilities::MPI::sum does)."""
+    dim = lps[0].mesh.dim
+    bit = np.uint8(1 << dim)
+    u = [np.array(a, np.float64) for a in u]
+    phi = [np.array(a, np.float64) for a in phi]
+    cyc = [np.array(a) for a in cyc]
+    flags = [np.array(a, np.uint8) for a in flags]
+    counts = []
+    for r, lp in enumerate(lps):
+        no = lp.n_owned
+        hanging = np.zeros(lp.mesh.n_nodes, bool)
+        hanging[lp.mesh.hn_nodes] = True
+        was = (flags[r][:no] & bit) != 0
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            q = np.asarray(res_phi[r], np.float64) / np.asarray(mass[r], np.float64)
+            cg = c * (phi[r][:no] - np.asarray(phi_old[r], np.float64))
+            crit = q + cg
+        inactive = (crit <= 0.0) & (cyc[r] < 5)
+        now = ~hanging[:no] & ~inactive
+        n_cycling = int(np.sum(now & (cyc[r] >= 5)))
+        phi[r][:no][now] = np.asarray(phi_old[r], np.float64)[now]
+        cyc[r][was & ~now] += 1
+        flags[r][:no] = (flags[r][:no] & ~bit) | (now.astype(np.uint8) << dim).astype(np.uint8)
+        counts.append((int(now.sum()), n_cycling, int(np.any(was != now))))
+    sent_u, sent_phi, sent_flags = [a.copy() for a in u], [a.copy() for a in phi], [a.copy() for a in flags]
+    for r, lp in enumerate(lps):
+        for k in range(len(lp.peers)):
+            to = lp.recv_nodes[int(lp.recv_ptr[k]):int(lp.recv_ptr[k + 1])]
+            u[r][to] = _copy_along_halo(lps, r, k, sent_u)
+            phi[r][to] = _copy_along_halo(lps, r, k, sent_phi)
+            flags[r][to] = (flags[r][to] & ~bit) | (_copy_along_halo(lps, r, k, sent_flags) & bit)
+    for r, lp in enumerate(lps):
+        m = lp.mesh
+        if not m.hn_nodes.size:
+            continue
+        n_par = np.diff(m.hn_ptr)
+        for field in [u[r][:, d] for d in range(dim)] + [phi[r]]:  # (views: the sums land in u / phi)
+            s = np.zeros(m.hn_nodes.size)
+            for j in range(int(n_par.max())):
+                has = n_par > j
+                at = m.hn_ptr[:-1][has] + j
+                s[has] = s[has] + m.hn_weights[at] * field[m.hn_parents[at]]
+            field[m.hn_nodes] = s
+    return {"u": u, "phi": phi, "cyc": cyc, "flags": flags, "counts": counts}
+
+
+def active_set_partitioned(ctxs, lps, res_ptrs, mass_ptrs, c: float, sol_ptrs, old_ptrs, cyc_ptrs):
+    """``pfm_active_set_exchange`` for N contexts that live in one process on one device: per rank
+    ``active_set_owned_device`` and ``state_set_solution_device``, then the messages of ``halo_pack_all`` and
+    ``halo_pack_flags_all`` are copied between the contexts' buffers (in place of the RCCL group) and unpacked, then
+    ``distribute_hanging_device``.  The ``*_ptrs`` are lists of device pointers, the arguments of ``active_set_device`` per
+    rank.  Returns the counts per rank.  Every context must have its halo lists registered (``halo_register``)."""
+    import torch
+
+    dim = ctxs[0].dim
+    rec = dim + 3
+    counts = []
+    for r, ctx in enumerate(ctxs):
+        counts.append(ctx.active_set_owned_device(res_ptrs[r], mass_ptrs[r], c, sol_ptrs[r], old_ptrs[r], cyc_ptrs[r]))
+        ctx.state_set_solution_device(sol_ptrs[r])
+    values, flag_bytes = [], []
+    for lp, ctx in zip(lps, ctxs):
+        n = int(lp.send_ptr[-1])
+        v = torch.zeros(max(n, 1) * rec, dtype=torch.float64, device="cuda")
+        f = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda")
+        if n:
+            ctx.halo_pack_all(v.data_ptr())
+            ctx.halo_pack_flags_all(f.data_ptr())
+        values.append(v)
+        flag_bytes.append(f)
+    torch.cuda.synchronize()  # the contexts run on streams of their own
+    for r, (lp, ctx) in enumerate(zip(lps, ctxs)):
+        n = int(lp.recv_ptr[-1])
+        if n == 0:
+            continue
+        v = torch.zeros(n * rec, dtype=torch.float64, device="cuda")
+        f = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        for k, s in enumerate(lp.peers):
+            ks = lps[s].peers.index(r)
+            a, b = int(lps[s].send_ptr[ks]), int(lps[s].send_ptr[ks + 1])
+            o = int(lp.recv_ptr[k])
+            v[o * rec:(o + b - a) * rec] = values[s][a * rec:b * rec]
+            f[o:o + b - a] = flag_bytes[s][a:b]
+        torch.cuda.synchronize()
+        ctx.halo_unpack_all(v.data_ptr())
+        ctx.halo_unpack_flags_all(f.data_ptr())
+        torch.cuda.synchronize()  # v and f are released when the loop moves on
+    for r, ctx in enumerate(ctxs):
+        ctx.distribute_hanging_device(sol_ptrs[r])
+    torch.cuda.synchronize()
+    return counts
+
+
 @dataclass
 class ProblemSetup:
     mesh: M.Mesh

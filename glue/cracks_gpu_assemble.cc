@@ -55,6 +55,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <map>
 #include <set>
@@ -102,6 +103,9 @@ namespace pfm_glue_detail
     // line_search(): newton_update and, for the stepwise form, saved_solution on the device; host staging
     double *d_upd = nullptr, *d_saved = nullptr;
     std::vector<double> h_upd, h_tmp;
+    // active_set_update(): diag_mass of the owned nodes (made at the first call after a rebuild) and the cycle counter
+    double *d_mass = nullptr;
+    int32_t *d_cycle = nullptr;
     std::vector<uint8_t> flags;
     // cells shipped by other ranks (hanging-node closure) and what is needed to keep their nodes' flags current
     struct ShippedCell
@@ -141,8 +145,9 @@ namespace pfm_glue_detail
     //   line_search_stepwise: line_search() runs the host loop of a rank with ghost peers (vector statements, scatter + halo +
     //                      assembly, pfm_residual_norms, MPI sum / max) also where pfm_line_search_device would do: the two
     //                      forms give the same vectors and the same result (tests/test_gpu_glue_line_search.py).
-    //   active_set_on_device: the host evaluates the active set with pfm_active_set_device on d_res[1]; together with
-    //                      residual_to_host == false, line_search() then leaves system_total_residual on the device.
+    //   active_set_on_device: the host evaluates the active set on d_res[1] with active_set_update() (pfm_active_set_exchange:
+    //                      any rank count, hanging nodes included); together with residual_to_host == false, line_search()
+    //                      then leaves system_total_residual on the device.
     bool line_search_stepwise = false;
     bool active_set_on_device = false;
     bool pin_host_matrix = false;
@@ -194,12 +199,15 @@ namespace pfm_glue_detail
             (void)hipFree(p);
           p = nullptr;
         }
-      for (double **p : {&d_upd, &d_saved})
+      for (double **p : {&d_upd, &d_saved, &d_mass})
         {
           if (*p)
             (void)hipFree(*p);
           *p = nullptr;
         }
+      if (d_cycle)
+        (void)hipFree(d_cycle);
+      d_cycle = nullptr;
     }
 
     // ---------------------------------------------------------------------------------------------------------
@@ -854,6 +862,55 @@ namespace pfm_glue_detail
       return r;
     }
 
+    // Start of newton_active_set() (cracks.cc:2811): the cycle counter of active_set_update() back to zero.
+    void reset_cycle_counter()
+    {
+      if (!d_cycle)
+        AssertThrow(hipMalloc((void **)&d_cycle, sizeof(int32_t) * std::max<size_t>((size_t)n_owned, 1)) == hipSuccess, ExcMessage("hipMalloc (cycle counter)"));
+      AssertThrow(hipMemset(d_cycle, 0, sizeof(int32_t) * (size_t)n_owned) == hipSuccess, ExcMessage("hipMemset (cycle counter)"));
+    }
+
+    // The active-set block of newton_active_set() (cracks.cc:2826-2890 with the counter of 2903-2909) on the device copy of
+    // system_total_residual (d_res[1], as the last residual assembly or line_search() left it), for a host that has set
+    // active_set_on_device: one collective call, pfm_active_set_exchange, on ranks with ghost peers and hanging nodes too.
+    // To be called behind an assemble() (old_solution and the Dirichlet bits of the flag bytes are that call's) and a
+    // reset_cycle_counter() at the start of the Newton loop.  P.solution is the context's copy unless the host has changed
+    // it since (compared on the host, uploaded if so); it comes back with one transfer, hanging nodes distributed.
+    // Afterwards the context's node state and flag bytes, ghosts included, are those of the new set, and `flags` holds the
+    // bytes of the local nodes: bit dim of flags[n] says whether the phase-field dof of node n is active, which is what the
+    // host's constraints_update needs (add_line + set_inhomogeneity(0), cracks.cc:2878-2879) before the next assemble()
+    // rebuilds the bytes from it.  The Dirichlet bits of ghost nodes remain the host's (set_newton_bc, through assemble()).
+    // Returns {active dofs, cycling dofs, 1 if the set changed}, summed over the ranks (cracks.cc:2893-2895, 2914).
+    template <class Problem>
+    std::array<int64_t, 3> active_set_update(Problem &P, const double c_const)
+    {
+      AssertThrow(ctx && state_complete, ExcMessage("PfmGlue::active_set_update: call assemble() first"));
+      AssertThrow(active_set_on_device, ExcMessage("PfmGlue::active_set_update: set active_set_on_device"));
+      AssertThrow(d_cycle, ExcMessage("PfmGlue::active_set_update: call reset_cycle_counter() at the start of the Newton loop"));
+      const size_t nd = (size_t)n_owned * (dim + 1);
+      if (!d_mass)
+        {
+          AssertThrow(hipMalloc((void **)&d_mass, sizeof(double) * std::max<size_t>((size_t)n_owned, 1)) == hipSuccess, ExcMessage("hipMalloc (diag_mass)"));
+          PFM_CALL(ctx, pfm_diag_mass_device(ctx, d_mass));
+        }
+      gather_owned(P.solution, h_tmp);
+      if (h_tmp != h_vec[0]) // the host has written the solution since the last assemble() / line_search()
+        {
+          h_vec[0].swap(h_tmp);
+          AssertThrow(hipMemcpy(d_vec[0], h_vec[0].data(), sizeof(double) * nd, hipMemcpyHostToDevice) == hipSuccess, ExcMessage("H2D"));
+        }
+      int64_t local[3] = {0, 0, 0};
+      PFM_CALL(ctx, pfm_active_set_exchange(ctx, comm, comm ? peer_ranks.data() : nullptr, d_res[1], d_mass, c_const, d_vec[0], d_vec[1],
+                                            d_cycle, local));
+      PFM_CALL(ctx, pfm_get_constraints(ctx, flags.data())); // (synchronises the context's stream)
+      const int rc = pfm_sync_status(ctx);
+      AssertThrow(rc == PFM_OK, ExcMessage(pfm_last_error(ctx)));
+      AssertThrow(hipMemcpy(h_vec[0].data(), d_vec[0], sizeof(double) * nd, hipMemcpyDeviceToHost) == hipSuccess, ExcMessage("D2H"));
+      scatter_owned(h_vec[0], P.solution);
+      return {Utilities::MPI::sum(local[0], P.mpi_com), Utilities::MPI::sum(local[1], P.mpi_com),
+              Utilities::MPI::max(local[2], P.mpi_com)};
+    }
+
     // global dof of (local node, component)
     // deal.II-knowledge (A) -- verify on a real install: loop over the cells, for every vertex v and component comp
     //   Assert(global_dof_of(P, node_of_phi_dof.at(cell->vertex_dof_index(v, dim)), comp) == cell->vertex_dof_index(v, comp)).
@@ -921,5 +978,9 @@ namespace pfm_glue_detail
 //   the whole loop (cracks.cc:2942-2957 / 3048-3062):
 //                              const auto ls = pfm_glue.line_search(*this, newton_residual, max_no_line_search_steps, line_search_damping);
 //                              line_search_step = ls.steps;  new_newton_residual = ls.norms[0];  residual_relevant = system_total_residual;
+//   the active-set block (cracks.cc:2826-2890, 2903-2909) with pfm_glue.active_set_on_device = true:
+//                              pfm_glue.reset_cycle_counter();                                  // where cracks.cc:2811 zeroes it
+//                              const auto n = pfm_glue.active_set_update(*this, 1e1 * E_modulus); // {active, cycling, changed}
+//                              then constraints_update from bit dim of pfm_glue.flags[node]
 
 #endif // PFM_WITH_DEALII

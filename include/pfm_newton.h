@@ -6,6 +6,7 @@
  * Reference interfaces replaced (all private members of FracturePhaseFieldProblem<dim>, cracks.cc):
  *   assemble_diag_mass_matrix()                       cracks.cc:2514-2562   -> pfm_diag_mass_device
  *   active-set block of newton_active_set()           cracks.cc:2826-2909   -> pfm_active_set_device
+ *   the same block on a rank with ghost peers         cracks.cc:2826-2890, 2788 -> pfm_active_set_exchange
  *   compute_energy(), compute_tcv()                   cracks.cc:3615-3701, 3553-3611 -> pfm_functionals
  *   constraints_update.set_zero(residual); residual.l2_norm() / linfty_norm()
  *                                                     cracks.cc:2791-2794, 2918-2919, 2947-2949 -> pfm_residual_norms
@@ -46,10 +47,72 @@ int pfm_diag_mass_device(pfm_ctx *ctx, double *d_mass);
  * the caller at the start of newton_active_set (cracks.cc:2811).
  * counts[0] = owned active dofs, counts[1] = cycling dofs among them, counts[2] = 1 if the set changed.
  * Synchronous (the counts are returned on the host, as the reference prints them).  On a partitioned mesh the
- * flags of ghost nodes are the caller's to exchange (pfm_get_constraints / pfm_set_constraints). */
+ * flags of ghost nodes are the caller's to exchange (pfm_get_constraints / pfm_set_constraints, or on the device
+ * pfm_halo_exchange_flags; with hanging nodes: pfm_active_set_exchange). */
 int pfm_active_set_device(pfm_ctx *ctx, const double *d_residual_total, const double *d_mass, double c,
                           double *d_solution, const double *d_old_solution, int32_t *d_cycle_counter,
                           int64_t counts[3]);
+
+/* ---- the active-set update on a partitioned mesh (hanging nodes included): pfm_active_set_device in pieces that a rank
+ * with ghost peers can compose, and the composition in one collective call.  The solution, the residual and the flag
+ * bytes stay on the device; per Newton step one byte per halo node travels next to the halo values. */
+
+/* The active-set predicate of cracks.cc:2837-2886 and the cycle counter of 2903-2909 WITHOUT the re-distribution of
+ * 2888-2890: the arguments, criterion, rounding (no fused multiply-add), cycle counter, phi := phi_old, flag bit `dim`
+ * and counts of pfm_active_set_device (the same kernel), over the owned nodes that do not hang, on ANY context -- a
+ * partitioned one with hanging nodes too.  Hanging nodes keep their (now stale) values in d_solution until
+ * pfm_distribute_hanging_device; ghost flag bytes are not touched (pfm_halo_exchange_flags).  Synchronous. */
+int pfm_active_set_owned_device(pfm_ctx *ctx, const double *d_residual_total, const double *d_mass, double c,
+                                double *d_solution, const double *d_old_solution, int32_t *d_cycle_counter,
+                                int64_t counts[3]);
+
+/* The import of the ghost nodes' active-set lines (what IndexSet active_set_locally_relevant / constraints_update hold of
+ * other ranks' dofs after cracks.cc:2826-2890).  The message is ONE BYTE per node, the flag byte of the context; the
+ * message of peer k starts at byte send_ptr[k] resp. recv_ptr[k] of the lists given to pfm_halo_register.
+ * PFM_HALO_DOUBLES_PER_NODE and the messages of pfm_halo_pack_all / pfm_halo_exchange are not affected.
+ *   pack:    d_buf_all[j] = flag byte of send node j                              (device buffer, n_send bytes)
+ *   unpack:  bit `dim` (the active-set line of the phase field) of d_buf_all[j] replaces bit `dim` of the flag byte of
+ *            ghost node recv_nodes[j]; its displacement bits stay what pfm_set_constraints gave -- they are
+ *            set_newton_bc's (cracks.cc:2711-2714) and do not change inside the Newton loop.  Owned nodes are never
+ *            written.
+ * Asynchronous on the context's stream.  A context without peers: PFM_OK, nothing launched. */
+int pfm_halo_pack_flags_all(pfm_ctx *ctx, uint8_t *d_buf_all);
+int pfm_halo_unpack_flags_all(pfm_ctx *ctx, const uint8_t *d_buf_all);
+/* pack -> one grouped ncclSend / ncclRecv per peer (ncclUint8) on the context's stream -> unpack, in message buffers of
+ * the context (allocated at the first call, counted in pfm_ctx_device_bytes).  The handle rules, the error path (a failure
+ * after the group has been opened aborts an owned communicator and disables the handle) and the collective rule (every
+ * rank of a peer pair calls it, in the same order relative to its other exchanges) are pfm_halo_exchange's.  Like that
+ * entry it is launch-ready but has NOT run between two ranks yet; the protocol is tested with in-process copies of the
+ * pack / unpack buffers.  A context without peers: PFM_OK, nothing launched, comm may be NULL. */
+int pfm_halo_exchange_flags(pfm_ctx *ctx, void *comm, const int *peer_ranks);
+
+/* constraints_hanging_nodes.distribute(solution) (cracks.cc:2888-2890 after the active set, and 2788 after
+ * set_initial_bc) for a context whose hanging nodes may have ghost parents.  For every local hanging node, owned or ghost,
+ * and every component:  value = sum_j hn_weights[j] * parent_j  in table order, where the parents are read from the
+ * context's node arrays of the solution (as last scattered by pfm_state_set / pfm_state_set_solution and imported by the
+ * halo) and the result is written to those arrays; for OWNED hanging nodes it is also written to d_solution (device vector
+ * over the owned dofs in the context's layout; may be NULL: node arrays only).  phi_old / phi_oldold are not touched.
+ * Ghost hanging nodes are recomputed here and not imported: their parents are local nodes (the ghost layer is closed under
+ * the hanging table), so no second exchange follows.  The table is closed (parents never hang): the reads and the writes
+ * are disjoint and the call is idempotent.  On an unpartitioned context the values equal what pfm_active_set_device leaves
+ * in d_solution bit for bit (one device function forms the sum in both).  Asynchronous on the context's stream.  A context
+ * without hanging nodes: PFM_OK, nothing launched. */
+int pfm_distribute_hanging_device(pfm_ctx *ctx, double *d_solution /* may be NULL */);
+
+/* cracks.cc:2826-2890 on a rank with ghost peers, in one collective call:
+ *   pfm_active_set_owned_device(...);  pfm_state_set_solution(d_solution, on_device = 1);
+ *   the halo values (pfm_halo_exchange's messages) and the flag bytes (pfm_halo_exchange_flags' messages) in ONE RCCL group;
+ *   pfm_distribute_hanging_device(d_solution).
+ * Afterwards d_solution, the context's node state (solution fields; phi_old / phi_oldold are re-imported with their
+ * unchanged values) and its flag bytes are what the next pfm_assemble_device needs, ghosts included.  counts are THIS
+ * rank's: the caller sums them (Utilities::MPI::sum, cracks.cc:2893-2895, 2914).  comm, peer_ranks: as pfm_halo_exchange;
+ * on a context without peers comm may be NULL, nothing is exchanged and d_solution, the flags, the cycle counters and the
+ * counts equal pfm_active_set_device's bit for bit (which does not scatter the node state; this call does).
+ * With peers it is launch-ready but has NOT run between two ranks yet (see pfm_halo_exchange_flags).
+ * PFM_ERR_BAD_ARG with nothing launched: a NULL context, vector or counts; peers without comm or peer_ranks. */
+int pfm_active_set_exchange(pfm_ctx *ctx, void *comm, const int *peer_ranks, const double *d_residual_total,
+                            const double *d_mass, double c, double *d_solution, const double *d_old_solution,
+                            int32_t *d_cycle_counter, int64_t counts[3]);
 
 /* What the line search reads after every assemble_nl_residual() (cracks.cc:2946-2949; 10-50 times per Newton step) and the
  * Newton loop after every assembly (cracks.cc:2791-2794, 2918-2919): the norms of a residual vector with the constrained
