@@ -88,6 +88,7 @@ class Context:
             raise PfmError(rc, "pfm_ctx_create", msg)
         self.n_owned_dofs = self.n_owned * (self.dim + 1)
         self.split_model = capi.SPLIT_REFERENCE  # what set_split_model last set (pfm_set_split_model)
+        self.split_route = capi.SPLIT_ROUTE_GENERAL  # what set_split_route last set (pfm_set_split_route)
 
     # -- helpers ---------------------------------------------------------------------
     def _check(self, rc: int, where: str):
@@ -115,6 +116,20 @@ class Context:
         set_params; a living context may change between 1 and 3 at any time."""
         self._check(self.lib.pfm_set_split_model(self._h, int(model)), "pfm_set_split_model")
         self.split_model = int(model)
+
+    def set_split_route(self, route: int):
+        """Which kernels take the residual-only assembly of a 3-D context under split model 3 (capi.SPLIT_ROUTE_*): 0 the
+        general family over all cells (default), 1 the row-owner residual kernel of the box, the sub-box or the level lattices
+        with the law at its q-points.  At any time on a living context; no effect on full assemblies and on model 1."""
+        self._check(self.lib.pfm_set_split_route(self._h, int(route)), "pfm_set_split_route")
+        self.split_route = int(route)
+
+    def split_route_info(self):
+        """(route set, whether a residual-only assembly with the current parameters, model and forced path would run the
+        split law on the row-owner kernels): pfm_ctx_split_route."""
+        a, b = C.c_int32(-1), C.c_int32(-1)
+        self._check(self.lib.pfm_ctx_split_route(self._h, C.byref(a), C.byref(b)), "pfm_ctx_split_route")
+        return int(a.value), int(b.value)
 
     def set_params(self, prm):
         p = prm if isinstance(prm, PfmParams) else PfmParams.from_any(prm)
@@ -654,6 +669,16 @@ class Assembler:
     @split_model.setter
     def split_model(self, model: int):
         self.ctx.set_split_model(model)
+
+    @property
+    def split_route(self) -> int:
+        """Where the residual-only assembly of a 3-D mesh under split model 3 runs (Context.set_split_route): 0 the general
+        family, 1 the row-owner kernels of the lattice.  May change at any time."""
+        return self.ctx.split_route
+
+    @split_route.setter
+    def split_route(self, route: int):
+        self.ctx.set_split_route(route)
 
     def allocate_matrix(self):
         if not self.system_pde_matrix:

@@ -28,6 +28,7 @@
 #include "pfm_cart_plan.h"
 #include "pfm_poly.h"
 #include "pfm_dma.h"
+#include "pfm_split3.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -79,6 +80,7 @@ namespace pfm
       double ih[3], vol, vih[3], geih[3]; // 1 / h_k, h_x h_y h_z, vol / h_k, G_c eps vol / h_k^2
       double c_g, c_pd, c_r2, c_r3;       // 1 - kappa, (alpha_B - 1) p, -2 (alpha_B - 1) p, G_c / eps
       double c_pdg, c_pdk;                // c_pd / c_g, c_pd kappa / c_g: the pressure term through the moments of g (residual_cell_poly)
+      double d_rhs;                       // decompose_stress_rhs: the weight of sigma- in k_cart_residual3<false, VOLDEV>
     };
 
     Scal make_scal(const pfm_params &prm, const CartView &cv, int dim)
@@ -118,6 +120,7 @@ namespace pfm
       s.c_pdk = s.c_pd * s.kappa / s.c_g;
       s.c_r2 = -2.0 * s.aB1 * s.p;
       s.c_r3 = s.Gc / s.eps;
+      s.d_rhs = prm.decompose_stress_rhs;
       return s;
     }
 
@@ -860,7 +863,10 @@ namespace pfm
       });
     }
 
-    template <bool LIN>
+    // VOLDEV (LIN = false only; CartPlan::voldev): the volumetric-deviatoric stress split of pfm_split3.h at the q-point,
+    // sigma+ in place of sigma and decompose_stress_rhs sigma- next to it (cracks.cc:2393-2432 with stress_term_plus /
+    // stress_term_minus).  The law has a max: the polynomial forms (residual_cell_poly, k_cart_residual3x / 3d) cannot carry it.
+    template <bool LIN, bool VOLDEV = false>
     __global__ __launch_bounds__(RTX *RTY, 2) void k_cart_residual3(DevView v, CartView cv, Scal S,
                                                                  double *__restrict__ res_pde,
                                                                  double *__restrict__ res_tot, int write_total,
@@ -1088,12 +1094,24 @@ namespace pfm
                     // sigma : E = sum_a sigma_aa g_aa + sum_{a<b} sigma_ab t_ab
                     const double t01 = gu[0][1] + gu[1][0], t02 = gu[0][2] + gu[2][0], t12 = gu[1][2] + gu[2][1];
                     const double trE = gu[0][0] + gu[1][1] + gu[2][2];
-                    const double lt = lam * trE;
-                    const double s00 = fma(mu2, gu[0][0], lt), s11 = fma(mu2, gu[1][1], lt), s22 = fma(mu2, gu[2][2], lt);
+                    double s00, s11, s22, zm = 0.0; // zm: decompose_stress_rhs sigma- = zm I
+                    if constexpr (VOLDEV)
+                      {
+                        const split3::VolDev V = split3::voldev(trE, lam, mu);
+                        s00 = split3::voldev_sigma_plus(V, mu, gu[0][0], true);
+                        s11 = split3::voldev_sigma_plus(V, mu, gu[1][1], true);
+                        s22 = split3::voldev_sigma_plus(V, mu, gu[2][2], true);
+                        zm = S.d_rhs * V.sm_iso;
+                      }
+                    else
+                      {
+                        const double lt = lam * trE;
+                        s00 = fma(mu2, gu[0][0], lt), s11 = fma(mu2, gu[1][1], lt), s22 = fma(mu2, gu[2][2], lt);
+                      }
                     const double s01 = mu * t01, s02 = mu * t02, s12 = mu * t12;
                     const double spE = fma(s00, gu[0][0], fma(s11, gu[1][1], s22 * gu[2][2])) + fma(s01, t01, fma(s02, t02, s12 * t12));
                     // Z = g sigma+ - (alpha_B - 1) p pfx^2 I (symmetric); the weights enter with the sums
-                    const double pd = c_pd * pf2;
+                    const double pd = VOLDEV ? c_pd * pf2 - zm : c_pd * pf2;
                     const double z00 = fma(g, s00, -pd), z11 = fma(g, s11, -pd), z22 = fma(g, s22, -pd);
                     const double z01 = g * s01, z02 = g * s02, z12 = g * s12;
                     // gamma pen + (1 - kappa) sigma:E pf - G_c/eps (1 - pf) - 2 (alpha_B - 1) p pf tr(E)
@@ -1675,7 +1693,8 @@ namespace pfm
       {
         const bool flat = pl.residual == PFM_RES_2M; // a wave per R2N nodes of a row and chunk of rows; 3-D: chunks of z-planes
         const TileGrid &g = pl.grid[flat ? PFM_ZC_RES2 : PFM_ZC_RES3];
-        const ResidualKernel kernel = residual_kernel[pl.residual][pl.residual_flag()];
+        // (CartPlan::voldev: the split law in the q-point form, whatever the scheme)
+        const ResidualKernel kernel = pl.voldev ? k_cart_residual3<false, true> : residual_kernel[pl.residual][pl.residual_flag()];
         if (g.n_tiles != 0)
           hipLaunchKernelGGL(kernel, dim3(flat ? g.n_tiles : xcd_grid(g.n_tiles)), dim3(flat ? 64 : RTX * RTY), 0, s_side, v, cv,
                              make_scal(p, cv, v.dim), res_pde, res_tot, (int)pl.residual_only, g.zc);

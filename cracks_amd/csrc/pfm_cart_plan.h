@@ -23,6 +23,13 @@ namespace pfm
     return {p.decompose_stress_matrix > 0 && p.timestep_number > 0, !mono && !penalised, !(p.constant_k < 0.5)};
   }
 
+  // The 3-D law of a split assembly and where its residual may run (pfm_set_split_model, pfm_set_split_route).  The default
+  // is what a caller of neither gets: every split assembly belongs to the general family.
+  struct CartSplit
+  {
+    int model = PFM_SPLIT_REFERENCE, route = PFM_SPLIT_ROUTE_GENERAL;
+  };
+
   // owned nodes per tile: k_cart_uu3 T3X x T3Y, k_cart_phi4 PN x PN, k_cart_residual3* RNX x RNY, k_cart_residual2m R2N, k_cart2d_cells O2 x O2
   constexpr int T3X = 8, T3Y = 4, PN = 7, RNX = 15, RNY = 15, R2N = 62, O2 = 7;
   constexpr int PFM_TILES_CELLS2 = PFM_ZC_KERNELS, PFM_TILE_KERNELS = PFM_ZC_KERNELS + 1; // the PFM_ZC_* kernels, then k_cart2d_cells
@@ -86,11 +93,15 @@ namespace pfm
     return g;
   }
 
-  enum CartResidual { PFM_RES_NONE, PFM_RES_3X, PFM_RES_3D, PFM_RES_3, PFM_RES_2M }; // k_cart_residual3x<het>, 3d<het>, 3<linear>, 2m<linear>
+  enum CartResidual { PFM_RES_NONE, PFM_RES_3X, PFM_RES_3D, PFM_RES_3, PFM_RES_2M }; // k_cart_residual3x<het>, 3d<het>, 3<linear> (CartPlan::voldev: 3<false, true>), 2m<linear>
   struct CartPlan
   {
     int dim = 0, phase = 0; // 0: the whole assembly; 1, 2: the halves of pfm_assemble_overlapped (ghost import in between)
     bool residual_only = false, supported = false; // not supported (stress split): the general family takes the assembly
+    // ... but for the residual-only assembly of a 3-D context under PFM_SPLIT_VOLDEV on PFM_SPLIT_ROUTE_LATTICE: the law is a few
+    // scalar statements on the strain and runs in k_cart_residual3<false, true>, for every scheme, cut into halves as an
+    // unsplit PFM_RES_3 is (the Jacobian kernels have no split form: a full assembly stays unsupported)
+    bool voldev = false;
     bool linear = false, interleaved = false, het = false; // scheme; layout; per-cell Lame coefficients (CartView::cell_lam)
     // Full 3-D assembly, linear scheme: every residual row is an exact function of its own matrix row (R_u = pressure part -
     // K_uu u, R_phi = G_c/eps mass - K_phiphi phi), so the Jacobian kernels write it and no residual kernel runs (2.1 of 15.8 ms
@@ -120,13 +131,15 @@ namespace pfm
   };
 
   // No side effects: what lattice cv of view v, the parameters and the switches say about this assembly.
-  inline CartPlan plan_cart(const DevView &v, const CartView &cv, const pfm_params &p, int residual_only, int phase, int n_cu)
+  inline CartPlan plan_cart(const DevView &v, const CartView &cv, const pfm_params &p, int residual_only, int phase, int n_cu,
+                            const CartSplit &split = CartSplit())
   {
     const Switches &sw = switches();
     const CartScheme sc = cart_scheme(p);
     CartPlan pl;
     pl.dim = v.dim, pl.phase = phase, pl.residual_only = residual_only != 0;
-    pl.supported = !sc.split && (v.dim == 2 || v.dim == 3);
+    pl.voldev = sc.split && v.dim == 3 && pl.residual_only && split.model == PFM_SPLIT_VOLDEV && split.route == PFM_SPLIT_ROUTE_LATTICE;
+    pl.supported = (!sc.split || pl.voldev) && (v.dim == 2 || v.dim == 3);
     if (!pl.supported)
       return pl;
     pl.linear = sc.linear, pl.interleaved = v.layout == PFM_LAYOUT_INTERLEAVED, pl.het = cv.cell_lam != nullptr;
@@ -141,7 +154,7 @@ namespace pfm
     if (v.dim == 2 && pl.residual_only)
       pl.residual = PFM_RES_2M;
     else if (v.dim == 3 && !pl.rows_residual)
-      pl.residual = !(sc.linear && whole_lex) ? PFM_RES_3
+      pl.residual = (!(sc.linear && whole_lex) || pl.voldev) ? PFM_RES_3
                     : (v.fused_solution && !pl.interleaved && v.n_nodes >= 64 && !Switches::res_no_wide_transfers()) ? PFM_RES_3X : PFM_RES_3D;
     pl.uu3_clock = sw.uu_clock && !pl.interleaved && !pl.het;
     pl.phi4_clock = (!pl.interleaved && !pl.het && sc.linear) ? sw.phi_clock : 0;

@@ -1400,6 +1400,16 @@ extern "C"
     return PFM_OK;
   }
 
+  int pfm_set_split_route(pfm_ctx *c, int route)
+  {
+    if (!c || (route != PFM_SPLIT_ROUTE_GENERAL && route != PFM_SPLIT_ROUTE_LATTICE))
+      return c ? fail(c, PFM_ERR_BAD_ARG, "unknown split route") : PFM_ERR_BAD_ARG;
+    if (route == PFM_SPLIT_ROUTE_LATTICE && c->v.dim != 3)
+      return fail(c, PFM_ERR_UNSUPPORTED, "the lattice route carries the volumetric-deviatoric split, a 3-D law");
+    c->split_route = route;
+    return PFM_OK;
+  }
+
   static pfm_ctx::HostPin *find_pin(pfm_ctx *c, const void *p, size_t bytes);
 
   // Host -> device copy of a buffer the CALLER owns.  Page-locked through pfm_host_register: an asynchronous DMA on `s`.
@@ -2333,6 +2343,8 @@ extern "C"
   // (the A/B switches of the dispatch: pfm_switches.h)
   // the stress split in the matrix (cracks.cc:2294): the general family has it, the row-owner kernels do not
   static bool stress_split(const pfm_ctx *c) { return c->have_params && cart_scheme(c->prm).split; }
+  // ... but for what plan_cart takes from the law and the route of the context (CartPlan::voldev)
+  static pfm::CartSplit cart_split(const pfm_ctx *c) { return {c->split_model, c->split_route}; }
 
   // Every decision of one assemble_impl call; what each means stands where it is made (plan_assembly, after_tables).
   struct AssemblyPlan
@@ -2341,7 +2353,8 @@ extern "C"
     bool residual_only = false, split = false, cart = false, patches = false, overlay3 = false, overlay_uu = false, nothing = false;
     bool pair = false, fork = false, levels_concurrent = false, fill_up_block = false, up_block_cleared = false;
     bool gather = false, fork_general = false, atomic_stream = false; // final behind the lazy tables: after_tables
-    CartPlan box; // cart: what the launchers of the cartesian family do (plan_cart)
+    CartPlan box;   // cart: what the launchers of the cartesian family do (plan_cart)
+    CartPlan level; // overlay3: the same for the first level lattice (every level shares its scheme, law and kernels)
     void after_tables(const pfm_ctx *c, bool gather_ready);
   };
 
@@ -2353,7 +2366,7 @@ extern "C"
     p.residual_only = residual_only != 0;
     p.split = stress_split(c);
     if (c->kernel_path == 1)
-      p.box = plan_cart(c->v, c->cv, c->prm, residual_only, phase, cart_n_cu());
+      p.box = plan_cart(c->v, c->cv, c->prm, residual_only, phase, cart_n_cu(), cart_split(c));
     p.cart = c->kernel_path == 1 && p.box.supported; // assemble_box
     // the general family and the overlays are not cut into interior / boundary work: everything in phase 2
     p.nothing = !p.cart && phase == 1;
@@ -2363,7 +2376,10 @@ extern "C"
     // cartesian overlay of a general mesh (AMR meshes; stress-split runs on a lattice): patch kernel (2-D) or level
     // lattices (3-D) for the regular rows, the general family for the rest (PFM_NO_PATCH=1 at context creation: general
     // family alone): assemble_overlay
-    p.overlay3 = !p.cart && c->v.dim == 3 && !c->levels3.empty() && c->kernel_path != 0 && !p.nothing && !p.split;
+    // (a split assembly keeps its level lattices where plan_cart has a kernel with the law: CartPlan::voldev)
+    if (!p.cart && c->v.dim == 3 && !c->levels3.empty() && c->kernel_path != 0 && !p.nothing)
+      p.level = plan_cart(c->v, c->levels3[0].cv, c->prm, residual_only, 0, cart_n_cu(), cart_split(c));
+    p.overlay3 = p.level.supported;
     p.patches = (!p.cart && c->v.dim == 2 && c->n_patch_blocks > 0 && c->kernel_path != 0 && !p.nothing) || p.overlay3;
     // 3-D cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*) -- wanted.  A split
     // assembly keeps it under PFM_SPLIT_VOLDEV, whose kernel is the unsplit form; the spectral instantiations have no SCR form
@@ -2617,7 +2633,7 @@ extern "C"
       {
         hipStream_t st = par ? c->ov_streams[i] : c->stream;
         const pfm::CartView &lcv = c->levels3[i].cv; // one plan per level lattice
-        rc = launch_assemble_cart(plan_cart(c->v, lcv, c->prm, p.residual_only, 0, cart_n_cu()), c->v, lcv, c->prm, d_values, d_res_pde,
+        rc = launch_assemble_cart(plan_cart(c->v, lcv, c->prm, p.residual_only, 0, cart_n_cu(), cart_split(c)), c->v, lcv, c->prm, d_values, d_res_pde,
                                   d_res_tot, st, st, c->levels3[i].d_scal, &c->clock);
       }
     for (size_t i = 0; par && i < nl; ++i)
@@ -2761,7 +2777,9 @@ extern "C"
       return PFM_ERR_BAD_ARG;
     if (!c->peers.empty())
       return fail(c, PFM_ERR_BAD_ARG, "pfm_assemble_nl_residual_device: a rank with peers imports ghosts between the scatter and the assembly");
-    const bool fuse = c->kernel_path == 1 && !stress_split(c) && c->v.n_owned == c->v.n_nodes && c->v.n_owned > 0 && Switches::fused_scatter();
+    // (the residual of the box on a row-owner kernel: unsplit, or the split law on the lattice route)
+    const bool fuse = c->kernel_path == 1 && (!c->have_params || plan_cart(c->v, c->cv, c->prm, 1, 0, cart_n_cu(), cart_split(c)).supported) &&
+                      c->v.n_owned == c->v.n_nodes && c->v.n_owned > 0 && Switches::fused_scatter();
     if (!fuse)
       {
         const int rc = state_set_impl(c, d_solution, nullptr, nullptr, 1);
@@ -3102,6 +3120,25 @@ extern "C"
   }
 
   int pfm_ctx_kernel_path(const pfm_ctx *c) { return c ? c->kernel_path : -1; }
+
+  int pfm_ctx_split_route(const pfm_ctx *c, int *route, int *lattice_residual)
+  {
+    if (!c)
+      return PFM_ERR_BAD_ARG;
+    if (route)
+      *route = c->split_route;
+    if (lattice_residual)
+      {
+        // the plan of such an assembly, not a second copy of its conditions
+        *lattice_residual = 0;
+        if (c->have_params)
+          {
+            const AssemblyPlan p = plan_assembly(c, 1, 0, nullptr);
+            *lattice_residual = ((p.cart && p.box.voldev) || (p.overlay3 && p.level.voldev)) ? 1 : 0;
+          }
+      }
+    return PFM_OK;
+  }
 
   int pfm_ctx_force_path(pfm_ctx *c, int path)
   {

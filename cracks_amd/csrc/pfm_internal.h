@@ -285,6 +285,7 @@ struct pfm_ctx
   pfm_params prm{};
   bool have_params = false;
   int split_model = 0; // PFM_SPLIT_*: pfm_set_split_model
+  int split_route = 0; // PFM_SPLIT_ROUTE_*: pfm_set_split_route
   int n_blocks = 1;
   int kernel_path = 0;
   int force_phase = 0; // pfm_ctx_force_phase (measurement)

@@ -142,6 +142,10 @@ namespace pfm_glue_detail
     //                      bitwise reproducible on meshes with hanging nodes as well)
     //                      (pfm_set_split_model; forwarded in front of the parameters at every assemble()).  With the default,
     //                      PFM_SPLIT_REFERENCE, a 3-D run with decompose_stress_matrix > 0 stops at PFM_ERR_UNSUPPORTED.
+    //   split_route:       PFM_SPLIT_ROUTE_LATTICE hands the residual-only assemblies of a 3-D run under PFM_SPLIT_VOLDEV (the
+    //                      line search's) to the row-owner kernels of the lattice (pfm_set_split_route; forwarded next to
+    //                      split_model).  The Jacobian call's residual_pde still comes from the general family: the two
+    //                      agree to rounding, not bit for bit.  Default PFM_SPLIT_ROUTE_GENERAL: nothing changes.
     //   line_search_stepwise: line_search() runs the host loop of a rank with ghost peers (vector statements, scatter + halo +
     //                      assembly, pfm_residual_norms, MPI sum / max) also where pfm_line_search_device would do: the two
     //                      forms give the same vectors and the same result (tests/test_gpu_glue_line_search.py).
@@ -153,6 +157,7 @@ namespace pfm_glue_detail
     bool pin_host_matrix = false;
     bool delta_values = false;
     int split_model = PFM_SPLIT_REFERENCE;
+    int split_route = PFM_SPLIT_ROUTE_GENERAL;
     bool residual_to_host = true;
     bool holds_host_pins = false;
     int64_t delta_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // of the last assemble() with delta_values (pfm_values_to_host_delta)
@@ -668,6 +673,7 @@ namespace pfm_glue_detail
       p.outer_solver = P.outer_solver == Problem::OuterSolverType::active_set ? PFM_SOLVER_ACTIVE_SET : PFM_SOLVER_SIMPLE_MONOLITHIC;
       p.use_old_timestep_pf = P.use_old_timestep_pf ? 1 : 0;
       PFM_CALL(ctx, pfm_set_split_model(ctx, split_model));
+      PFM_CALL(ctx, pfm_set_split_route(ctx, split_route));
       PFM_CALL(ctx, pfm_set_params(ctx, &p));
 
       // constraints_update minus the hanging-node lines: one flag byte per local node (cracks.cc:2442-2463)

@@ -131,6 +131,28 @@ enum
   PFM_SPLIT_VOLDEV = 3
 };
 int pfm_set_split_model(pfm_ctx *ctx, int model);
+/* Which kernels take the residual-only assembly (the line search's call, cracks.cc:2942-2957) of a 3-D context under
+ * PFM_SPLIT_VOLDEV with the split on.
+ *   PFM_SPLIT_ROUTE_GENERAL  the general family over all cells, as every split assembly.  Default: nothing about a caller
+ *                            that never sets a route changes, bit for bit.
+ *   PFM_SPLIT_ROUTE_LATTICE  the row-owner residual kernel of the cartesian family with the law at its q-points
+ *                            (k_cart_residual3<false, true>, for every scheme): on a box, on a partitioned sub-box in both
+ *                            halves of pfm_assemble_overlapped, and on the level lattices of a 3-D overlay, whose remaining
+ *                            cells stay with the general family and its gather.  Full assemblies, model 1, 2-D contexts and a
+ *                            context forced to path 0 (pfm_ctx_force_path) run as under PFM_SPLIT_ROUTE_GENERAL.  A Newton step
+ *                            then has its Jacobian call's residual_pde from the general family and its line-search
+ *                            residuals from the lattice kernels: equal to rounding, not bit for bit.
+ * May be called at any time on a living context: the next assembly follows it.  An unknown route: PFM_ERR_BAD_ARG.
+ * PFM_SPLIT_ROUTE_LATTICE on a 2-D context: PFM_ERR_UNSUPPORTED.  With model 0 or 1 the route is accepted and has no effect.
+ * pfm_ctx_split_route: the route set and, lattice_residual, whether a residual-only assembly with the current parameters,
+ * model and forced path would run the law on the row-owner kernels (0 before pfm_set_params); either pointer may be null. */
+enum
+{
+  PFM_SPLIT_ROUTE_GENERAL = 0,
+  PFM_SPLIT_ROUTE_LATTICE = 1
+};
+int pfm_set_split_route(pfm_ctx *ctx, int route);
+int pfm_ctx_split_route(const pfm_ctx *ctx, int *route, int *lattice_residual);
 /* constraints_update minus the hanging nodes: one byte per local node, bit c set <=> dof
  * (node, c) has a homogeneous line (Dirichlet from set_newton_bc cracks.cc:2711-2714, or
  * active set cracks.cc:2878-2879).  Call whenever constraints_update is rebuilt. */

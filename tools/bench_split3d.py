@@ -15,6 +15,12 @@ where they must agree: in a second state of pure tension the split assembly repr
 the unsplit arm and one arm per model, alternating; the keys of a model's arm then carry its name instead of "split".
 
     python tools/bench_split3d.py [--n 100] [--reps 20] [--warmup 3] [--rounds 3] [--model {spectral,voldev} ...]
+
+--route general lattice times something else: the residual-only assembly of PFM_SPLIT_VOLDEV on the box context itself, once per
+route of pfm_set_split_route (general: the general family over all cells; lattice: k_cart_residual3<false, true>), next to
+two yardstick arms with the split off -- "unsplit", what the context runs by itself (the polynomial row-owner kernels), and
+"unsplit_qpoint", the q-point form k_cart_residual3<false> the law sits in (reached with a penalised monolithic scheme) --
+all arms alternating round by round in one process.  The two routes are compared with each other on the timed state.
 """
 import argparse
 import json
@@ -37,6 +43,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="off / on alternations; the medians of all rounds are reported")
     ap.add_argument("--layout", choices=["blocked", "interleaved"], default="blocked")
     ap.add_argument("--model", choices=["spectral", "voldev"], nargs="+", default=["spectral"], help="the split law(s) to time")
+    ap.add_argument("--route", choices=["general", "lattice"], nargs="+", default=None,
+                    help="time the residual-only assembly of model 3 per split route on the box context instead (see above)")
     args = ap.parse_args()
 
     import torch
@@ -72,6 +80,9 @@ def main():
     asm.set_constraints(np.zeros(mesh.n_nodes, np.uint8))
     asm.set_vectors(sol, old, old)
     asm.allocate_matrix()
+
+    if args.route:
+        return bench_routes(args, asm, capi, mesh, prm_off, prm_on, O.make_params(**{"lambda": 121.15}, outer_solver=1, gamma_penal=1e-2, **base))
 
     def configure(split):
         # the unsplit assembly through the general family as well (the box's own kernels are not the yardstick here)
@@ -127,6 +138,59 @@ def main():
         for m in arms:
             key = "split" if len(arms) == 1 else m
             rec[tag][f"{key}_ms_per_1e6_cells"] = float(np.median(np.concatenate(ts[m])) * 1e6 / mesh.n_cells)
+    print(json.dumps(rec))
+
+
+def bench_routes(args, asm, capi, mesh, prm_off, prm_on, prm_qpoint):
+    """--route: residual-only arms on the box context (kernel path 1), alternating round by round"""
+    routes = {"general": capi.SPLIT_ROUTE_GENERAL, "lattice": capi.SPLIT_ROUTE_LATTICE}
+    arms = list(dict.fromkeys(args.route)) + ["unsplit", "unsplit_qpoint"]
+    asm.split_model = capi.SPLIT_VOLDEV
+
+    def configure(arm):
+        asm.split_route = routes.get(arm, capi.SPLIT_ROUTE_GENERAL)
+        asm.set_params(prm_on if arm in routes else prm_qpoint if arm == "unsplit_qpoint" else prm_off)
+        assert asm.ctx.kernel_path == 1 and asm.ctx.split_route_info()[1] == int(arm == "lattice")
+
+    def timed(arm):
+        configure(arm)
+        for _ in range(args.warmup):
+            asm.assemble_system(True)
+        asm.synchronize()
+        asm.ctx.timing_enable(True)
+        for _ in range(args.reps):
+            asm.assemble_system(True)
+        asm.synchronize()
+        ts = asm.ctx.kernel_times_ms()
+        asm.ctx.timing_enable(False)
+        assert ts.size == args.reps
+        return ts
+
+    outs = {}
+    for arm in [a for a in arms if a in routes]:
+        configure(arm)
+        asm.assemble_system(True)
+        asm.synchronize()
+        outs[arm] = (asm.system_pde_residual.clone(), asm.system_total_residual.clone())
+    rec = {"metric": "split3d_routes_residual_only", "cells": int(mesh.n_cells), "layout": args.layout, "reps": args.reps, "rounds": args.rounds,
+           "arms": arms}
+    if len(outs) == 2:
+        rec["lattice_deviation_from_general"] = max(float((a - b).abs().max() / max(1.0, float(b.abs().max())))
+                                                    for a, b in zip(outs["lattice"], outs["general"]))
+    ts = {arm: [] for arm in arms}
+    for _ in range(args.rounds):
+        for arm in arms:
+            ts[arm].append(timed(arm))
+    med = {arm: float(np.median(np.concatenate(ts[arm]))) for arm in arms}
+    for arm in arms:
+        rec[arm] = {"ms": med[arm], "min_ms": float(np.concatenate(ts[arm]).min()), "round_medians_ms": [float(np.median(t)) for t in ts[arm]],
+                    "ms_per_1e6_cells": med[arm] * 1e6 / mesh.n_cells}
+    if "lattice" in med:
+        rec["lattice_over_unsplit"] = med["lattice"] / med["unsplit"]
+        rec["lattice_over_unsplit_qpoint"] = med["lattice"] / med["unsplit_qpoint"]
+    if "lattice" in med and "general" in med:
+        rec["lattice_over_general"] = med["lattice"] / med["general"]
+        rec["lattice_below_general_in_every_round"] = all(np.median(l) < np.median(g) for l, g in zip(ts["lattice"], ts["general"]))
     print(json.dumps(rec))
 
 

@@ -95,7 +95,7 @@ def compile_to_asm(src: str, resources: bool = False, pattern: str = "") -> str:
 def print_resources(remarks: str, pattern: str):
     """The compiler's resource-usage remarks (registers, scratch, LDS, occupancy), one line per kernel that matches."""
     name, vals = None, {}
-    for line in remarks.split("\n") + ["Function Name: "]:
+    for line in remarks.split("\n") + ["remark: Function Name: "]:  # (the sentinel flushes the last kernel)
         m = re.search(r"remark:\s+(?:Function Name: (\S*)|([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+))", line)
         if not m:
             continue
