@@ -6,6 +6,7 @@ import numpy as np
 import scipy.sparse as sp
 
 import oracle_api as O
+import parity_scale as PS
 from cracks_amd import mesh as M
 from cracks_amd.assembler import Context, node_flags_from_dof_flags
 
@@ -51,9 +52,72 @@ def oracle(c, residual_only):
     return r, rowptr, colind
 
 
+def reference_matrix(c, hanging_only=False):
+    """The oracle's Jacobian of a Case as one CSR over the global dofs -- the matrix the scales of tests/parity_scale.py
+    come from.  hanging_only: distributed with the hanging-node constraints in the place of constraints_update."""
+    rowptr, colind = M.dof_sparsity(c.mesh, c.layout)
+    r = O.assemble(c.mesh, c.layout, c.params, c.sol, c.old, c.oldold, c.ch if hanging_only else c.cu, c.ch, False,
+                   rowptr, colind, c.cell_lambda, c.cell_mu)
+    assert r.err == 0
+    return sp.csr_matrix((r.values, colind, rowptr), shape=(c.layout.n_dofs,) * 2)
+
+
+def total_matrix(c, A_ref=None):
+    """The reference matrix whose rows belong to residual_total: the active-set scheme (outer_solver 0) distributes that
+    vector with the hanging-node constraints alone (cracks.cc:2439-2464), so its Dirichlet and active-set rows hold the
+    sums of the unconstrained rows; every other scheme uses constraints_update, i.e. A_ref itself."""
+    if c.params.outer_solver == 0:
+        return reference_matrix(c, hanging_only=True)
+    return reference_matrix(c) if A_ref is None else A_ref
+
+
+def residual_parity(c, res_pde, res_tot, ref_pde, ref_tot, A_ref=None, A_tot=None, tol=TOL, tag=""):
+    """The per-row and per-part checks of tests/parity_scale.py on the two vectors of a residual-only call (either may be
+    None), with the scales of one oracle Jacobian of the case."""
+    if A_ref is None:
+        A_ref = reference_matrix(c)
+    if res_pde is not None:
+        PS.assert_residual(res_pde, ref_pde, A_ref, c.layout, c.sol, tol, f"{c.name} {tag} residual_pde")
+    if res_tot is not None:
+        if A_tot is None:
+            A_tot = total_matrix(c, A_ref)
+        PS.assert_residual(res_tot, ref_tot, A_tot, c.layout, c.sol, tol, f"{c.name} {tag} residual_total")
+
+
+def reference_parity(layout, sol, A, A_ref, vectors=(), tol=TOL, tag="", A_tot=None):
+    """The four checks of tests/parity_scale.py against a reference CSR of any origin (oracle, numpy reference, a scaled 2-D
+    matrix): A (or None) per entry and per block on its own pattern, each (vector, reference, "pde" | "tot") per row and per
+    part with the scales of A_ref -- of A_tot for "tot", when the scheme distributes residual_total with other constraints.
+    Returns A_ref on A's pattern."""
+    if A is not None:
+        A.sort_indices()
+        A_ref = PS.on_pattern(A_ref, A)
+        PS.assert_matrix(A, A_ref, layout, tol, tag)
+    for v, ref, which in vectors:
+        mat = A_tot if (which == "tot" and A_tot is not None) else A_ref
+        PS.assert_residual(v, ref, mat, layout, sol, tol, f"{tag} residual_{which}")
+    return A_ref
+
+
+def path_parity(ctx, layout, values, values_other, vectors=(), tol=TOL, tag=""):
+    """One GPU path against another, no reference matrix in play: the per-block check on the matrices (blocks classified
+    by the layout, so the interleaved layout's single value array is split too) and the per-part check on each pair of
+    vectors.  No per-entry or per-row check: their scales belong to a reference."""
+    if values is not None:
+        A, B = blocks_to_global(ctx, layout, values), blocks_to_global(ctx, layout, values_other)
+        A.sort_indices()
+        B.sort_indices()
+        blk = PS.block_of_entries(layout, PS.entry_rows(B), B.indices)
+        PS.assert_blocks([A.data[blk == b] for b in range(4)], [B.data[blk == b] for b in range(4)], tol, f"{tag} (path against path)", PS.BLOCKS)
+    phi = PS.is_phi(layout)
+    for k, (a, b) in enumerate(vectors):
+        PS.assert_parts(a, b, phi, tol, f"{tag} (path against path) vector {k}")
+
+
 def full_parity(c, tol=TOL, ctx=None):
     """Full assembly, then the residual-only call, of a Case against the oracle: identical pattern, every matrix entry and
-    both residuals within tol.  ctx: a context of the case to run on (default: a new one); returned."""
+    both residuals within tol of max(1, |reference|_inf); then the four checks of tests/parity_scale.py, always at TOL.
+    ctx: a context of the case to run on (default: a new one); returned."""
     if ctx is None:
         ctx = make_context(c)
     values, res_pde, _ = ctx.assemble_host(c.sol, c.old, c.oldold, residual_only=False)
@@ -69,6 +133,11 @@ def full_parity(c, tol=TOL, ctx=None):
     r2, _, _ = oracle(c, True)
     assert linf_scaled(res_pde2, r2.residual_pde) < tol
     assert linf_scaled(res_tot2, r2.residual_total) < tol
+    # the same comparisons at the scale of each entry, block, row and part (tests/parity_scale.py)
+    # -- always at TOL: a caller's wider tol belongs to the whole-matrix comparison above alone
+    PS.assert_matrix(A, A_ref, c.layout, TOL, c.name)
+    residual_parity(c, res_pde, None, r.residual_pde, None, A_ref, tag="full")
+    residual_parity(c, res_pde2, res_tot2, r2.residual_pde, r2.residual_total, A_ref, tag="residual-only")
     return ctx
 
 

@@ -52,6 +52,17 @@ class Ref:
                                            jacobian=False)
         self.pde = R.distribute_vector(c.layout, c.mesh.cells, Re, c.cu)
         self.tot = R.residual_total(c.layout, c.mesh.cells, c.params, Re, c.cu, c.ch)
+        self._c, self._sol, self._mats = c, (c.sol if sol is None else sol), None
+
+    def matrices(self):
+        """(A, A_tot) of the reference's law at the same state, made on first use: the matrices whose rows belong to
+        residual_pde and residual_total -- what the per-row scale of tests/parity_scale.py is taken from"""
+        if self._mats is None:
+            c = self._c
+            Ke, Re, _ = V.element_matrices(c.mesh, c.layout, c.params, self._sol, c.old, c.oldold, c.cell_lambda, c.cell_mu)
+            A = R.distribute_matrix(c.mesh, c.layout, Ke, Re, c.cu)[0]
+            self._mats = (A, A if c.params.outer_solver != 0 else R.distribute_matrix(c.mesh, c.layout, Ke, Re, c.ch)[0])
+        return self._mats
 
 
 @functools.lru_cache(maxsize=None)

@@ -19,7 +19,7 @@ import cases
 import oracle_api as O
 from cracks_amd import build
 from cracks_amd import mesh as M
-from gpu_util import linf_scaled
+from gpu_util import linf_scaled, reference_parity, total_matrix
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "glue_driver.cpp")
@@ -207,3 +207,7 @@ def test_glue_rebuild_and_assemble_match_the_oracle(name, maker, tmp_path):
     assert (A.indptr == A_ref.indptr).all() and (A.indices == A_ref.indices).all()
     assert linf_scaled(A.data, A_ref.data) < TOL
     assert linf_scaled(np.fromfile(os.path.join(d, "out_res_pde.bin"))[to_mock], rf.residual_pde) < TOL
+    # every entry, block, residual row and residual part at its own scale (tests/parity_scale.py)
+    reference_parity(lay, c.sol, A, A_ref, [(np.fromfile(os.path.join(d, "out_res_pde.bin"))[to_mock], rf.residual_pde, "pde"),
+                                            (res_pde, ro.residual_pde, "pde"), (res_tot, ro.residual_total, "tot")],
+                     tag=f"glue {name}", A_tot=total_matrix(c, A_ref))

@@ -7,7 +7,8 @@ import scipy.sparse as sp
 import cases
 import oracle_api as O
 from cracks_amd import mesh as M
-from gpu_util import blocks_to_global, linf_scaled, make_context
+import parity_scale as PS
+from gpu_util import blocks_to_global, linf_scaled, make_context, path_parity, reference_matrix, residual_parity
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
@@ -62,9 +63,12 @@ def test_cart_residual_matches_oracle(dim, n, lo, hi, blocked, monolithic):
     r, _, _ = oracle(c, True)
     assert linf_scaled(res_pde, r.residual_pde) < TOL
     assert linf_scaled(res_tot, r.residual_total) < TOL
+    A_ref = reference_matrix(c)  # one oracle Jacobian of the case: the scales of the per-row check
+    residual_parity(c, res_pde, res_tot, r.residual_pde, r.residual_total, A_ref, tag="cartesian")
     ctx.force_path(0)
     _, g_pde, g_tot = ctx.assemble_host(c.sol, c.old, c.oldold, True)
     assert linf_scaled(res_pde, g_pde) < TOL and linf_scaled(res_tot, g_tot) < TOL
+    residual_parity(c, g_pde, g_tot, r.residual_pde, r.residual_total, A_ref, tag="general")
 
 
 def _full(c, path):
@@ -79,6 +83,8 @@ def _full(c, path):
     err = linf_scaled(A.data, A_ref.data)
     assert err < TOL, err
     assert linf_scaled(res_pde, r.residual_pde) < TOL
+    PS.assert_matrix(A, A_ref, c.layout, TOL, f"{c.name} path {path}")
+    PS.assert_residual(res_pde, r.residual_pde, A_ref, c.layout, c.sol, TOL, f"{c.name} path {path} residual_pde")
 
 
 @pytest.mark.parametrize("blocked", [True, False])
@@ -173,6 +179,7 @@ def test_cart_is_the_default_full_path_for_boxes():
     for a, b in zip(values, values_g):
         assert linf_scaled(a, b) < TOL
     assert linf_scaled(res_pde, res_g) < TOL
+    path_parity(ctx, c.layout, values, values_g, [(res_pde, res_g)], tag="cartesian against general")
 
 
 @pytest.mark.parametrize("dim,n", [(3, (1, 1, 1)), (3, (2, 1, 3)), (3, (1, 8, 1)), (2, (1, 1)), (2, (3, 1))])
@@ -184,6 +191,7 @@ def test_cart_degenerate_boxes(dim, n):
     r, _, _ = oracle(c, True)
     assert linf_scaled(res_pde, r.residual_pde) < TOL
     assert linf_scaled(res_tot, r.residual_total) < TOL
+    residual_parity(c, res_pde, res_tot, r.residual_pde, r.residual_total, tag="degenerate box")
     _full(c, path=ctx.kernel_path)
 
 
@@ -224,6 +232,7 @@ def test_cart_random_constraints_stress(blocked, kappa_zero):
     r, _, _ = oracle(c, True)
     assert linf_scaled(res_pde, r.residual_pde) < TOL
     assert linf_scaled(res_tot, r.residual_total) < TOL
+    residual_parity(c, res_pde, res_tot, r.residual_pde, r.residual_total, tag="random constraints")
     _full(c, path=1)
 
 
@@ -272,6 +281,7 @@ def test_cart_matches_general_family_on_a_medium_box(blocked):
     for a, b in zip(v1, v0):
         assert linf_scaled(a, b) < TOL
     assert linf_scaled(r1, r0) < TOL and linf_scaled(rp1, rp0) < TOL and linf_scaled(rt1, rt0) < TOL
+    path_parity(ctx, c.layout, v1, v0, [(r1, r0), (rp1, rp0), (rt1, rt0)], tag="medium box, cartesian against general")
 
 
 @pytest.mark.parametrize("dim,n", [(3, (9, 5, 11)), (2, (12, 7))])
@@ -286,11 +296,13 @@ def test_cart_residual_with_old_timestep_phase_field(dim, n):
     _, res_pde, res_tot = ctx.assemble_host(c.sol, c.old, c.oldold, True)
     r, _, _ = oracle(c, True)
     assert linf_scaled(res_pde, r.residual_pde) < TOL and linf_scaled(res_tot, r.residual_total) < TOL
+    residual_parity(c, res_pde, res_tot, r.residual_pde, r.residual_total, tag="use_old_timestep_pf")
     c.params.use_old_timestep_pf = 0  # extrapolated pf_extra with unequal time steps (tfac != 1), clamped to [0, 1]
     ctx = make_context(c)
     _, res_pde, res_tot = ctx.assemble_host(c.sol, c.old, c.oldold, True)
     r, _, _ = oracle(c, True)
     assert linf_scaled(res_pde, r.residual_pde) < TOL and linf_scaled(res_tot, r.residual_total) < TOL
+    residual_parity(c, res_pde, res_tot, r.residual_pde, r.residual_total, tag="extrapolated pf_extra")
 
 
 def test_jacobian_pair_sequential_and_residual_kernel_agree(tmp_path):
@@ -334,6 +346,9 @@ def test_jacobian_pair_sequential_and_residual_kernel_agree(tmp_path):
     # the quadrature residual against the residual from the rows: round-off apart; the matrix to round-off as well
     assert val["rows"].shape == val["quad"].shape and linf_scaled(val["rows"], val["quad"]) < TOL
     assert rhs["rows"].shape == rhs["quad"].shape and linf_scaled(rhs["rows"], rhs["quad"]) < TOL
+    # the files hold the (u,u) values / the residuals of four boxes end to end and no reference: the (u,u) block at its own
+    # scale, with no floor, is all the per-block check can say here
+    PS.assert_blocks([val["rows"]], [val["quad"]], TOL, "quadrature residual kernel against the rows", ["uu x4"])
 
 
 # ---- 2-D row-owner Jacobian (pfm_cart2d.hip): BASELINE config 2 with the matrix, tests/sneddon_2d_1.prm on a uniform mesh
@@ -389,6 +404,8 @@ def test_cart2d_split_runs_stay_on_the_general_family():
     A = blocks_to_global(ctx, c.layout, values)
     A.sort_indices()
     assert linf_scaled(A.data, A_ref.data) < 1e-11 and linf_scaled(res_pde, r.residual_pde) < 1e-11
+    PS.assert_matrix(A, A_ref, c.layout, TOL, "2-D split on a lattice")  # (at the project's bar; measured 1.3e-15)
+    PS.assert_residual(res_pde, r.residual_pde, A_ref, c.layout, c.sol, TOL, "2-D split on a lattice residual_pde")
 
 
 # ---- heterogeneous material on the row-owner kernels (cracks.cc:2207-2216): per-cell Lame coefficients, cells handed
@@ -426,6 +443,7 @@ def test_cart_heterogeneous_material_residual(dim, n, lo, hi, monolithic):
     r, _, _ = oracle(c, True)
     assert linf_scaled(res_pde, r.residual_pde) < TOL
     assert linf_scaled(res_tot, r.residual_total) < TOL
+    residual_parity(c, res_pde, res_tot, r.residual_pde, r.residual_total, tag="heterogeneous")
 
 
 def test_cart_heterogeneous_material_mean_diagonal_and_constraints():
@@ -505,6 +523,8 @@ def test_assemble_nl_residual_device_reads_the_solution_itself(dim, n, blocked):
     A = blocks_to_global(ctx, c.layout, [v.cpu().numpy() for v in vals])
     A.sort_indices()
     assert linf_scaled(A.data, A_ref.data) < TOL and linf_scaled(bufs[0].cpu().numpy(), r.residual_pde) < TOL
+    PS.assert_matrix(A, A_ref, c.layout, TOL, "Jacobian after the fused residual entry")
+    PS.assert_residual(bufs[0].cpu().numpy(), r.residual_pde, A_ref, c.layout, sol2, TOL, "Jacobian after the fused residual entry, residual_pde")
 
 
 @pytest.mark.parametrize("n,het", [((15, 15, 2), False), ((16, 31, 5), False), ((14, 29, 3), False), ((33, 16, 26), False),
@@ -548,6 +568,7 @@ def test_residual_kernels_with_planes_by_transfer_agree(n, het, monkeypatch):
     c.sol = sol2
     r, _, _ = oracle(c, True)
     assert linf_scaled(rx, r.residual_pde) < TOL and linf_scaled(tx, r.residual_total) < TOL
+    residual_parity(c, rx, tx, r.residual_pde, r.residual_total, tag="planes by transfer")
 
 
 def dead_zone(c):
@@ -690,6 +711,9 @@ def test_general_family_launch_modes_agree(tmp_path):
     for tag in ("general", "overlay"):
         assert val[tag].shape == val["general_seq"].shape
         assert linf_scaled(val[tag], val["general_seq"]) < TOL and linf_scaled(rhs[tag], rhs["general_seq"]) < TOL
+        # launch mode against launch mode, no reference: the residual parts at their own scale (the value file holds the four
+        # blocks end to end, so only the whole is at hand there)
+        PS.assert_parts(rhs[tag], rhs["general_seq"], PS.is_phi(cases.kat_miehe_tension().layout), TOL, f"launch mode {tag}")
     # side stream or not: only the entries that receive atomic adds (rows next to hanging nodes) may differ in the last bit
     same = val["general"] == val["general_seq"]
     assert same.mean() > 0.5
@@ -721,11 +745,14 @@ def test_host_pointer_call_with_the_hosts_own_arrays(blocked, registered):
         assert (A.indptr == A_ref.indptr).all() and (A.indices == A_ref.indices).all()
         assert np.abs(A.data).max() < 1e70 and linf_scaled(A.data, A_ref.data) < TOL
         assert linf_scaled(res_pde, ref.residual_pde) < TOL
+        PS.assert_matrix(A, A_ref, c.layout, TOL, f"host arrays, call {rep}")
+        PS.assert_residual(res_pde, ref.residual_pde, A_ref, c.layout, sol, TOL, f"host arrays, call {rep} residual_pde")
         if blocked:
             assert not values[1].any()  # (u,phi) = 0, cracks.cc:2333-2337
     ctx.assemble_host(c.sol, c.old, c.oldold, True, out=(None, res_pde, res_tot))
     ro = O.assemble(c.mesh, c.layout, c.params, c.sol, c.old, c.oldold, c.cu, c.ch, True)
     assert linf_scaled(res_pde, ro.residual_pde) < TOL and linf_scaled(res_tot, ro.residual_total) < TOL
+    residual_parity(c, res_pde, res_tot, ro.residual_pde, ro.residual_total, tag="host arrays")
     if registered:
         ctx.host_unregister(values[0])
         ctx.host_unregister()

@@ -10,7 +10,7 @@ import pytest
 import scipy.sparse as sp
 
 from cracks_amd import mesh as M
-from gpu_util import TOL, blocks_to_global, linf_scaled, make_context, oracle
+from gpu_util import TOL, blocks_to_global, linf_scaled, make_context, oracle, reference_parity
 from test_gpu_cart import box_case
 from test_gpu_pattern import _permuted_patterns
 
@@ -54,6 +54,7 @@ def _against_oracle(ctx, c, vals, res, A_ref, res_ref):
     e_mat, e_res = linf_scaled(A.data, A_ref.data), linf_scaled(res, res_ref)
     print(f"|dA|_inf = {e_mat:.2e}, |dR|_inf = {e_res:.2e}")
     assert e_mat < TOL and e_res < TOL
+    reference_parity(c.layout, c.sol, A, A_ref, [(res, res_ref, "pde")], tag="face tiles")
 
 
 @pytest.mark.parametrize("flagged", [True, False], ids=["dirichlet_faces", "no_flags"])

@@ -16,6 +16,7 @@ import pytest
 import scipy.sparse as sp
 
 import oracle_api as O
+import parity_scale as PS
 from cracks_amd import mesh as M
 
 pytestmark = pytest.mark.gpu
@@ -118,6 +119,7 @@ def test_rows_of_the_bench_mesh_match_the_oracle():
         return t[torch.from_numpy(np.asarray(idx, np.int64)).cuda()].cpu().numpy()
 
     worst = 0.0
+    samples = _Samples()
     for (i, j, k), gn in zip(pts, S):
         nb = [ii + NP * (jj + NP * kk) for kk in range(max(k - 1, 0), min(k + 1, n) + 1)
               for jj in range(max(j - 1, 0), min(j + 1, n) + 1) for ii in range(max(i - 1, 0), min(i + 1, n) + 1)]
@@ -135,21 +137,47 @@ def test_rows_of_the_bench_mesh_match_the_oracle():
             row = A_ref[lu(ln, c)].toarray().ravel()
             for dd in range(3):
                 worst = max(worst, np.abs(got_uu[c, :, dd] - row[lu(lnb, dd)]).max())
+                samples.add("uu", got_uu[c, :, dd], row[lu(lnb, dd)])
             worst = max(worst, np.abs(got_up[c] - row[lu(lnb, 3)]).max())
+            samples.add("uphi", got_up[c], row[lu(lnb, 3)])
         row = A_ref[lu(ln, 3)].toarray().ravel()
         for dd in range(3):
             worst = max(worst, np.abs(got_pu[:, dd] - row[lu(lnb, dd)]).max())
+            samples.add("phiu", got_pu[:, dd], row[lu(lnb, dd)])
         worst = max(worst, np.abs(got_pp - row[lu(lnb, 3)]).max())
+        samples.add("phiphi", got_pp, row[lu(lnb, 3)])
         # residuals: Jacobian call (pde), residual-only call (pde + total)
         gd = [3 * gn + c for c in range(3)] + [3 * N + gn]
         ld = [lu(ln, c) for c in range(4)]
         worst = max(worst, np.abs(fetch(res_full, gd) - r.residual_pde[ld]).max())
         worst = max(worst, np.abs(fetch(res_d, gd) - r_res.residual_pde[ld]).max())
         worst = max(worst, np.abs(fetch(tot_d, gd) - r_res.residual_total[ld]).max())
+        for key, got_v, want_v in (("full", fetch(res_full, gd), r.residual_pde[ld]), ("pde", fetch(res_d, gd), r_res.residual_pde[ld]),
+                                   ("tot", fetch(tot_d, gd), r_res.residual_total[ld])):
+            samples.add(key + "_u", got_v[:-1], want_v[:-1])
+            samples.add(key + "_phi", got_v[-1:], want_v[-1:])
     scale = max(1.0, float(np.abs(r.values).max()))
     print(f"full size {n}^3: {len(pts)} rows, {len(seams)} seam planes of chunk lengths {sorted(lens)}, {cell_ids.size} oracle cells, "
           f"max |GPU - oracle| = {worst:.3e} (scale {scale:.2e})")
     assert worst < 1e-12 * scale
+    samples.check()
+
+
+class _Samples:
+    """The sampled rows by block and residual part.  The oracle ran on the cells around the samples only, so there is no
+    reference matrix of the whole mesh and no diagonal for every column: the per-block and per-part checks of
+    tests/parity_scale.py on the rows that exist -- each block and each part at its own |reference|_inf, no floor."""
+
+    def __init__(self):
+        self.got, self.want = {}, {}
+
+    def add(self, key, got, want):
+        self.got.setdefault(key, []).append(np.ravel(got))
+        self.want.setdefault(key, []).append(np.ravel(want))
+
+    def check(self):
+        keys = list(self.got)
+        PS.assert_blocks([np.concatenate(self.got[k]) for k in keys], [np.concatenate(self.want[k]) for k in keys], 1e-12, "full size row samples", keys)
 
 
 @pytest.mark.timeout(900)
@@ -239,6 +267,7 @@ def test_rows_of_the_config2_mesh_match_the_oracle():
         return t[torch.from_numpy(np.asarray(idx, np.int64)).cuda()].cpu().numpy()
 
     worst = 0.0
+    samples = _Samples()
     for (i, j), gn in zip(pts, S):
         nb = [ii + NP * jj for jj in range(max(j - 1, 0), min(j + 1, n) + 1) for ii in range(max(i - 1, 0), min(i + 1, n) + 1)]
         d = len(nb)
@@ -255,16 +284,25 @@ def test_rows_of_the_config2_mesh_match_the_oracle():
             row = A_ref[lu(ln, c)].toarray().ravel()
             for dd in range(2):
                 worst = max(worst, np.abs(got_uu[c, :, dd] - row[lu(lnb, dd)]).max())
+                samples.add("uu", got_uu[c, :, dd], row[lu(lnb, dd)])
             worst = max(worst, np.abs(got_up[c] - row[lu(lnb, 2)]).max())
+            samples.add("uphi", got_up[c], row[lu(lnb, 2)])
         row = A_ref[lu(ln, 2)].toarray().ravel()
         for dd in range(2):
             worst = max(worst, np.abs(got_pu[:, dd] - row[lu(lnb, dd)]).max())
+            samples.add("phiu", got_pu[:, dd], row[lu(lnb, dd)])
         worst = max(worst, np.abs(got_pp - row[lu(lnb, 2)]).max())
+        samples.add("phiphi", got_pp, row[lu(lnb, 2)])
         gd = [2 * gn + c for c in range(2)] + [2 * N + gn]
         ld = [lu(ln, c) for c in range(3)]
         worst = max(worst, np.abs(fetch(res_full, gd) - r.residual_pde[ld]).max())
         worst = max(worst, np.abs(fetch(res_d, gd) - r_res.residual_pde[ld]).max())
         worst = max(worst, np.abs(fetch(tot_d, gd) - r_res.residual_total[ld]).max())
+        for key, got_v, want_v in (("full", fetch(res_full, gd), r.residual_pde[ld]), ("pde", fetch(res_d, gd), r_res.residual_pde[ld]),
+                                   ("tot", fetch(tot_d, gd), r_res.residual_total[ld])):
+            samples.add(key + "_u", got_v[:-1], want_v[:-1])
+            samples.add(key + "_phi", got_v[-1:], want_v[-1:])
     scale = max(1.0, float(np.abs(r.values).max()))
     print(f"full size {n}^2: {len(pts)} rows, {cell_ids.size} oracle cells, max |GPU - oracle| = {worst:.3e} (scale {scale:.2e})")
     assert worst < 1e-12 * scale
+    samples.check()

@@ -9,6 +9,7 @@ import pytest
 import oracle_api as O
 from cracks_amd import mesh as M
 from cracks_amd import partition as P
+import parity_scale as PS
 from gpu_util import linf_scaled
 
 pytestmark = pytest.mark.gpu
@@ -20,6 +21,40 @@ def _global_problem(dim, n):
     h = g.min_cell_diameter()
     u, phi, po, poo, flags = bench.synthetic_state(g, np.arange(g.n_nodes), h, dim)
     return g, h, u, phi, po, poo, flags
+
+
+def _global_diagonal(ref_pat, ref_vals):
+    """|diagonal| of the single-rank matrix over the global dofs, from its (u,u) and (phi,phi) blocks"""
+    out = []
+    for b in (0, 3):
+        rp, ci = ref_pat[b]
+        rows = np.repeat(np.arange(rp.size - 1), np.diff(rp))
+        d = np.zeros(rp.size - 1)
+        on = ci == rows
+        d[rows[on]] = np.abs(ref_vals[b][on])
+        out.append(d)
+    return np.concatenate(out)
+
+
+class _BlockAccumulator:
+    """The compared rows of one block of a rank against the single rank's: per entry at sqrt(|d_i| |d_j|), d the diagonal of
+    the single-rank matrix over the global rows, and the block at its own |want|_inf (tests/parity_scale.py).  The single
+    rank is a GPU path too; its diagonal only sets the scale."""
+
+    def __init__(self, d_ref, n_u, b):
+        self.d, self.b = d_ref, b
+        self.r0, self.c0 = (n_u if b in (2, 3) else 0), (n_u if b in (1, 3) else 0)
+        self.got, self.want, self.grow, self.gcol = [], [], [], []
+
+    def add(self, grow, got, want):
+        for k, w in want.items():
+            self.got.append(got[k])
+            self.want.append(w)
+            self.grow.append(self.r0 + grow)
+            self.gcol.append(self.c0 + k)
+
+    def check(self, tag):
+        PS.assert_rank_block(self.got, self.want, self.d, np.asarray(self.grow, np.int64), np.asarray(self.gcol, np.int64), PS.BLOCKS[self.b], 1e-12, tag)
 
 
 @pytest.mark.parametrize("dim,n,world,path", [(3, (12, 11, 10), 2, 1), (3, (12, 11, 10), 8, 1), (3, (9, 9, 9), 4, 0),
@@ -51,6 +86,7 @@ def test_owned_rows_match_single_rank(dim, n, world, path):
     ref_vals = [m.cpu().numpy() for m in ref.system_pde_matrix]
     ref_res = ref.system_pde_residual.cpu().numpy()
     ref_pat = [ref.ctx.pattern(b) for b in range(4)]
+    d_ref = _global_diagonal(ref_pat, ref_vals)  # of the single-rank matrix, over the global dofs [u | phi]
 
     p = P.factor_ranks(world, dim)
     lps = [P.build_local_problem(dim, n, p, r) for r in range(world)]
@@ -109,6 +145,8 @@ def test_owned_rows_match_single_rank(dim, n, world, path):
             gd_u = (gi[:no, None] * dim + np.arange(dim)[None, :]).ravel()
             assert linf_scaled(res[:no * dim], ref_res[gd_u]) < 1e-12
             assert linf_scaled(res[no * dim:], ref_res[N * dim + gi[:no]]) < 1e-12
+            # (the single rank is a GPU path as well: each part at its own scale, no floor)
+            PS.assert_blocks([res[:no * dim], res[no * dim:]], [ref_res[gd_u], ref_res[N * dim + gi[:no]]], 1e-12, f"rank {r} residual", ["u", "phi"])
             if residual_only:
                 continue
             # matrix rows: map local columns to global and compare value by value
@@ -118,6 +156,7 @@ def test_owned_rows_match_single_rank(dim, n, world, path):
                 grp, gci = ref_pat[b]
                 ncr = dim if b in (0, 1) else 1
                 ncc = dim if b in (0, 2) else 1
+                acc = _BlockAccumulator(d_ref, N * dim, b)
                 rows = no * ncr
                 for lr in np.linspace(0, rows - 1, min(rows, 400)).astype(int):
                     node, c = divmod(lr, ncr)
@@ -129,6 +168,8 @@ def test_owned_rows_match_single_rank(dim, n, world, path):
                     assert set(got) == set(want)
                     scale = max(1.0, max(abs(x) for x in want.values()))
                     assert max(abs(got[k] - want[k]) for k in want) < 1e-12 * scale
+                    acc.add(grow, got, want)
+                acc.check(f"rank {r}")
 
 
 @pytest.mark.parametrize("kind,world,ghost_layer", [("slit2d", 4, "closure"), ("slit2d", 3, "closure"), ("box3d", 2, "closure"),
@@ -181,6 +222,7 @@ def test_general_partition_owned_rows_match_single_rank(kind, world, ghost_layer
     ref_vals = [m.cpu().numpy() for m in ref.system_pde_matrix]
     ref_res = ref.system_pde_residual.cpu().numpy()
     ref_pat = [ref.ctx.pattern(b) for b in range(4)]
+    d_ref = _global_diagonal(ref_pat, ref_vals)  # of the single-rank matrix, over the global dofs [u | phi]
 
     # "dealii+shipped": the cell set a deal.II host hands over (its one-cell ghost layer + the cells that reach an owned
     # row through a hanging vertex, shipped by their owners: partition.hanging_closure_shipments, the glue)
@@ -220,12 +262,14 @@ def test_general_partition_owned_rows_match_single_rank(kind, world, ghost_layer
         gd_u = (gi[:no, None] * dim + np.arange(dim)[None, :]).ravel()
         assert linf_scaled(res[:no * dim], ref_res[gd_u]) < 1e-12
         assert linf_scaled(res[no * dim:], ref_res[N * dim + gi[:no]]) < 1e-12
+        PS.assert_blocks([res[:no * dim], res[no * dim:]], [ref_res[gd_u], ref_res[N * dim + gi[:no]]], 1e-12, "rank residual", ["u", "phi"])
         for b in range(4):
             rp, ci = a.ctx.pattern(b)
             vals = a.system_pde_matrix[b].cpu().numpy()
             grp, gci = ref_pat[b]
             ncr = dim if b in (0, 1) else 1
             ncc = dim if b in (0, 2) else 1
+            acc = _BlockAccumulator(d_ref, N * dim, b)
             for lr in range(no * ncr):
                 node, c = divmod(lr, ncr)
                 grow = gi[node] * ncr + c
@@ -236,6 +280,8 @@ def test_general_partition_owned_rows_match_single_rank(kind, world, ghost_layer
                 assert set(got) == set(want)
                 scale = max(1.0, max(abs(x) for x in want.values()))
                 assert max(abs(got[k] - want[k]) for k in want) < 1e-12 * scale
+                acc.add(grow, got, want)
+            acc.check("rank")
 
 
 @pytest.mark.parametrize("world,cells,extra", [(2, 40, []), (8, 36, []), (4, 300, ["--dim", "2", "--residual-only"])])

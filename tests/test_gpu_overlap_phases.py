@@ -22,7 +22,8 @@ import scipy.sparse as sp
 from cracks_amd import mesh as M
 from cracks_amd import partition as P
 from cracks_amd.assembler import Context, node_flags_from_dof_flags
-from gpu_util import blocks_to_global, exchange_ghosts, linf_scaled
+import parity_scale as PS
+from gpu_util import blocks_to_global, exchange_ghosts, linf_scaled, reference_matrix, total_matrix
 from test_gpu_cart import box_case, dead_zone, heterogeneous, oracle
 
 pytestmark = pytest.mark.gpu
@@ -124,8 +125,11 @@ def box_ranks(c, n, p):
 class Reference:
     """A (scipy CSR over the global dofs, indices sorted) or None, and the two residuals"""
 
-    def __init__(self, layout, A, res_pde, res_tot):
+    def __init__(self, layout, A, res_pde, res_tot, sol=None, A_scale=None, A_tot=None):
         self.layout, self.A, self.res_pde, self.res_tot = layout, A, res_pde, res_tot
+        # for the per-row scale of tests/parity_scale.py: the solution and the reference matrices whose rows belong to the two
+        # vectors (None: no reference matrix at hand, the residual parts are compared at their own scale only)
+        self.sol, self.A_scale, self.A_tot = sol, (A if A_scale is None else A_scale), A_tot
         if A is not None:
             A.sort_indices()
             rows = np.repeat(np.arange(A.shape[0], dtype=np.int64), np.diff(A.indptr))
@@ -135,7 +139,8 @@ class Reference:
 def oracle_reference(c, residual_only):
     r, rp, ci = oracle(c, residual_only)
     A = None if residual_only else sp.csr_matrix((r.values, ci, rp), shape=(c.layout.n_dofs,) * 2)
-    return Reference(c.layout, A, r.residual_pde, r.residual_total)
+    A_scale = reference_matrix(c) if residual_only else A  # (residual-only: one oracle Jacobian of the case for the scales)
+    return Reference(c.layout, A, r.residual_pde, r.residual_total, c.sol, A_scale, total_matrix(c, A_scale))
 
 
 def check_against_reference(rank, W, residual_only, ref):
@@ -148,8 +153,10 @@ def check_against_reference(rank, W, residual_only, ref):
     gd = glay.dof(gi[nn], cc)  # the global rows this rank owns
     res = W[-2:] if residual_only else W[-1:]
     assert linf_scaled(res[0][ld], ref.res_pde[gd]) < TOL
+    _rows_at_their_scale(res[0][ld], ref.res_pde[gd], ref, ref.A_scale, gd, cc == dim, f"rank {rank.index} residual_pde")
     if residual_only:
         assert linf_scaled(res[1][ld], ref.res_tot[gd]) < TOL
+        _rows_at_their_scale(res[1][ld], ref.res_tot[gd], ref, ref.A_tot, gd, cc == dim, f"rank {rank.index} residual_total")
         return
     keys, vals = [], []
     for b in range(ctx.n_blocks):
@@ -173,6 +180,23 @@ def check_against_reference(rank, W, residual_only, ref):
     pos = np.minimum(np.searchsorted(ref.keys, keys), ref.keys.size - 1)
     assert (ref.keys[pos] == keys).all()
     assert linf_scaled(vals, ref.A.data[pos]) < TOL
+    # the owned rows' entries at the scales of the global reference: d = diag(ref.A) over the global dofs, each block at its own
+    grow, gcol = keys // ref.A.shape[1], keys % ref.A.shape[1]
+    blk = PS.block_of_entries(glay, grow, gcol)
+    for b in range(4):
+        m = blk == b
+        if ref.sol is not None:  # a reference proper: per entry and per block
+            PS.assert_rank_block(vals[m], ref.A.data[pos][m], ref.A.diagonal(), grow[m], gcol[m], PS.BLOCKS[b], TOL, f"rank {rank.index}, owned rows")
+        else:  # ref is another GPU path: the block at its own scale only
+            PS.assert_blocks([vals[m]], [ref.A.data[pos][m]], TOL, f"rank {rank.index}, owned rows", [PS.BLOCKS[b]])
+
+
+def _rows_at_their_scale(v, want, ref, A, gd, phi_rows, tag):
+    """owned rows of a rank: per part always, per row where the reference carries its matrix and solution"""
+    if A is not None and ref.sol is not None:
+        PS.assert_rank_rows(v, want, A, ref.layout, ref.sol, gd, TOL, tag)
+    else:
+        PS.assert_parts(v, want, phi_rows, TOL, tag)
 
 
 # ---- the protocol -------------------------------------------------------------------------------------------------------

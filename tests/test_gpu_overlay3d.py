@@ -9,7 +9,7 @@ import scipy.sparse as sp
 import cases
 import oracle_api as O
 from cracks_amd import mesh as M
-from gpu_util import blocks_to_global, linf_scaled, make_context
+from gpu_util import blocks_to_global, linf_scaled, make_context, reference_parity, total_matrix
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
@@ -62,6 +62,8 @@ def check_against_oracle(c, ctx):
     ro = O.assemble(c.mesh, c.layout, c.params, c.sol, c.old, c.oldold, c.cu, c.ch, True, None, None, c.cell_lambda, c.cell_mu)
     _, res_pde, res_tot = ctx.assemble_host(c.sol, c.old, c.oldold, True)
     assert linf_scaled(res_pde, ro.residual_pde) < TOL and linf_scaled(res_tot, ro.residual_total) < TOL
+    reference_parity(c.layout, c.sol, A, A_ref, [(res, r.residual_pde, "pde"), (res_pde, ro.residual_pde, "pde"), (res_tot, ro.residual_total, "tot")],
+                     tag=f"overlay3d {c.name}", A_tot=total_matrix(c, A_ref))
 
 
 @pytest.mark.parametrize("blocked", [True, False])

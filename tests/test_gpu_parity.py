@@ -10,7 +10,8 @@ import pytest
 import cases
 import oracle_api as O
 from cracks_amd import mesh as M
-from gpu_util import full_parity as _full_parity, linf_scaled, make_context, oracle as _oracle
+import parity_scale as PS
+from gpu_util import full_parity as _full_parity, linf_scaled, make_context, oracle as _oracle, residual_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -27,6 +28,8 @@ def test_step0_residual_golden_through_the_abi(make):
     r, _, _ = _oracle(c, True)
     assert linf_scaled(res_pde, r.residual_pde) < TOL
     assert linf_scaled(res_tot, r.residual_total) < TOL
+    # per row and per part (tests/parity_scale.py), the scales from one oracle Jacobian of the case
+    residual_parity(c, res_pde, res_tot, r.residual_pde, r.residual_total, tag="step 0")
 
 
 @pytest.mark.parametrize("make", cases.ALL_KATS, ids=lambda f: f.__name__)
@@ -138,10 +141,14 @@ def test_device_resident_assembler_matches_host_entry():
     for b in range(4):
         assert linf_scaled(asm.system_pde_matrix[b].cpu().numpy(), values[b]) < 1e-13
     assert linf_scaled(asm.system_pde_residual.cpu().numpy(), res_pde) < 1e-13
+    # one GPU entry against the other, no reference matrix in play: each block and each residual part at its own scale
+    PS.assert_blocks([m.cpu().numpy() for m in asm.system_pde_matrix], values, TOL, "assembler against the host entry", PS.BLOCKS)
+    PS.assert_parts(asm.system_pde_residual.cpu().numpy(), res_pde, PS.is_phi(c.layout), TOL, "assembler against the host entry")
     asm.assemble_nl_residual()
     asm.synchronize()
     r, _, _ = _oracle(c, True)
     assert linf_scaled(asm.system_total_residual.cpu().numpy(), r.residual_total) < TOL
+    residual_parity(c, asm.system_pde_residual.cpu().numpy(), asm.system_total_residual.cpu().numpy(), r.residual_pde, r.residual_total, tag="assembler")
     assert torch.isfinite(asm.system_pde_residual).all()
 
 

@@ -17,6 +17,7 @@ from cracks_amd import capi
 from cracks_amd import mesh as M
 from cracks_amd import partition as P
 from cracks_amd.assembler import Context, node_flags_from_dof_flags
+import parity_scale as PS
 from gpu_util import make_context
 
 pytestmark = pytest.mark.gpu
@@ -116,9 +117,12 @@ def test_partitioned_rows_land_in_a_column_sorted_host_csr(world, path):
             want = np.asarray(A_ref[grow, gcol]).ravel()
             got = vals[b].cpu().numpy()
             assert np.abs(got - want).max() < TOL * max(1.0, np.abs(want).max()), (rank, b)
+            PS.assert_rank_block(got, want, A_ref.diagonal(), grow, gcol, PS.BLOCKS[b], TOL, f"pattern rank {rank}")
         r = res.cpu().numpy()
         assert np.abs(r[:no * dim] - res_ref[(gi[:no, None] * dim + np.arange(dim)).ravel()]).max() < TOL
         assert np.abs(r[no * dim:] - res_ref[N * dim + gi[:no]]).max() < TOL
+        gd = np.concatenate([(gi[:no, None] * dim + np.arange(dim)).ravel(), N * dim + gi[:no]])
+        PS.assert_rank_rows(r, res_ref[gd], A_ref, lay, sol, gd, TOL, f"pattern rank {rank} residual_pde")
         ctx.close()
     assert n_perm_rows > 0  # ghost columns were present
 
@@ -284,5 +288,11 @@ def test_lattice_with_permuted_node_numbering(blocked):
             grow, gcol = rows, ci
         want = np.asarray(A_ref[grow, gcol]).ravel()
         assert np.abs(values[b] - want).max() < TOL * max(1.0, np.abs(want).max()), b
+        if blocked:
+            PS.assert_rank_block(values[b], want, A_ref.diagonal(), grow, gcol, PS.BLOCKS[b], TOL, "permuted pattern")
+        else:  # one value array over all four blocks: on the global matrix
+            PS.assert_matrix(sp.csr_matrix((values[b], (grow, gcol)), shape=A_ref.shape), sp.csr_matrix((want, (grow, gcol)), shape=A_ref.shape), lay,
+                             TOL, "permuted pattern")
     assert np.abs(res - res_ref).max() < TOL * max(1.0, np.abs(res_ref).max())
+    PS.assert_residual(res, res_ref, A_ref, lay, c.sol, TOL, "permuted pattern residual_pde")
     ctx.close()

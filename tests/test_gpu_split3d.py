@@ -21,7 +21,8 @@ from cracks_amd import capi
 from cracks_amd import mesh as M
 from cracks_amd import partition as P
 from cracks_amd.assembler import Context, node_flags_from_dof_flags
-from gpu_util import TOL, blocks_to_global, exchange_ghosts, linf_scaled, make_context, oracle
+import parity_scale as PS
+from gpu_util import TOL, blocks_to_global, exchange_ghosts, linf_scaled, make_context, oracle, reference_parity, total_matrix
 
 pytestmark = pytest.mark.gpu
 
@@ -152,6 +153,9 @@ def test_entry_by_entry_against_the_numpy_reference(kind, blocked, d, cell_lame)
     print(f"split3d {kind} blocked={blocked} d={d}: matrix {e_A:.2e} residual {e_R:.2e} residual-only {e_ro:.2e} / {e_tot:.2e} "
           f"(eigenvalue margin {margin:.3f})")
     assert e_A < TOL and e_R < TOL and e_ro < TOL and e_tot < TOL
+    # at the scale of each entry, block, row and part (no constraints: residual_total's rows are the matrix's too)
+    A_on = reference_parity(c.layout, c.sol, _matrix(ctx, c, values), A_ref, [(res, r_ref, "pde"), (res_ro, r_ref, "pde"), (tot_ro, r_ref, "tot")],
+                            tag=f"split3d {kind} blocked={blocked} d={d}")
     # the line-search entry on the same context
     import torch
     d_sol = torch.from_numpy(c.sol).cuda()
@@ -159,6 +163,7 @@ def test_entry_by_entry_against_the_numpy_reference(kind, blocked, d, cell_lame)
     ctx.assemble_nl_residual_device(d_sol.data_ptr(), d_r.data_ptr(), d_t.data_ptr())
     ctx.sync_status()
     assert linf_scaled(d_r.cpu().numpy(), r_ref) < TOL
+    reference_parity(c.layout, c.sol, None, A_on, [(d_r.cpu().numpy(), r_ref, "pde")], tag="split3d line-search entry")
     if kind == "box":
         # split off again: the context returns to its own kernels, bit for bit what a fresh context computes
         off = _copy(c.params, timestep_number=0)
@@ -196,6 +201,8 @@ def _tension_parity(c, **ctx_kw):
     e_2, e_t = linf_scaled(res2, r2.residual_pde), linf_scaled(tot2, r2.residual_total)
     print(f"split3d tension {c.name}: matrix {e_A:.2e} residual {e_R:.2e} residual-only {e_2:.2e} / {e_t:.2e}")
     assert e_A < TOL and e_R < TOL and e_2 < TOL and e_t < TOL
+    reference_parity(c.layout, c.sol, A, A_ref, [(res, r.residual_pde, "pde"), (res2, r2.residual_pde, "pde"), (tot2, r2.residual_total, "tot")],
+                     tag=f"split3d tension {c.name}", A_tot=total_matrix(off, A_ref))
     ctx.close()
 
 
@@ -271,6 +278,8 @@ def test_pure_tension_on_two_ranks():
         ctx.sync_status()
         gdof = np.concatenate([(gi[:no, None] * 3 + np.arange(3)[None, :]).ravel(), 3 * g.n_nodes + gi[:no]])
         assert linf_scaled(res.cpu().numpy(), r.residual_pde[gdof]) < TOL
+        # the owned rows of this rank at the scales of the global reference: s_i of the global rows, d = diag(A_ref)
+        PS.assert_rank_rows(res.cpu().numpy(), r.residual_pde[gdof], A_ref, glay, cg.sol, gdof, TOL, "split3d two ranks, owned rows")
         scale = max(1.0, np.abs(r.values).max())
         for b in range(4):
             rp, ci = ctx.pattern(b)
@@ -281,6 +290,7 @@ def test_pure_tension_on_two_ranks():
             gcol = gi[ci // ncc] * ncc + ci % ncc + (0 if b in (0, 2) else 3 * g.n_nodes)
             want = np.asarray(A_ref[grow, gcol]).ravel()
             assert np.abs(v - want).max() < TOL * scale
+            PS.assert_rank_block(v, want, A_ref.diagonal(), grow, gcol, PS.BLOCKS[b], TOL, "split3d two ranks")
         ctx.close()
 
 
@@ -330,6 +340,9 @@ def test_extrusion_reproduces_the_2d_oracle_with_its_split_on():
         assert e_R < TOL and e_A < TOL
         _, res_ro, _ = ctx.assemble_host(*s3, True)
         assert linf_scaled(S @ res_ro, hz * r.residual_pde) < TOL
+        # the collapsed 3-D matrix against h_z times the 2-D oracle's, at the scales of the latter
+        reference_parity(l2, s2[0], (S @ A3 @ S.T).tocsr(), hz * A2, [(S @ res, hz * r.residual_pde, "pde"), (S @ res_ro, hz * r.residual_pde, "pde")],
+                         tag=f"split3d extrusion blocked={blocked}")
         ctx.close()
 
 
@@ -359,6 +372,7 @@ def test_exactly_diagonal_isotropic_and_zero_strain():
     _, res_ro, tot_ro = ctx.assemble_host(c.sol, c.old, c.oldold, True)
     print(f"split3d special cases: matrix {e_A:.2e} residual {e_R:.2e} residual-only {linf_scaled(res_ro, r_ref):.2e}")
     assert e_A < TOL and e_R < TOL and linf_scaled(res_ro, r_ref) < TOL and np.isfinite(tot_ro).all()
+    reference_parity(c.layout, c.sol, _matrix(ctx, c, values), A_ref, [(res, r_ref, "pde"), (res_ro, r_ref, "pde")], tag="split3d special cases")
     values2, res2, _ = ctx.assemble_host(c.sol, c.old, c.oldold, False)
     assert res2.tobytes() == res.tobytes() and values2[0].tobytes() == values[0].tobytes()
     ctx.sync_status()

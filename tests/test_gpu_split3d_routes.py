@@ -24,7 +24,8 @@ import split3d_ref as R
 import topology_cases as T
 from cracks_amd import capi
 from cracks_amd import mesh as M
-from gpu_util import TOL, linf_scaled
+import parity_scale as PS
+from gpu_util import TOL, linf_scaled, reference_parity
 from test_gpu_split3d import LAM, MU, SHEAR, _box, _copy, _matrix, _params, _spectral_context
 
 pytestmark = pytest.mark.gpu
@@ -88,6 +89,9 @@ class Ref:
         # residuals -- distributed with the hanging-node constraints alone under the active-set scheme (outer_solver 0: the
         # lines of constraints_update keep their entries), with constraints_update under every other scheme
         self.tot = R.residual_total(c.layout, c.mesh.cells, c.params, Re, c.cu, c.ch)
+        # the matrix whose rows belong to residual_total (the scales of tests/parity_scale.py): under the active-set scheme the
+        # same element matrices distributed with the hanging-node constraints alone
+        self.A_tot = self.A if c.params.outer_solver != 0 else R.distribute_matrix(c.mesh, c.layout, Ke, Re, c.ch)[0]
 
 
 def check_split(tag, ctx, c, ref):
@@ -100,6 +104,8 @@ def check_split(tag, ctx, c, ref):
     print(f"split3d routes {tag}: matrix {e[0]:.2e} residual {e[1]:.2e} residual-only {e[2]:.2e} / {e[3]:.2e} "
           f"(eigenvalue margin {ref.margin:.3f})")
     assert max(e) < TOL, e
+    reference_parity(c.layout, c.sol, A, ref.A, [(res, ref.res, "pde"), (pde, ref.res, "pde"), (tot, ref.tot, "tot")], tag=f"split3d routes {tag}",
+                     A_tot=ref.A_tot)
     return e
 
 
@@ -214,7 +220,7 @@ def test_two_ranks_and_both_halves_of_the_overlapped_assembly(blocked):
     g = M.box_mesh(3, n)
     c = mixed_case("two_ranks", g, blocked, _params(), 60, faces_and_active_set(5)(g))
     ref = Ref(c)
-    refs = {False: OP.Reference(c.layout, ref.A, ref.res, None), True: OP.Reference(c.layout, None, ref.res, ref.tot)}
+    refs = {False: OP.Reference(c.layout, ref.A, ref.res, None, c.sol), True: OP.Reference(c.layout, None, ref.res, ref.tot, c.sol, ref.A, ref.A_tot)}
     # the ranks are built with the parameters of step 0 (the split is refused before the model is set), then switched
     off = cases.Case("step0", g, c.layout, _copy(c.params, timestep_number=0), c.sol, c.old, c.oldold, c.cu, c.ch)
     ranks = OP.box_ranks(off, n, (2, 1, 1))
@@ -263,6 +269,9 @@ def test_device_line_search_on_a_split_context(blocked, solver, norm, restore):
     pde_ref = R.distribute_vector(c.layout, mesh.cells, Re, c.cu)
     tot_ref = R.residual_total(c.layout, mesh.cells, c.params, Re, c.cu, c.ch)
     e = (linf_scaled(runs[1]["vec"]["pde"][0], pde_ref), linf_scaled(runs[1]["vec"]["tot"][0], tot_ref))
+    # (no reference matrix at the accepted vector: the residual parts at their own scale)
+    for got_v, ref_v in ((runs[1]["vec"]["pde"][0], pde_ref), (runs[1]["vec"]["tot"][0], tot_ref)):
+        PS.assert_parts(got_v, ref_v, PS.is_phi(c.layout), TOL, "split3d routes line search, accepted vector")
     print(f"split3d routes line search blocked={blocked} solver={solver}: residual at the accepted vector {e[0]:.2e} / {e[1]:.2e} "
           f"(eigenvalue margin {margin:.3f})")
     assert max(e) < TOL

@@ -24,7 +24,8 @@ import split_voldev_cases as SC
 from cracks_amd import capi
 from cracks_amd import mesh as M
 from cracks_amd.assembler import Context, node_flags_from_dof_flags
-from gpu_util import TOL, linf_scaled, make_context, oracle
+import parity_scale as PS
+from gpu_util import TOL, linf_scaled, make_context, oracle, residual_parity
 from test_gpu_split3d import _copy
 from test_gpu_split3d_routes import smallest_edge
 
@@ -64,7 +65,17 @@ def check(tag, ctx, c, ref):
     e = (linf_scaled(pde, ref.pde), linf_scaled(tot, ref.tot))
     print(f"split_lattice {tag}: residual_pde {e[0]:.2e} residual_total {e[1]:.2e}")
     assert np.isfinite(pde).all() and np.isfinite(tot).all() and max(e) < TOL, e
+    scaled(tag, c, ref, pde, tot)
     return pde, tot
+
+
+def scaled(tag, c, ref, pde=None, tot=None):
+    """per row and per part (tests/parity_scale.py), the scales from the reference's own Jacobian of the state"""
+    A_ref, A_tot = ref.matrices()
+    if pde is not None:
+        PS.assert_residual(pde, ref.pde, A_ref, c.layout, ref._sol, TOL, f"split_lattice {tag} residual_pde")
+    if tot is not None:
+        PS.assert_residual(tot, ref.tot, A_tot, c.layout, ref._sol, TOL, f"split_lattice {tag} residual_total")
 
 
 # ---------------------------------------------------------------- 1
@@ -147,6 +158,7 @@ def test_without_compression_it_is_the_unsplit_oracle():
     e = (linf_scaled(pde, r.residual_pde), linf_scaled(tot, r.residual_total))
     print(f"split_lattice {c.name} against the unsplit oracle: {e[0]:.2e} / {e[1]:.2e}")
     assert max(e) < TOL
+    residual_parity(off, pde, tot, r.residual_pde, r.residual_total, tag="split_lattice against the unsplit oracle")
     ctx.close()
 
 
@@ -182,7 +194,7 @@ def test_two_ranks_and_both_halves_of_the_overlapped_assembly(blocked):
     c = LC.two_rank_case(blocked)
     SC.assert_mixed(c)
     r = LC.ref(LC.two_rank_case, blocked)
-    ref = OP.Reference(c.layout, None, r.pde, r.tot)
+    ref = OP.Reference(c.layout, None, r.pde, r.tot, c.sol, *r.matrices())
     single = _context(c)
     assert single.split_route_info() == (LATTICE, 1)
     one = check(c.name + " (one rank)", single, c, r)
@@ -205,6 +217,8 @@ def test_two_ranks_and_both_halves_of_the_overlapped_assembly(blocked):
             print(f"split_lattice {c.name} rank {rk.index} output {k}: against the single rank {e:.2e} "
                   f"(same bits: {OP._same_bits(W[k][ld], one[k][gd])}), phase 1 wrote {share:.2f}")
             assert e < TOL
+            # (a rank against the single rank, owned rows only: the parts at their own scale)
+            PS.assert_parts(W[k][ld], one[k][gd], cc == 3, TOL, f"split_lattice {c.name} rank {rk.index} output {k}")
             assert 0.0 < share < 1.0, "each sub-box has interior and boundary tiles"
         rk.ctx.close()
 
@@ -224,6 +238,7 @@ def test_overlay_level_lattices_with_the_law_and_the_general_family_for_the_rest
     assert _bytes(*_residuals(ctx, c)) == _bytes(*first)
     values, res = _full(ctx, c)
     assert linf_scaled(res, ref.pde) < TOL
+    scaled(c.name + " full assembly", c, ref, res)
     ctx.set_split_route(GENERAL)
     assert ctx.split_route_info() == (GENERAL, 0) and ctx.overlay_info() == info
     values_g, res_g = _full(ctx, c)
@@ -262,6 +277,7 @@ def test_fused_entry_equals_the_three_call_sequence(shape, kind):
         funcs.append(ctx.functionals())
     ref = LC.ref(LC.box_case, shape, kind)
     assert linf_scaled(outs[1][0], ref.pde) < TOL and linf_scaled(outs[1][1], ref.tot) < TOL
+    scaled("fused entry", c, ref, outs[1][0], outs[1][1])
     assert same_bits(outs[0][0], outs[1][0]) and same_bits(outs[0][1], outs[1][1])
     assert same_bits(np.asarray(funcs[0]), np.asarray(funcs[1])) and np.isfinite(funcs[1]).all()
     ctx.close()
@@ -295,8 +311,10 @@ def test_device_line_search_under_both_routes(blocked, solver, norm, restore):
     assert LS.same_bits(l["vec"]["sol"][0], g["vec"]["sol"][0])  # a function of the step count alone
     for k in ("pde", "tot"):
         assert linf_scaled(l["vec"][k][0], g["vec"][k][0]) < TOL
+        PS.assert_parts(l["vec"][k][0], g["vec"][k][0], PS.is_phi(c.layout), TOL, f"split_lattice line search, route against route, {k}")
     r = LC.Ref(c, l["vec"]["sol"][0])
     assert linf_scaled(l["vec"]["pde"][0], r.pde) < TOL and linf_scaled(l["vec"]["tot"][0], r.tot) < TOL
+    scaled("line search, accepted vector", c, r, l["vec"]["pde"][0], l["vec"]["tot"][0])
     for ctx in ctxs.values():
         ctx.close()
 
@@ -323,9 +341,11 @@ def test_one_living_context_through_both_routes():
     unsplit, _ = run(off, GENERAL, 0)
     lattice, (pde, tot) = run(c, LATTICE, 1)
     assert linf_scaled(pde, ref.pde) < TOL and linf_scaled(tot, ref.tot) < TOL
+    scaled("living context, lattice route", c, ref, pde, tot)
     assert run(off, LATTICE, 0)[0] == unsplit
     general, (pde_g, tot_g) = run(c, GENERAL, 0)
     assert linf_scaled(pde_g, ref.pde) < TOL and linf_scaled(tot_g, ref.tot) < TOL
+    scaled("living context, general route", c, ref, pde_g, tot_g)
     assert general[:-2] == lattice[:-2]  # the full assembly does not follow the route
     again, _ = run(c, LATTICE, 1)
     assert again == lattice

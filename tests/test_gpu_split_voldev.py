@@ -26,7 +26,8 @@ import split_voldev_cases as SC
 import split_voldev_ref as V
 from cracks_amd import capi
 from cracks_amd.assembler import Context, node_flags_from_dof_flags
-from gpu_util import TOL, linf_scaled, make_context, oracle
+import parity_scale as PS
+from gpu_util import TOL, linf_scaled, make_context, oracle, reference_parity, total_matrix
 from test_gpu_split3d import _copy, _matrix
 from test_gpu_split3d_routes import constrained_rows_hold_their_placeholder, smallest_edge
 
@@ -48,6 +49,9 @@ class Ref:
         Ke, Re, self.E = law.element_matrices(c.mesh, c.layout, c.params, c.sol, c.old, c.oldold, c.cell_lambda, c.cell_mu)
         self.A, self.res = R.distribute_matrix(c.mesh, c.layout, Ke, Re, c.cu)
         self.tot = R.residual_total(c.layout, c.mesh.cells, c.params, Re, c.cu, c.ch)
+        # the matrix whose rows belong to residual_total (the scales of tests/parity_scale.py): under the active-set scheme the
+        # same element matrices distributed with the hanging-node constraints alone
+        self.A_tot = self.A if c.params.outer_solver != 0 else R.distribute_matrix(c.mesh, c.layout, Ke, Re, c.ch)[0]
 
 
 @functools.lru_cache(maxsize=None)
@@ -78,6 +82,8 @@ def check(tag, ctx, c, ref):
     e = (e_A, linf_scaled(out[1], ref.res), linf_scaled(out[2], ref.res), linf_scaled(out[3], ref.tot))
     print(f"split_voldev {tag}: matrix {e[0]:.2e} residual {e[1]:.2e} residual-only {e[2]:.2e} / {e[3]:.2e}")
     assert all(np.isfinite(v).all() for v in out[0]) and max(e) < TOL, e
+    reference_parity(c.layout, c.sol, A, ref.A, [(out[1], ref.res, "pde"), (out[2], ref.res, "pde"), (out[3], ref.tot, "tot")], tag=f"split_voldev {tag}",
+                     A_tot=ref.A_tot)
     return out
 
 
@@ -95,6 +101,8 @@ def check_unsplit_oracle(tag, ctx, c):
          linf_scaled(out[3], r2.residual_total))
     print(f"split_voldev {tag} against the unsplit oracle: matrix {e[0]:.2e} residual {e[1]:.2e} residual-only {e[2]:.2e} / {e[3]:.2e}")
     assert all(np.isfinite(v).all() for v in out[0]) and max(e) < TOL, e
+    reference_parity(c.layout, c.sol, A, A_ref, [(out[1], r.residual_pde, "pde"), (out[2], r2.residual_pde, "pde"), (out[3], r2.residual_total, "tot")],
+                     tag=f"split_voldev {tag} against the unsplit oracle", A_tot=total_matrix(off, A_ref))
     return out
 
 
@@ -262,7 +270,7 @@ def test_two_ranks_and_both_halves_of_the_overlapped_assembly(blocked):
     c = SC.two_rank_case(blocked)
     SC.assert_mixed(c)
     ref = _ref(SC.two_rank_case, blocked)
-    refs = {False: OP.Reference(c.layout, ref.A, ref.res, None), True: OP.Reference(c.layout, None, ref.res, ref.tot)}
+    refs = {False: OP.Reference(c.layout, ref.A, ref.res, None, c.sol), True: OP.Reference(c.layout, None, ref.res, ref.tot, c.sol, ref.A, ref.A_tot)}
     off = cases.Case("step0", c.mesh, c.layout, _copy(c.params, timestep_number=0), c.sol, c.old, c.oldold, c.cu, c.ch)
     ranks = OP.box_ranks(off, n, (2, 1, 1))
     for r in ranks:
@@ -306,6 +314,9 @@ def test_device_line_search_on_a_model_3_context(blocked, solver, norm, restore)
     pde_ref = R.distribute_vector(c.layout, c.mesh.cells, Re, c.cu)
     tot_ref = R.residual_total(c.layout, c.mesh.cells, c.params, Re, c.cu, c.ch)
     e = (linf_scaled(runs[1]["vec"]["pde"][0], pde_ref), linf_scaled(runs[1]["vec"]["tot"][0], tot_ref))
+    # (no reference matrix at the accepted vector: the residual parts at their own scale)
+    for got_v, ref_v in ((runs[1]["vec"]["pde"][0], pde_ref), (runs[1]["vec"]["tot"][0], tot_ref)):
+        PS.assert_parts(got_v, ref_v, PS.is_phi(c.layout), TOL, "split_voldev line search, accepted vector")
     print(f"split_voldev line search blocked={blocked} solver={solver}: residual at the accepted vector {e[0]:.2e} / {e[1]:.2e} "
           f"(share {share:.2f}, margin {margin:.1e})")
     assert max(e) < TOL

@@ -15,7 +15,7 @@ import pytest
 
 import topology_cases as T
 from cracks_amd.capi import PfmError
-from gpu_util import TOL, full_parity, make_context, oracle
+from gpu_util import TOL, full_parity, make_context, oracle, reference_matrix, total_matrix
 
 pytestmark = pytest.mark.gpu
 
@@ -100,7 +100,7 @@ def test_colour_overflow_next_to_the_gather_every_time():
     time: twenty Jacobians on one context, each against the oracle."""
     import scipy.sparse as sp
 
-    from gpu_util import blocks_to_global, linf_scaled
+    from gpu_util import blocks_to_global, linf_scaled, reference_parity
 
     c = T.fan3d_41_hanging()
     r, rp, ci = oracle(c, False)
@@ -113,6 +113,7 @@ def test_colour_overflow_next_to_the_gather_every_time():
         A.sort_indices()
         assert (A.indices == A_ref.indices).all()
         assert linf_scaled(A.data, A_ref.data) < TOL and linf_scaled(res, r.residual_pde) < TOL
+        reference_parity(c.layout, c.sol, A, A_ref, [(res, r.residual_pde, "pde")], tag="topology, long rows")
     ctx.close()
 
 
@@ -185,7 +186,8 @@ def test_colour_overflow_on_a_partition_along_z(blocked):
     for residual_only in (False, True):
         r, rp, ci = oracle(c, residual_only)
         A = None if residual_only else sp.csr_matrix((r.values, ci, rp), shape=(c.layout.n_dofs,) * 2)
-        ref = Reference(c.layout, A, r.residual_pde, r.residual_total)
+        A_scale = A if A is not None else reference_matrix(c)
+        ref = Reference(c.layout, A, r.residual_pde, r.residual_total, c.sol, A_scale, total_matrix(c, A_scale))
         for rank, buf in zip(ranks, recv):
             ctx = rank.ctx
             assert ctx.kernel_path == 0

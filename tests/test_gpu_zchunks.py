@@ -22,7 +22,7 @@ import scipy.sparse as sp
 
 from cracks_amd.assembler import Context
 from cracks_amd.capi import PfmError
-from gpu_util import blocks_to_global, exchange_ghosts, linf_scaled, make_context
+from gpu_util import blocks_to_global, exchange_ghosts, linf_scaled, make_context, reference_parity, residual_parity
 from test_gpu_cart import box_case, dead_zone, heterogeneous, oracle
 
 pytestmark = pytest.mark.gpu
@@ -113,12 +113,14 @@ def full_against_oracle(c, ctx, outs):
     assert (A.indptr == A_ref.indptr).all() and (A.indices == A_ref.indices).all()
     assert linf_scaled(A.data, A_ref.data) < TOL
     assert linf_scaled(outs[-1].cpu().numpy(), r.residual_pde) < TOL
+    reference_parity(c.layout, c.sol, A, A_ref, [(outs[-1].cpu().numpy(), r.residual_pde, "pde")], tag=f"zchunks {c.name}")
 
 
 def residual_against_oracle(c, outs):
     r, _, _ = oracle(c, True)
     assert linf_scaled(outs[0].cpu().numpy(), r.residual_pde) < TOL
     assert linf_scaled(outs[1].cpu().numpy(), r.residual_total) < TOL
+    residual_parity(c, outs[0].cpu().numpy(), outs[1].cpu().numpy(), r.residual_pde, r.residual_total, tag="zchunks")
 
 
 def case3(n, kind, blocked):
