@@ -118,9 +118,10 @@ class Context:
         self.split_model = int(model)
 
     def set_split_route(self, route: int):
-        """Which kernels take the residual-only assembly of a 3-D context under split model 3 (capi.SPLIT_ROUTE_*): 0 the
+        """Which kernels take the residual-only assembly of a 3-D context under a split law (capi.SPLIT_ROUTE_*): 0 the
         general family over all cells (default), 1 the row-owner residual kernel of the box, the sub-box or the level lattices
-        with the law at its q-points.  At any time on a living context; no effect on full assemblies and on model 1."""
+        with the law at its q-points under model 3 (no effect on model 1), 3 the same kernel under model 3 and under model 1,
+        the spectral law.  At any time on a living context; no effect on full assemblies."""
         self._check(self.lib.pfm_set_split_route(self._h, int(route)), "pfm_set_split_route")
         self.split_route = int(route)
 
@@ -672,8 +673,8 @@ class Assembler:
 
     @property
     def split_route(self) -> int:
-        """Where the residual-only assembly of a 3-D mesh under split model 3 runs (Context.set_split_route): 0 the general
-        family, 1 the row-owner kernels of the lattice.  May change at any time."""
+        """Where the residual-only assembly of a 3-D mesh under a split law runs (Context.set_split_route): 0 the general
+        family, 1 the row-owner kernels of the lattice under model 3, 3 under models 1 and 3.  May change at any time."""
         return self.ctx.split_route
 
     @split_route.setter

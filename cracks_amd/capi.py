@@ -19,7 +19,7 @@ STATUS_NAMES = {0: "PFM_OK", 1: "PFM_ERR_BAD_ARG", 2: "PFM_ERR_HIP", 3: "PFM_ERR
 COMM_ID_BYTES = 128
 LAYOUT_INTERLEAVED, LAYOUT_BLOCKED = 0, 1
 SPLIT_REFERENCE, SPLIT_SPECTRAL, SPLIT_VOLDEV = 0, 1, 3  # pfm_set_split_model (2 is unassigned)
-SPLIT_ROUTE_GENERAL, SPLIT_ROUTE_LATTICE = 0, 1  # pfm_set_split_route
+SPLIT_ROUTE_GENERAL, SPLIT_ROUTE_LATTICE, SPLIT_ROUTE_LATTICE_ANY = 0, 1, 3  # pfm_set_split_route (2 is unassigned)
 
 # every symbol include/pfm_assemble.h declares
 EXPORTS = [

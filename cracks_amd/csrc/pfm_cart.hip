@@ -80,7 +80,7 @@ namespace pfm
       double ih[3], vol, vih[3], geih[3]; // 1 / h_k, h_x h_y h_z, vol / h_k, G_c eps vol / h_k^2
       double c_g, c_pd, c_r2, c_r3;       // 1 - kappa, (alpha_B - 1) p, -2 (alpha_B - 1) p, G_c / eps
       double c_pdg, c_pdk;                // c_pd / c_g, c_pd kappa / c_g: the pressure term through the moments of g (residual_cell_poly)
-      double d_rhs;                       // decompose_stress_rhs: the weight of sigma- in k_cart_residual3<false, VOLDEV>
+      double d_rhs;                       // decompose_stress_rhs: the weight of sigma- in k_cart_residual3<false, VOLDEV, SPECTRAL>
     };
 
     Scal make_scal(const pfm_params &prm, const CartView &cv, int dim)
@@ -866,7 +866,11 @@ namespace pfm
     // VOLDEV (LIN = false only; CartPlan::voldev): the volumetric-deviatoric stress split of pfm_split3.h at the q-point,
     // sigma+ in place of sigma and decompose_stress_rhs sigma- next to it (cracks.cc:2393-2432 with stress_term_plus /
     // stress_term_minus).  The law has a max: the polynomial forms (residual_cell_poly, k_cart_residual3x / 3d) cannot carry it.
-    template <bool LIN, bool VOLDEV = false>
+    // SPECTRAL (LIN = false only; CartPlan::spectral): the eigen split of pfm_split3.h at the q-point, split_strain<false> and
+    // split_stress3 as the general family runs them.  sigma- has shear components here, so all six fluxes carry it.  The three
+    // q_x of a (q_y, q_z) pass go through ONE copy of the q-point body (a loop that is not unrolled): three inlined copies of
+    // the Jacobi sweeps do not fit the register budget of two workgroups per CU.
+    template <bool LIN, bool VOLDEV = false, bool SPECTRAL = false>
     __global__ __launch_bounds__(RTX *RTY, 2) void k_cart_residual3(DevView v, CartView cv, Scal S,
                                                                  double *__restrict__ res_pde,
                                                                  double *__restrict__ res_tot, int write_total,
@@ -1094,26 +1098,47 @@ namespace pfm
                     // sigma : E = sum_a sigma_aa g_aa + sum_{a<b} sigma_ab t_ab
                     const double t01 = gu[0][1] + gu[1][0], t02 = gu[0][2] + gu[2][0], t12 = gu[1][2] + gu[2][1];
                     const double trE = gu[0][0] + gu[1][1] + gu[2][2];
-                    double s00, s11, s22, zm = 0.0; // zm: decompose_stress_rhs sigma- = zm I
-                    if constexpr (VOLDEV)
+                    double spE, z00, z11, z22, z01, z02, z12; // sigma+ : E and the fluxes Z (symmetric); the weights enter with the sums
+                    if constexpr (SPECTRAL)
                       {
-                        const split3::VolDev V = split3::voldev(trE, lam, mu);
-                        s00 = split3::voldev_sigma_plus(V, mu, gu[0][0], true);
-                        s11 = split3::voldev_sigma_plus(V, mu, gu[1][1], true);
-                        s22 = split3::voldev_sigma_plus(V, mu, gu[2][2], true);
-                        zm = S.d_rhs * V.sm_iso;
+                        // Voigt order 00, 11, 22, 01, 02, 12, plain components
+                        const double Ev[6] = {gu[0][0], gu[1][1], gu[2][2], 0.5 * t01, 0.5 * t02, 0.5 * t12};
+                        split3::Split3 P;
+                        split3::split_strain<false>(Ev, P);
+                        double sp[6], sm[6];
+                        split3::split_stress3(Ev, P, lam, mu, sp, sm);
+                        spE = 0.0;
+#pragma unroll
+                        for (int r = 0; r < 6; ++r)
+                          spE += sp[r] * (r < 3 ? Ev[r] : 2.0 * Ev[r]);
+                        // Z = g sigma+ + decompose_stress_rhs sigma- - (alpha_B - 1) p pfx^2 I: sigma- has shear components
+                        const double pd = c_pd * pf2;
+                        z00 = fma(g, sp[0], fma(S.d_rhs, sm[0], -pd)), z11 = fma(g, sp[1], fma(S.d_rhs, sm[1], -pd)), z22 = fma(g, sp[2], fma(S.d_rhs, sm[2], -pd));
+                        z01 = fma(g, sp[3], S.d_rhs * sm[3]), z02 = fma(g, sp[4], S.d_rhs * sm[4]), z12 = fma(g, sp[5], S.d_rhs * sm[5]);
                       }
                     else
                       {
-                        const double lt = lam * trE;
-                        s00 = fma(mu2, gu[0][0], lt), s11 = fma(mu2, gu[1][1], lt), s22 = fma(mu2, gu[2][2], lt);
+                        double s00, s11, s22, zm = 0.0; // zm: decompose_stress_rhs sigma- = zm I
+                        if constexpr (VOLDEV)
+                          {
+                            const split3::VolDev V = split3::voldev(trE, lam, mu);
+                            s00 = split3::voldev_sigma_plus(V, mu, gu[0][0], true);
+                            s11 = split3::voldev_sigma_plus(V, mu, gu[1][1], true);
+                            s22 = split3::voldev_sigma_plus(V, mu, gu[2][2], true);
+                            zm = S.d_rhs * V.sm_iso;
+                          }
+                        else
+                          {
+                            const double lt = lam * trE;
+                            s00 = fma(mu2, gu[0][0], lt), s11 = fma(mu2, gu[1][1], lt), s22 = fma(mu2, gu[2][2], lt);
+                          }
+                        const double s01 = mu * t01, s02 = mu * t02, s12 = mu * t12;
+                        spE = fma(s00, gu[0][0], fma(s11, gu[1][1], s22 * gu[2][2])) + fma(s01, t01, fma(s02, t02, s12 * t12));
+                        // Z = g sigma+ - (alpha_B - 1) p pfx^2 I
+                        const double pd = VOLDEV ? c_pd * pf2 - zm : c_pd * pf2;
+                        z00 = fma(g, s00, -pd), z11 = fma(g, s11, -pd), z22 = fma(g, s22, -pd);
+                        z01 = g * s01, z02 = g * s02, z12 = g * s12;
                       }
-                    const double s01 = mu * t01, s02 = mu * t02, s12 = mu * t12;
-                    const double spE = fma(s00, gu[0][0], fma(s11, gu[1][1], s22 * gu[2][2])) + fma(s01, t01, fma(s02, t02, s12 * t12));
-                    // Z = g sigma+ - (alpha_B - 1) p pfx^2 I (symmetric); the weights enter with the sums
-                    const double pd = VOLDEV ? c_pd * pf2 - zm : c_pd * pf2;
-                    const double z00 = fma(g, s00, -pd), z11 = fma(g, s11, -pd), z22 = fma(g, s22, -pd);
-                    const double z01 = g * s01, z02 = g * s02, z12 = g * s12;
                     // gamma pen + (1 - kappa) sigma:E pf - G_c/eps (1 - pf) - 2 (alpha_B - 1) p pf tr(E)
                     double rq = fma(pf, fma(c_r2, trE, fma(c_g, spE, c_r3)), -c_r3);
                     if constexpr (!LIN)
@@ -1148,9 +1173,22 @@ namespace pfm
                         r1 = fma(wx, rq, r1);
                       }
                   };
-                  xq(0, std::true_type{});
-                  xq(1, std::false_type{});
-                  xq(2, std::false_type{});
+                  if constexpr (SPECTRAL)
+                    {
+#pragma unroll
+                      for (int c = 0; c < 4; ++c)
+                        A0[c] = Bs[c] = B1[c] = Cs[c] = C1[c] = 0.0;
+                      rs = r1 = 0.0;
+#pragma unroll 1
+                      for (int qx = 0; qx < 3; ++qx) // one copy of the eigen solve
+                        xq(qx, std::false_type{});
+                    }
+                  else
+                    {
+                      xq(0, std::true_type{});
+                      xq(1, std::false_type{});
+                      xq(2, std::false_type{});
+                    }
                   // y and z factors: M[i][j][k] += P Y_j Z_k + B dY_j Z_k + C Y_j dZ_k with (Y, dY) = (1, 0) | (eta, 1/h_y)
                   const double kx = ihx * wyz, ky = ihy * wyz, kz = ihz * wyz, kze = kz * eta;
 #pragma unroll
@@ -1694,7 +1732,9 @@ namespace pfm
         const bool flat = pl.residual == PFM_RES_2M; // a wave per R2N nodes of a row and chunk of rows; 3-D: chunks of z-planes
         const TileGrid &g = pl.grid[flat ? PFM_ZC_RES2 : PFM_ZC_RES3];
         // (CartPlan::voldev: the split law in the q-point form, whatever the scheme)
-        const ResidualKernel kernel = pl.voldev ? k_cart_residual3<false, true> : residual_kernel[pl.residual][pl.residual_flag()];
+        const ResidualKernel kernel = pl.spectral ? k_cart_residual3<false, false, true>
+                                      : pl.voldev ? k_cart_residual3<false, true>
+                                                  : residual_kernel[pl.residual][pl.residual_flag()];
         if (g.n_tiles != 0)
           hipLaunchKernelGGL(kernel, dim3(flat ? g.n_tiles : xcd_grid(g.n_tiles)), dim3(flat ? 64 : RTX * RTY), 0, s_side, v, cv,
                              make_scal(p, cv, v.dim), res_pde, res_tot, (int)pl.residual_only, g.zc);

@@ -93,7 +93,7 @@ namespace pfm
     return g;
   }
 
-  enum CartResidual { PFM_RES_NONE, PFM_RES_3X, PFM_RES_3D, PFM_RES_3, PFM_RES_2M }; // k_cart_residual3x<het>, 3d<het>, 3<linear> (CartPlan::voldev: 3<false, true>), 2m<linear>
+  enum CartResidual { PFM_RES_NONE, PFM_RES_3X, PFM_RES_3D, PFM_RES_3, PFM_RES_2M }; // k_cart_residual3x<het>, 3d<het>, 3<linear> (CartPlan::voldev: 3<false, true>; spectral: 3<false, false, true>), 2m<linear>
   struct CartPlan
   {
     int dim = 0, phase = 0; // 0: the whole assembly; 1, 2: the halves of pfm_assemble_overlapped (ghost import in between)
@@ -102,6 +102,9 @@ namespace pfm
     // scalar statements on the strain and runs in k_cart_residual3<false, true>, for every scheme, cut into halves as an
     // unsplit PFM_RES_3 is (the Jacobian kernels have no split form: a full assembly stays unsupported)
     bool voldev = false;
+    // ... and under PFM_SPLIT_SPECTRAL on PFM_SPLIT_ROUTE_LATTICE_ANY: the eigen split of pfm_split3.h at the q-points of
+    // k_cart_residual3<false, false, true>.  In every other field the plan is the voldev plan of the same lattice and phase.
+    bool spectral = false;
     bool linear = false, interleaved = false, het = false; // scheme; layout; per-cell Lame coefficients (CartView::cell_lam)
     // Full 3-D assembly, linear scheme: every residual row is an exact function of its own matrix row (R_u = pressure part -
     // K_uu u, R_phi = G_c/eps mass - K_phiphi phi), so the Jacobian kernels write it and no residual kernel runs (2.1 of 15.8 ms
@@ -138,8 +141,11 @@ namespace pfm
     const CartScheme sc = cart_scheme(p);
     CartPlan pl;
     pl.dim = v.dim, pl.phase = phase, pl.residual_only = residual_only != 0;
-    pl.voldev = sc.split && v.dim == 3 && pl.residual_only && split.model == PFM_SPLIT_VOLDEV && split.route == PFM_SPLIT_ROUTE_LATTICE;
-    pl.supported = (!sc.split || pl.voldev) && (v.dim == 2 || v.dim == 3);
+    const bool lattice_law = sc.split && v.dim == 3 && pl.residual_only; // a split residual that the row-owner kernel can carry
+    pl.voldev = lattice_law && split.model == PFM_SPLIT_VOLDEV &&
+                (split.route == PFM_SPLIT_ROUTE_LATTICE || split.route == PFM_SPLIT_ROUTE_LATTICE_ANY);
+    pl.spectral = lattice_law && split.model == PFM_SPLIT_SPECTRAL && split.route == PFM_SPLIT_ROUTE_LATTICE_ANY;
+    pl.supported = (!sc.split || pl.voldev || pl.spectral) && (v.dim == 2 || v.dim == 3);
     if (!pl.supported)
       return pl;
     pl.linear = sc.linear, pl.interleaved = v.layout == PFM_LAYOUT_INTERLEAVED, pl.het = cv.cell_lam != nullptr;
@@ -154,7 +160,7 @@ namespace pfm
     if (v.dim == 2 && pl.residual_only)
       pl.residual = PFM_RES_2M;
     else if (v.dim == 3 && !pl.rows_residual)
-      pl.residual = (!(sc.linear && whole_lex) || pl.voldev) ? PFM_RES_3
+      pl.residual = (!(sc.linear && whole_lex) || pl.voldev || pl.spectral) ? PFM_RES_3
                     : (v.fused_solution && !pl.interleaved && v.n_nodes >= 64 && !Switches::res_no_wide_transfers()) ? PFM_RES_3X : PFM_RES_3D;
     pl.uu3_clock = sw.uu_clock && !pl.interleaved && !pl.het;
     pl.phi4_clock = (!pl.interleaved && !pl.het && sc.linear) ? sw.phi_clock : 0;

@@ -1402,10 +1402,10 @@ extern "C"
 
   int pfm_set_split_route(pfm_ctx *c, int route)
   {
-    if (!c || (route != PFM_SPLIT_ROUTE_GENERAL && route != PFM_SPLIT_ROUTE_LATTICE))
+    if (!c || (route != PFM_SPLIT_ROUTE_GENERAL && route != PFM_SPLIT_ROUTE_LATTICE && route != PFM_SPLIT_ROUTE_LATTICE_ANY))
       return c ? fail(c, PFM_ERR_BAD_ARG, "unknown split route") : PFM_ERR_BAD_ARG;
-    if (route == PFM_SPLIT_ROUTE_LATTICE && c->v.dim != 3)
-      return fail(c, PFM_ERR_UNSUPPORTED, "the lattice route carries the volumetric-deviatoric split, a 3-D law");
+    if (route != PFM_SPLIT_ROUTE_GENERAL && c->v.dim != 3)
+      return fail(c, PFM_ERR_UNSUPPORTED, "the lattice routes carry the 3-D split laws");
     c->split_route = route;
     return PFM_OK;
   }
@@ -2343,7 +2343,7 @@ extern "C"
   // (the A/B switches of the dispatch: pfm_switches.h)
   // the stress split in the matrix (cracks.cc:2294): the general family has it, the row-owner kernels do not
   static bool stress_split(const pfm_ctx *c) { return c->have_params && cart_scheme(c->prm).split; }
-  // ... but for what plan_cart takes from the law and the route of the context (CartPlan::voldev)
+  // ... but for what plan_cart takes from the law and the route of the context (CartPlan::voldev, CartPlan::spectral)
   static pfm::CartSplit cart_split(const pfm_ctx *c) { return {c->split_model, c->split_route}; }
 
   // Every decision of one assemble_impl call; what each means stands where it is made (plan_assembly, after_tables).
@@ -2376,13 +2376,15 @@ extern "C"
     // cartesian overlay of a general mesh (AMR meshes; stress-split runs on a lattice): patch kernel (2-D) or level
     // lattices (3-D) for the regular rows, the general family for the rest (PFM_NO_PATCH=1 at context creation: general
     // family alone): assemble_overlay
-    // (a split assembly keeps its level lattices where plan_cart has a kernel with the law: CartPlan::voldev)
+    // (a split assembly keeps its level lattices where plan_cart has a kernel with the law: CartPlan::voldev, CartPlan::spectral)
     if (!p.cart && c->v.dim == 3 && !c->levels3.empty() && c->kernel_path != 0 && !p.nothing)
       p.level = plan_cart(c->v, c->levels3[0].cv, c->prm, residual_only, 0, cart_n_cu(), cart_split(c));
     p.overlay3 = p.level.supported;
     p.patches = (!p.cart && c->v.dim == 2 && c->n_patch_blocks > 0 && c->kernel_path != 0 && !p.nothing) || p.overlay3;
     // 3-D cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*) -- wanted.  A split
     // assembly keeps it under PFM_SPLIT_VOLDEV, whose kernel is the unsplit form; the spectral instantiations have no SCR form
+    // (also where the level lattices take the spectral residual, CartPlan::spectral: the cells at hanging vertices then add with
+    // atomics and such an overlay residual is not bitwise reproducible)
     p.gather = !p.cart && c->v.dim == 3 && c->hang_gather && (!p.split || c->split_model == PFM_SPLIT_VOLDEV) && !p.nothing;
     // The two Jacobian kernels of a 3-D box next to each other (default): with equal LDS allocations (64 granules of 1280 B
     // each) any freed slot of a CU takes a workgroup of either kernel, the (u,u) and the phase-field workgroups mix and
@@ -3134,7 +3136,7 @@ extern "C"
         if (c->have_params)
           {
             const AssemblyPlan p = plan_assembly(c, 1, 0, nullptr);
-            *lattice_residual = ((p.cart && p.box.voldev) || (p.overlay3 && p.level.voldev)) ? 1 : 0;
+            *lattice_residual = ((p.cart && (p.box.voldev || p.box.spectral)) || (p.overlay3 && (p.level.voldev || p.level.spectral))) ? 1 : 0;
           }
       }
     return PFM_OK;

@@ -146,6 +146,7 @@ namespace pfm_glue_detail
     //                      line search's) to the row-owner kernels of the lattice (pfm_set_split_route; forwarded next to
     //                      split_model).  The Jacobian call's residual_pde still comes from the general family: the two
     //                      agree to rounding, not bit for bit.  Default PFM_SPLIT_ROUTE_GENERAL: nothing changes.
+    //                      PFM_SPLIT_ROUTE_LATTICE_ANY does the same under PFM_SPLIT_SPECTRAL as well.
     //   line_search_stepwise: line_search() runs the host loop of a rank with ghost peers (vector statements, scatter + halo +
     //                      assembly, pfm_residual_norms, MPI sum / max) also where pfm_line_search_device would do: the two
     //                      forms give the same vectors and the same result (tests/test_gpu_glue_line_search.py).

@@ -132,7 +132,7 @@ enum
 };
 int pfm_set_split_model(pfm_ctx *ctx, int model);
 /* Which kernels take the residual-only assembly (the line search's call, cracks.cc:2942-2957) of a 3-D context under
- * PFM_SPLIT_VOLDEV with the split on.
+ * split law (PFM_SPLIT_VOLDEV, or PFM_SPLIT_SPECTRAL under PFM_SPLIT_ROUTE_LATTICE_ANY) with the split on.
  *   PFM_SPLIT_ROUTE_GENERAL  the general family over all cells, as every split assembly.  Default: nothing about a caller
  *                            that never sets a route changes, bit for bit.
  *   PFM_SPLIT_ROUTE_LATTICE  the row-owner residual kernel of the cartesian family with the law at its q-points
@@ -142,14 +142,26 @@ int pfm_set_split_model(pfm_ctx *ctx, int model);
  *                            context forced to path 0 (pfm_ctx_force_path) run as under PFM_SPLIT_ROUTE_GENERAL.  A Newton step
  *                            then has its Jacobian call's residual_pde from the general family and its line-search
  *                            residuals from the lattice kernels: equal to rounding, not bit for bit.
+ *   PFM_SPLIT_ROUTE_LATTICE_ANY  (= 1 | 2) the row-owner residual kernel for every law that has a form there.  Under
+ *                            PFM_SPLIT_VOLDEV it is PFM_SPLIT_ROUTE_LATTICE, bit for bit.  Under PFM_SPLIT_SPECTRAL the eigen
+ *                            split runs at the q-points of k_cart_residual3<false, false, true> (split_strain<false> and
+ *                            split_stress3 of pfm_split3.h, the statements of the general family), on the same lattices and
+ *                            halves.  On a 3-D overlay the cells at hanging vertices stay with the general family, whose
+ *                            spectral instantiations have no scratch + gather form and add with atomics: such a residual
+ *                            is equal to the general route's to rounding but NOT bitwise reproducible run to run (a box or
+ *                            a partitioned sub-box is).  With model 0 it is accepted and has no effect.  The value 2 alone
+ *                            is unassigned and stays refused.
  * May be called at any time on a living context: the next assembly follows it.  An unknown route: PFM_ERR_BAD_ARG.
- * PFM_SPLIT_ROUTE_LATTICE on a 2-D context: PFM_ERR_UNSUPPORTED.  With model 0 or 1 the route is accepted and has no effect.
+ * PFM_SPLIT_ROUTE_LATTICE or _ANY on a 2-D context: PFM_ERR_UNSUPPORTED.  PFM_SPLIT_ROUTE_LATTICE with model 0 or 1 is
+ * accepted and has no effect.
  * pfm_ctx_split_route: the route set and, lattice_residual, whether a residual-only assembly with the current parameters,
- * model and forced path would run the law on the row-owner kernels (0 before pfm_set_params); either pointer may be null. */
+ * model and forced path would run its law, either one, on the row-owner kernels (0 before pfm_set_params); either pointer
+ * may be null. */
 enum
 {
   PFM_SPLIT_ROUTE_GENERAL = 0,
-  PFM_SPLIT_ROUTE_LATTICE = 1
+  PFM_SPLIT_ROUTE_LATTICE = 1,
+  PFM_SPLIT_ROUTE_LATTICE_ANY = 3
 };
 int pfm_set_split_route(pfm_ctx *ctx, int route);
 int pfm_ctx_split_route(const pfm_ctx *ctx, int *route, int *lattice_residual);

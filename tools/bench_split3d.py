@@ -21,6 +21,10 @@ route of pfm_set_split_route (general: the general family over all cells; lattic
 two yardstick arms with the split off -- "unsplit", what the context runs by itself (the polynomial row-owner kernels), and
 "unsplit_qpoint", the q-point form k_cart_residual3<false> the law sits in (reached with a penalised monolithic scheme) --
 all arms alternating round by round in one process.  The two routes are compared with each other on the timed state.
+
+--route general lattice --model spectral does the same for PFM_SPLIT_SPECTRAL: "general" is route 0, the general family over all
+cells, and "lattice" is PFM_SPLIT_ROUTE_LATTICE_ANY, k_cart_residual3<false, false, true>.  Same arms, alternation and JSON
+keys, plus "model".  Without --model spectral the --route run times model 3 as before.
 """
 import argparse
 import json
@@ -42,10 +46,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3, help="off / on alternations; the medians of all rounds are reported")
     ap.add_argument("--layout", choices=["blocked", "interleaved"], default="blocked")
-    ap.add_argument("--model", choices=["spectral", "voldev"], nargs="+", default=["spectral"], help="the split law(s) to time")
+    ap.add_argument("--model", choices=["spectral", "voldev"], nargs="+", default=None, help="the split law(s) to time (default: spectral)")
     ap.add_argument("--route", choices=["general", "lattice"], nargs="+", default=None,
-                    help="time the residual-only assembly of model 3 per split route on the box context instead (see above)")
+                    help="time the residual-only assembly of model 3 (--model spectral: of model 1) per split route on the box context "
+                         "instead (see above)")
     args = ap.parse_args()
+    route_spectral = bool(args.route) and args.model == ["spectral"]  # (--route without --model: model 3, as before)
+    args.model = args.model or ["spectral"]
 
     import torch
 
@@ -82,7 +89,8 @@ def main():
     asm.allocate_matrix()
 
     if args.route:
-        return bench_routes(args, asm, capi, mesh, prm_off, prm_on, O.make_params(**{"lambda": 121.15}, outer_solver=1, gamma_penal=1e-2, **base))
+        return bench_routes(args, asm, capi, mesh, prm_off, prm_on, O.make_params(**{"lambda": 121.15}, outer_solver=1, gamma_penal=1e-2, **base),
+                            route_spectral)
 
     def configure(split):
         # the unsplit assembly through the general family as well (the box's own kernels are not the yardstick here)
@@ -141,11 +149,11 @@ def main():
     print(json.dumps(rec))
 
 
-def bench_routes(args, asm, capi, mesh, prm_off, prm_on, prm_qpoint):
+def bench_routes(args, asm, capi, mesh, prm_off, prm_on, prm_qpoint, spectral=False):
     """--route: residual-only arms on the box context (kernel path 1), alternating round by round"""
-    routes = {"general": capi.SPLIT_ROUTE_GENERAL, "lattice": capi.SPLIT_ROUTE_LATTICE}
+    routes = {"general": capi.SPLIT_ROUTE_GENERAL, "lattice": capi.SPLIT_ROUTE_LATTICE_ANY if spectral else capi.SPLIT_ROUTE_LATTICE}
     arms = list(dict.fromkeys(args.route)) + ["unsplit", "unsplit_qpoint"]
-    asm.split_model = capi.SPLIT_VOLDEV
+    asm.split_model = capi.SPLIT_SPECTRAL if spectral else capi.SPLIT_VOLDEV
 
     def configure(arm):
         asm.split_route = routes.get(arm, capi.SPLIT_ROUTE_GENERAL)
@@ -174,6 +182,8 @@ def bench_routes(args, asm, capi, mesh, prm_off, prm_on, prm_qpoint):
         outs[arm] = (asm.system_pde_residual.clone(), asm.system_total_residual.clone())
     rec = {"metric": "split3d_routes_residual_only", "cells": int(mesh.n_cells), "layout": args.layout, "reps": args.reps, "rounds": args.rounds,
            "arms": arms}
+    if spectral:
+        rec["model"] = "spectral"
     if len(outs) == 2:
         rec["lattice_deviation_from_general"] = max(float((a - b).abs().max() / max(1.0, float(b.abs().max())))
                                                     for a, b in zip(outs["lattice"], outs["general"]))
