@@ -550,7 +550,6 @@ namespace pfm
       };
 
       int it = 0;
-      bool regular_prev = false; // the last step's copy-out took the regular path (its store count is known)
 #pragma unroll 1
       for (int k = kA; k < kB; ++k, ++it)
         {
@@ -593,6 +592,11 @@ namespace pfm
                   stamp6(-1);
                   // stores of this wave since its requests, on a regular tile: at least 2 per row component in waves 5, 6, 7
                   // (their third position lies outside the tile; the single values are wave 0's since round 6)
+                  // Whether the last step's copy-out took the regular path is read from the flags of its plane (parity
+                  // par ^ 1, untouched until the next step), not carried in a register across the plane loop.  Behind a
+                  // plane off the regular path the wait drains: a count derived from the row masks of that plane (round 8,
+                  // profiles/r08) did not pay
+                  const bool regular_prev = (NCOL == 3) && __builtin_amdgcn_readfirstlane(sh.irregular[par ^ 1]) == 0;
                   if (!regular_prev)
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                   else
@@ -979,36 +983,49 @@ namespace pfm
                   // and no such wait: the LDS reads of three positions in one batch, then their stores.
                   if (!(__builtin_amdgcn_readfirstlane(sh.irregular[par]) & 2))
                     {
-                      constexpr int NPOS = NN3 * rowlen, NB = 3;
-#pragma unroll 1
-                      for (int f0 = t; f0 < NPOS; f0 += NB * NT3)
+                      // Round 8: thread <-> (node group g, element e of the row) as on the regular path: lattice offset and
+                      // column component of a thread are fixed (one division per copy-out, none per position), the nodes
+                      // g, g + NGRP, ... follow in two batches of NB: every row of the tile and every element of a row once
+                      constexpr int NGRP = NT3 / rowlen, NB = (NCOL == 3) ? 3 : 4;
+                      static_assert(2 * NB * NGRP >= NN3 && (2 * NB - 1) * NGRP < NN3, "two batches cover the tile, no batch is empty");
+                      int tq = t;
+                      asm volatile("" : "+v"(tq)); // (g, e) are recomputed per component, not kept live across the node phases
+                      if (tq < NGRP * rowlen)
                         {
-                          long long dst[NB];
-                          unsigned mk[NB];
-                          int od[NB];
-                          double val[NB];
-#pragma unroll
-                          for (int i = 0; i < NB; ++i)
+                          int key; // g | o << 8 | d << 16: one register across the loop, unpacked per batch
+                          {
+                            const int g = tq / rowlen, e = tq - g * rowlen;
+                            const int o = e / NCOL, d = e - o * NCOL;
+                            key = g | (o << 8) | (d << 16);
+                          }
+#pragma unroll 1
+                          for (int b = 0; b < 2; ++b)
                             {
-                              const int f = min(f0 + i * NT3, NPOS - 1); // (clamped duplicates are dropped below)
-                              const int nl = f / rowlen, e = f - nl * rowlen;
-                              const int o = e / NCOL, d = e - o * NCOL;
-                              dst[i] = rowbase[nl];
-                              mk[i] = rowmask[nl];
-                              val[i] = lds_read64(stage + nl * STG + o * 3 + min(d, 2)); // (d = 3: zeroed below, no read in a branch)
-                              od[i] = o | (d << 8);
-                            }
-                          __builtin_amdgcn_sched_barrier(0);
+                              asm volatile("" : "+v"(key));
+                              const int n0 = (key & 0xff) + b * (NB * NGRP), o = (key >> 8) & 0xff, d = key >> 16;
+                              const double *src = stage + o * 3 + min(d, 2); // (d = 3: zeroed below, no read in a branch)
+                              long long dst[NB];
+                              unsigned mk[NB];
+                              double val[NB];
 #pragma unroll
-                          for (int i = 0; i < NB; ++i)
-                            {
-                              const int o = od[i] & 0xff, d = od[i] >> 8;
-                              const unsigned mask = mk[i];
-                              if (f0 + i * NT3 < NPOS && dst[i] >= 0 && ((mask >> o) & 1u))
+                              for (int i = 0; i < NB; ++i)
                                 {
-                                  const int sl = __popc(mask & ((1u << o) - 1u));
-                                  const int deg = __popc(mask & 0x7ffffffu);
-                                  vals[dst[i] + (long long)c * NCOL * deg + sl * NCOL + d] = (d < 3) ? val[i] : 0.0;
+                                  const int nl = min(n0 + i * NGRP, NN3 - 1); // (clamped duplicates are dropped below)
+                                  dst[i] = rowbase[nl];
+                                  mk[i] = rowmask[nl];
+                                  val[i] = lds_read64(src + nl * STG);
+                                }
+                              __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                              for (int i = 0; i < NB; ++i)
+                                {
+                                  const unsigned mask = mk[i];
+                                  if (n0 + i * NGRP < NN3 && dst[i] >= 0 && ((mask >> o) & 1u))
+                                    {
+                                      const int sl = __popc(mask & ((1u << o) - 1u));
+                                      const int deg = __popc(mask & 0x7ffffffu);
+                                      vals[dst[i] + (long long)c * NCOL * deg + sl * NCOL + d] = (d < 3) ? val[i] : 0.0;
+                                    }
                                 }
                             }
                         }
@@ -1149,7 +1166,6 @@ namespace pfm
 #undef PFM_COMPONENT
 #undef PFM_PER_SET
           }
-          regular_prev = regular_tile;
           stamp(6);
         }
       if constexpr (RES)
