@@ -89,6 +89,7 @@ class Context:
         self.n_owned_dofs = self.n_owned * (self.dim + 1)
         self.split_model = capi.SPLIT_REFERENCE  # what set_split_model last set (pfm_set_split_model)
         self.split_route = capi.SPLIT_ROUTE_GENERAL  # what set_split_route last set (pfm_set_split_route)
+        self.hanging_mode = capi.HANGING_MODE_DEFAULT  # what set_hanging_mode last set (pfm_set_hanging_mode)
 
     # -- helpers ---------------------------------------------------------------------
     def _check(self, rc: int, where: str):
@@ -131,6 +132,20 @@ class Context:
         a, b = C.c_int32(-1), C.c_int32(-1)
         self._check(self.lib.pfm_ctx_split_route(self._h, C.byref(a), C.byref(b)), "pfm_ctx_split_route")
         return int(a.value), int(b.value)
+
+    def set_hanging_mode(self, mode: int):
+        """How the cells at hanging vertices reach the outputs (capi.HANGING_MODE_*): 0 as ever (3-D unsplit and model 3:
+        scratch + ordered gather; 3-D model 1 and 2-D: atomic adds), 1 scratch + ordered gather in both dimensions and under
+        every law (bitwise reproducible), 2 the atomic class everywhere.  At any time on a living context."""
+        self._check(self.lib.pfm_set_hanging_mode(self._h, int(mode)), "pfm_set_hanging_mode")
+        self.hanging_mode = int(mode)
+
+    def hanging_info(self):
+        """(mode set, [cells at hanging vertices, the next assembly gathers them, rows of the gather tables, device bytes of
+        tables and scratch, the next assembly issues floating-point atomic adds]): pfm_ctx_hanging_info."""
+        m, out = C.c_int32(-1), (C.c_int64 * 5)()
+        self._check(self.lib.pfm_ctx_hanging_info(self._h, C.byref(m), out), "pfm_ctx_hanging_info")
+        return int(m.value), [int(x) for x in out]
 
     def set_params(self, prm):
         p = prm if isinstance(prm, PfmParams) else PfmParams.from_any(prm)
@@ -680,6 +695,16 @@ class Assembler:
     @split_route.setter
     def split_route(self, route: int):
         self.ctx.set_split_route(route)
+
+    @property
+    def hanging_mode(self) -> int:
+        """How the cells at hanging vertices reach the outputs (Context.set_hanging_mode): 0 the default, 1 scratch + ordered
+        gather wherever a form exists (bitwise reproducible), 2 the atomic class.  May change at any time."""
+        return self.ctx.hanging_mode
+
+    @hanging_mode.setter
+    def hanging_mode(self, mode: int):
+        self.ctx.set_hanging_mode(mode)
 
     def allocate_matrix(self):
         if not self.system_pde_matrix:

@@ -1181,14 +1181,20 @@ extern "C"
               {
                 v.hcell = dev_upload(c, hcell.data(), hcell.size());
                 v.cslot_h = dev_alloc<uint8_t>(c, hcells.size() * (size_t)(nv * MPH * nv * MPH));
-                if (dim == 3)
-                  {
-                    v.cres = dev_alloc<uint8_t>(c, hcells.size() * (size_t)pfm::PFM_CRES_BYTES);
-                    c->n_hcells = (int64_t)hcells.size();
-                    // round 6 default: scratch + ordered gather instead of FP64 atomics (ensure_hang_gather, on first use);
-                    // PFM_HANGING_ATOMIC=1 keeps the atomic class, PFM_HANGING_COLOURED=1 the colour classes of round 5
-                    c->hang_gather = !hanging_coloured && !Switches::hanging_atomic();
-                  }
+                // records of the reduced scatter (k_build_cres), in 2-D for PFM_HANGING_MODE_GATHER alone
+                v.cres = dev_alloc<uint8_t>(c, hcells.size() * (size_t)pfm::PFM_CRES_BYTES);
+                c->n_hcells = (int64_t)hcells.size();
+                // round 6 default in 3-D: scratch + ordered gather instead of FP64 atomics (ensure_hang_gather, on first use);
+                // PFM_HANGING_ATOMIC=1 keeps the atomic class, PFM_HANGING_COLOURED=1 the colour classes of round 5
+                c->hang_gather = dim == 3 && !hanging_coloured && !Switches::hanging_atomic();
+              }
+            else if (dim == 2 && hanging_cells(m, hn_idx, 0x7fffffff, hcells, hcell))
+              {
+                // a node with more parents than the slot table holds (the atomic class searches its rows, find_slot): the
+                // records take any number of parents as long as a quad resolves to 16 nodes at most
+                v.hcell = dev_upload(c, hcell.data(), hcell.size());
+                v.cres = dev_alloc<uint8_t>(c, hcells.size() * (size_t)pfm::PFM_CRES_BYTES);
+                c->n_hcells = (int64_t)hcells.size();
               }
           }
         clk.mark("ring cells");
@@ -1407,6 +1413,16 @@ extern "C"
     if (route != PFM_SPLIT_ROUTE_GENERAL && c->v.dim != 3)
       return fail(c, PFM_ERR_UNSUPPORTED, "the lattice routes carry the 3-D split laws");
     c->split_route = route;
+    return PFM_OK;
+  }
+
+  int pfm_set_hanging_mode(pfm_ctx *c, int mode)
+  {
+    if (!c || (mode != PFM_HANGING_MODE_DEFAULT && mode != PFM_HANGING_MODE_GATHER && mode != PFM_HANGING_MODE_ATOMIC))
+      return c ? fail(c, PFM_ERR_BAD_ARG, "unknown hanging mode") : PFM_ERR_BAD_ARG;
+    if (mode == PFM_HANGING_MODE_GATHER && c->hanging_coloured)
+      return fail(c, PFM_ERR_UNSUPPORTED, "PFM_HANGING_COLOURED=1: the cells at hanging vertices sit in the colour classes");
+    c->hang_mode = mode;
     return PFM_OK;
   }
 
@@ -1709,66 +1725,34 @@ extern "C"
   {
     if (c->hang_gather_ready)
       return true;
-    if (!c->hang_gather || !c->v.cres || c->n_hcells == 0)
+    if (c->hang_gather_failed || !c->v.cres || c->n_hcells == 0)
       return false;
     (void)hipSetDevice(c->device);
     const int64_t nh = c->n_hcells;
     pfm::raw_vector<uint8_t> rec((size_t)nh * pfm::PFM_CRES_BYTES);
     if (hipMemcpy(rec.data(), c->v.cres, rec.size(), hipMemcpyDeviceToHost) != hipSuccess)
       throw HipFail{hipGetLastError(), "cres D2H"};
-    const int32_t NO = c->v.n_owned;
-    std::vector<int32_t> cnt((size_t)NO + 1, 0);
-    std::vector<long long> off((size_t)nh + 1, 0);
-    for (int64_t hc = 0; hc < nh; ++hc)
+    const int dim = c->v.dim, kcmp = dim * dim + dim + 1; // Kuu dim x dim, Kpu dim, Kpp
+    pfm::HangGatherLists L;
+    if (!pfm::hang_gather_lists(rec.data(), nh, 1 << dim, kcmp, c->v.n_owned, L))
       {
-        const uint8_t *r = rec.data() + (size_t)hc * pfm::PFM_CRES_BYTES;
-        const int R = r[pfm::PFM_CRES_R];
-        if (R > 16)
-          {
-            c->hang_gather = false;
-            return false;
-          }
-        off[(size_t)hc + 1] = off[(size_t)hc] + (long long)R * R * 13;
-        const int32_t *node = reinterpret_cast<const int32_t *>(r), *hv = reinterpret_cast<const int32_t *>(r + pfm::PFM_CRES_HV);
-        for (int i = 0; i < R; ++i)
-          if (node[i] < NO)
-            ++cnt[(size_t)node[i]];
-        for (int a = 0; a < 8; ++a)
-          if (hv[a] >= 0 && hv[a] < NO)
-            ++cnt[(size_t)hv[a]];
+        c->hang_gather = false;
+        c->hang_gather_failed = true;
+        return false;
       }
-    std::vector<int32_t> rows, row_of((size_t)NO, -1);
-    std::vector<long long> ptr(1, 0);
-    for (int32_t n = 0; n < NO; ++n)
-      if (cnt[(size_t)n])
-        {
-          row_of[(size_t)n] = (int32_t)rows.size();
-          rows.push_back(n);
-          ptr.push_back(ptr.back() + cnt[(size_t)n]);
-        }
-    std::vector<pfm::HgEntry> list((size_t)std::max<long long>(ptr.back(), 1));
-    std::vector<long long> fill(ptr.begin(), ptr.end() - 1);
-    for (int64_t hc = 0; hc < nh; ++hc)
-      {
-        const uint8_t *r = rec.data() + (size_t)hc * pfm::PFM_CRES_BYTES;
-        const int R = r[pfm::PFM_CRES_R];
-        const int32_t *node = reinterpret_cast<const int32_t *>(r), *hv = reinterpret_cast<const int32_t *>(r + pfm::PFM_CRES_HV);
-        for (int i = 0; i < R; ++i)
-          if (node[i] < NO)
-            list[(size_t)fill[(size_t)row_of[(size_t)node[i]]]++] = pfm::HgEntry{(int32_t)(hc * 32 + i), R, off[(size_t)hc] + (long long)i * R * 13};
-        for (int a = 0; a < 8; ++a)
-          if (hv[a] >= 0 && hv[a] < NO)
-            list[(size_t)fill[(size_t)row_of[(size_t)hv[a]]]++] = pfm::HgEntry{(int32_t)(hc * 32 + 16 + a), R, 0};
-      }
-    c->n_hg_rows = (int64_t)rows.size();
-    if (rows.empty())
-      rows.push_back(0);
-    c->d_hg_rows = dev_upload(c, rows.data(), rows.size());
-    c->d_hg_ptr = dev_upload(c, ptr.data(), ptr.size());
-    c->d_hg_list = dev_upload(c, list.data(), list.size());
-    c->v.hs_off = dev_upload(c, off.data(), off.size());
-    c->v.hs_K = dev_alloc<double>(c, (size_t)std::max<long long>(off.back(), 1));
+    const int64_t bytes0 = c->device_bytes;
+    c->n_hg_rows = (int64_t)L.rows.size();
+    if (L.rows.empty())
+      L.rows.push_back(0);
+    if (L.list.empty())
+      L.list.push_back(pfm::HgEntry{0, 0, 0});
+    c->d_hg_rows = dev_upload(c, L.rows.data(), L.rows.size());
+    c->d_hg_ptr = dev_upload(c, L.ptr.data(), L.ptr.size());
+    c->d_hg_list = dev_upload(c, L.list.data(), L.list.size());
+    c->v.hs_off = dev_upload(c, L.off.data(), L.off.size());
+    c->v.hs_K = dev_alloc<double>(c, (size_t)std::max<long long>(L.off.back(), 1));
     c->v.hs_RD = dev_alloc<double>(c, (size_t)nh * pfm::PFM_HS_RD);
+    c->hang_gather_bytes = c->device_bytes - bytes0;
     c->hang_gather_ready = true;
     return true;
   }
@@ -2381,11 +2365,14 @@ extern "C"
       p.level = plan_cart(c->v, c->levels3[0].cv, c->prm, residual_only, 0, cart_n_cu(), cart_split(c));
     p.overlay3 = p.level.supported;
     p.patches = (!p.cart && c->v.dim == 2 && c->n_patch_blocks > 0 && c->kernel_path != 0 && !p.nothing) || p.overlay3;
-    // 3-D cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*) -- wanted.  A split
-    // assembly keeps it under PFM_SPLIT_VOLDEV, whose kernel is the unsplit form; the spectral instantiations have no SCR form
-    // (also where the level lattices take the spectral residual, CartPlan::spectral: the cells at hanging vertices then add with
-    // atomics and such an overlay residual is not bitwise reproducible)
-    p.gather = !p.cart && c->v.dim == 3 && c->hang_gather && (!p.split || c->split_model == PFM_SPLIT_VOLDEV) && !p.nothing;
+    // cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*) -- wanted.
+    // PFM_HANGING_MODE_DEFAULT: 3-D only, and a split assembly keeps it under PFM_SPLIT_VOLDEV alone (under the spectral law
+    // the cells at hanging vertices add with atomics, also where the level lattices take the spectral residual,
+    // CartPlan::spectral: not bitwise reproducible).  PFM_HANGING_MODE_GATHER: both dimensions, every law; _ATOMIC: never.
+    const bool gather_default = c->v.dim == 3 && c->hang_gather && (!p.split || c->split_model == PFM_SPLIT_VOLDEV);
+    const bool gather_asked = c->hang_mode == PFM_HANGING_MODE_GATHER && c->n_hcells > 0 && c->v.cres && !c->hanging_coloured;
+    p.gather = !p.cart && !p.nothing && !c->hang_gather_failed &&
+               (c->hang_mode == PFM_HANGING_MODE_DEFAULT ? gather_default : gather_asked);
     // The two Jacobian kernels of a 3-D box next to each other (default): with equal LDS allocations (64 granules of 1280 B
     // each) any freed slot of a CU takes a workgroup of either kernel, the (u,u) and the phase-field workgroups mix and
     // fill each other's stalls: 14.07 -> 13.75 ms per assembly at 216^3 (PFM_JAC_SEQUENTIAL=1: one after the other).
@@ -3139,6 +3126,34 @@ extern "C"
             *lattice_residual = ((p.cart && (p.box.voldev || p.box.spectral)) || (p.overlay3 && (p.level.voldev || p.level.spectral))) ? 1 : 0;
           }
       }
+    return PFM_OK;
+  }
+
+  int pfm_ctx_hanging_info(const pfm_ctx *c, int *mode, int64_t out[5])
+  {
+    if (!c)
+      return PFM_ERR_BAD_ARG;
+    if (mode)
+      *mode = c->hang_mode;
+    if (!out)
+      return PFM_OK;
+    out[0] = c->n_hcells;
+    out[1] = 0;
+    out[2] = c->hang_gather_ready ? c->n_hg_rows : 0;
+    out[3] = c->hang_gather_bytes;
+    out[4] = 0;
+    if (!c->have_params)
+      return PFM_OK;
+    // the plan of such an assembly and the view its classes would take, not a second copy of their conditions
+    double *const no_values[4] = {nullptr, nullptr, nullptr, nullptr};
+    const AssemblyPlan p = plan_assembly(c, 0, 0, no_values);
+    out[1] = p.gather ? 1 : 0;
+    if (p.cart || p.nothing)
+      return PFM_OK; // the row-owner kernels: every entry written once
+    // floating-point atomic adds: the atomic class (cells at hanging vertices that do not go through the gather, cells that
+    // found no colour) and the ring of the plain classes
+    const bool atomic_class = (c->n_hcells > 0 && !p.gather && !c->hanging_coloured) || c->colour_overflow;
+    out[4] = (atomic_class || general_view(c, p, true).cell_ring != nullptr) ? 1 : 0;
     return PFM_OK;
   }
 

@@ -17,13 +17,7 @@
 namespace pfm
 {
   // Device-side view of the static mesh tables and the node state (SoA, HBM resident).
-  constexpr int PFM_CRES_SLOT = 64, PFM_CRES_R = 320, PFM_CRES_HV = 336, PFM_CRES_CELL = 368, PFM_CRES_BYTES = 376;
-  struct HgEntry // one contribution to a row of the gather tables (pfm_ctx::d_hg_list)
-  {
-    int32_t code; // hc * 32 + index: index < 16 = resolved node i of cell hc, 16 + a = the row of the cell's hanging vertex a
-    int32_t R;    // resolved nodes of the cell
-    long long koff; // first double of row i of the cell's K' in DevView::hs_K
-  };
+  // (PFM_CRES_*, HgEntry: pfm_mesh_plan.h, next to the host-only builder of the gather lists)
   constexpr int PFM_HS_RD = 96; // doubles per cell of DevView::hs_RD: residual of 16 resolved nodes x 4, placeholder of 8 vertices x 4
   struct DevView
   {
@@ -47,14 +41,15 @@ namespace pfm
     // parents than that (the cell kernel then searches the row, find_slot)
     const int32_t *hcell;
     const uint8_t *cslot_h;
-    // 3-D: per such cell a record of PFM_CRES_BYTES: int32 node[16] (its distinct constraint-resolved nodes, -1 unused),
+    // per such cell (2-D and 3-D) a record of PFM_CRES_BYTES: int32 node[16] (its distinct constraint-resolved nodes, -1 unused),
     // uint8 slot[16][16] at PFM_CRES_SLOT (slot of node j in the row of node i), uint8 R at PFM_CRES_R (0xff: more than 16).
     // The cell kernel forms C^T K C over these nodes before it adds (k_assemble_general, KRED).  nullptr: no such cells.
     const uint8_t *cres;         // (round 6: + int32 hv[8] at PFM_CRES_HV, the cell's hanging vertices' nodes (-1: does not hang),
                                  // and the cell id at PFM_CRES_CELL)
-    // Round 6, the default on 3-D meshes with hanging nodes: the cells at hanging vertices do not add into the outputs at all.
-    // Their kernel writes K' = C^T K C, R' = C^T R and the placeholder diagonals into per-cell scratch (hs_K at hs_off[hc]:
-    // R x R x 13 doubles; hs_RD: PFM_HS_RD doubles per cell), and k_hanging_gather adds them row by row in a fixed order
+    // Round 6, the default on 3-D meshes with hanging nodes (everywhere under PFM_HANGING_MODE_GATHER): the cells at hanging
+    // vertices do not add into the outputs at all.  Their kernel writes K' = C^T K C, R' = C^T R and the placeholder diagonals
+    // into per-cell scratch (hs_K at hs_off[hc]: R x R x KCMP doubles, KCMP = 13 in 3-D and 7 in 2-D; hs_RD: PFM_HS_RD doubles
+    // per cell, the same strides in both dimensions), and k_hanging_gather adds them row by row in a fixed order
     // (pfm_ctx::d_hg_*): no atomics, no colour classes, bitwise reproducible.  nullptr: the atomic class of round 5.
     double *hs_K;
     const long long *hs_off;
@@ -376,7 +371,10 @@ struct pfm_ctx
   pfm::HgEntry *d_hg_list = nullptr;
   int64_t n_hg_rows = 0;
   int64_t n_hcells = 0;           // cells at hanging vertices (records of DevView::cres)
-  bool hang_gather = false;       // decided at pfm_ctx_create (PFM_HANGING_ATOMIC=1: off)
+  bool hang_gather = false;       // PFM_HANGING_MODE_DEFAULT, 3-D: decided at pfm_ctx_create (PFM_HANGING_ATOMIC=1: off)
+  int hang_mode = 0;              // PFM_HANGING_MODE_*: pfm_set_hanging_mode
+  bool hang_gather_failed = false; // a cell with more than 16 resolved nodes: the context keeps its atomic class in every mode
+  int64_t hang_gather_bytes = 0;  // device bytes of the gather tables and the scratch (counted in device_bytes)
   bool hang_gather_ready = false; // tables and scratch exist
   bool colour_overflow = false;   // cells without a hanging vertex sit in the last class (a node of more than 62 cells)
   pfm::DevBuf buf_norm_partial; // pfm_residual_norms: [2048][2] block partials + the 3 results; pfm_line_search_device: [2048][3] + 5

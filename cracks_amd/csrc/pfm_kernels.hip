@@ -212,7 +212,7 @@ namespace pfm
     // the unsplit one: two loop invariants spill (20 bytes of scratch, one reload per round of 8 q-points); bound to one
     // workgroup per CU nothing spills and the kernel is 50 % slower (profiles/split_voldev/README.md).
     template <int dim, bool FULL, bool SPLIT, bool ATOMIC, bool RING = false /* DevView::cell_ring is set */, bool PATCH_OR_VOLDEV = false,
-              bool SCR = false /* 3-D cells at hanging vertices: reduced matrix / residual into DevView::hs_* instead of the outputs */>
+              bool SCR = false /* cells at hanging vertices: reduced matrix / residual into DevView::hs_* instead of the outputs */>
     __global__ __launch_bounds__(256, (dim == 3 && FULL && !SPLIT) ? 2 : 1) void k_assemble_general(DevView v, pfm_params prm, Vals vals,
                                                               double *res_pde, double *res_tot,
                                                               int residual_only, long long class_begin, long long class_size)
@@ -241,9 +241,12 @@ namespace pfm
       constexpr int KCMP = 13;                      // Kuu 3 x 3, Kpu 3, Kpp
       constexpr int KCELL = KRED ? (nv * nv * KCMP > NSLOT * QST ? nv * nv * KCMP : NSLOT * QST) : NSLOT * QST; // doubles per cell of s_q
       static_assert(NSLOT * QST <= KCELL, "the exchange slots of a hex are the head of its KCELL region");
-      __shared__ __attribute__((aligned(16))) double s_q[dim == 3 ? (KRED ? CPB * KCELL : NSLOT * CPB * QST) : 2];
+      // 2-D SCR: per quad the weights of its 4 vertices in its (at most 16) resolved nodes and, FULL, its 4 x 4 x 7 matrix
+      constexpr bool SCR2 = dim == 2 && SCR;
+      constexpr int KCMP2 = 7, K2W = 16 * nv, K2CELL = K2W + (FULL ? nv * nv * KCMP2 : 0);
+      __shared__ __attribute__((aligned(16))) double s_q[dim == 3 ? (KRED ? CPB * KCELL : NSLOT * CPB * QST) : (SCR2 ? CPB * K2CELL : 2)];
       auto sq_at = [&](int slot, int cell_in_wg) { return KRED ? cell_in_wg * KCELL + slot * QST : (slot * CPB + cell_in_wg) * QST; };
-      __shared__ double s_rr[(dim == 3 && !PATCH) ? CPB : 1][nv][nc]; // residual entries of a cell at hanging vertices, by vertex
+      __shared__ double s_rr[((dim == 3 && !PATCH) || SCR2) ? CPB : 1][nv][nc]; // residual entries of a cell at hanging vertices, by vertex
       __shared__ uint8_t s_icnt[KRED ? CPB : 1][16], s_ia[KRED ? CPB : 1][16][8];
       __shared__ double s_iw[KRED ? CPB : 1][16][8];
 
@@ -1488,7 +1491,7 @@ namespace pfm
       // (pfm_mesh_plan.cpp: greedy_colours over the resolved nodes): plain read-modify-write in a fixed order, bitwise reproducible.
       const uint8_t *rec = nullptr;
       int RN = 0xff;
-      if constexpr (dim == 3 && !PATCH)
+      if constexpr ((dim == 3 && !PATCH) || SCR2)
         if (v.cres)
           {
             const int hc3 = v.hcell[cell];
@@ -1499,6 +1502,134 @@ namespace pfm
               }
           }
       const bool red = RN <= 16;
+      // 2-D quad at a hanging vertex, scratch form: its four lanes (one wave) stage R and K by vertex in LDS, lane a the weights
+      // of vertex a in the resolved nodes; then lane l takes the resolved nodes l, l + 4, ... (R' = C^T R) and the node pairs
+      // l, l + 4, ... (K' = C^T K C, 7 values: Kuu 2 x 2, Kpu 2, Kpp), each sum over the vertices in ascending order.
+      // Everything goes to the scratch unmasked; k_hanging_gather applies the flags and adds in list order.
+      if constexpr (SCR2)
+        if (red)
+          {
+            const int hcq = v.hcell[cell];
+            const int32_t *rnode = reinterpret_cast<const int32_t *>(rec);
+            double *const Wc = s_q + cl * K2CELL, *const Kc = Wc + K2W;
+#pragma unroll
+            for (int c = 0; c < nc; ++c)
+              s_rr[cl][a][c] = R[c];
+            if constexpr (FULL)
+              {
+#pragma unroll
+                for (int b = 0; b < nv; ++b)
+                  {
+                    double *o = Kc + (a * nv + b) * KCMP2;
+#pragma unroll
+                    for (int c = 0; c < 2; ++c)
+#pragma unroll
+                      for (int d = 0; d < 2; ++d)
+                        o[2 * c + d] = Kuu[b][c][d];
+                    o[4] = Kpu[b][0];
+                    o[5] = Kpu[b][1];
+                    o[6] = Kpp[b];
+                  }
+              }
+            {
+              const int kA2 = v.hn_index[A];
+              for (int i = 0; i < RN; ++i)
+                {
+                  const int P = rnode[i];
+                  double w = 0.0;
+                  if (kA2 < 0)
+                    w = A == P ? 1.0 : 0.0;
+                  else
+                    for (long long r = v.hn_ptr[kA2]; r < v.hn_ptr[kA2 + 1]; ++r)
+                      if (v.hn_parents[r] == P)
+                        w += v.hn_weights[r];
+                  Wc[i * nv + a] = w;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int i = a; i < RN; i += nv)
+              {
+                const int P = rnode[i];
+                if (P >= v.n_owned || (v.row_patch && v.row_patch[P]))
+                  continue;
+                double acc[nc];
+#pragma unroll
+                for (int c = 0; c < nc; ++c)
+                  acc[c] = 0.0;
+                for (int x = 0; x < nv; ++x)
+                  {
+                    const double w = Wc[i * nv + x];
+                    if (w == 0.0)
+                      continue;
+#pragma unroll
+                    for (int c = 0; c < nc; ++c)
+                      acc[c] = fma(w, s_rr[cl][x][c], acc[c]);
+                  }
+                double *o = v.hs_RD + (long long)hcq * PFM_HS_RD + i * 4;
+#pragma unroll
+                for (int c = 0; c < nc; ++c)
+                  o[c] = acc[c];
+              }
+            if constexpr (FULL)
+              {
+                for (int pq = a; pq < RN * RN; pq += nv)
+                  {
+                    const int i = pq / RN, j = pq - i * RN;
+                    const int P = rnode[i];
+                    if (P >= v.n_owned || (v.row_patch && v.row_patch[P]) || rec[PFM_CRES_SLOT + 16 * i + j] == 0xff)
+                      continue;
+                    double acc[KCMP2];
+#pragma unroll
+                    for (int t = 0; t < KCMP2; ++t)
+                      acc[t] = 0.0;
+                    for (int x = 0; x < nv; ++x)
+                      {
+                        const double wi = Wc[i * nv + x];
+                        if (wi == 0.0)
+                          continue;
+                        for (int y = 0; y < nv; ++y)
+                          {
+                            const double wj = Wc[j * nv + y];
+                            if (wj == 0.0)
+                              continue;
+                            const double w = wi * wj;
+                            const double *k = Kc + (x * nv + y) * KCMP2;
+#pragma unroll
+                            for (int t = 0; t < KCMP2; ++t)
+                              acc[t] = fma(w, k[t], acc[t]);
+                          }
+                      }
+                    double *o = v.hs_K + v.hs_off[hcq] + (long long)pq * KCMP2;
+#pragma unroll
+                    for (int t = 0; t < KCMP2; ++t)
+                      o[t] = acc[t];
+                  }
+                // placeholder diagonal of vertex a: |K_ii| or, when that is zero, the mean |diagonal| of the element matrix
+                double dg[nc] = {0.0, 0.0, 0.0}, dsum = 0.0;
+#pragma unroll
+                for (int b = 0; b < nv; ++b)
+                  if (b == a)
+                    {
+                      dg[0] = fabs(Kuu[b][0][0]);
+                      dg[1] = fabs(Kuu[b][1][1]);
+                      dg[2] = fabs(Kpp[b]);
+                    }
+#pragma unroll
+                for (int c = 0; c < nc; ++c)
+                  dsum += dg[c];
+#pragma unroll
+                for (int m = 1; m < LPC; m <<= 1)
+                  dsum += __shfl_xor(dsum, m, LPC);
+                const double avg = dsum / (double)dpc;
+                double *o = v.hs_RD + (long long)hcq * PFM_HS_RD + 64 + a * 4;
+#pragma unroll
+                for (int c = 0; c < nc; ++c)
+                  o[c] = dg[c] != 0.0 ? dg[c] : avg;
+              }
+            return;
+          }
       if (!ATOMIC && !red)
         {
           // Colour class without hanging vertices: the rows of node A are touched by this thread only during this
@@ -1965,14 +2096,16 @@ namespace pfm
     // placeholder diagonal of a constrained vertex (deal.II distribute_local_to_global) and the residual entries.
     // Rows of more than HG_DEG neighbours (none on 2:1 meshes of hexes; tests/test_gpu_topology.py: fan3d_30_hanging) take the
     // entries one by one with plain read-modify-writes of the outputs (same order).
+    // dim = 2 (PFM_HANGING_MODE_GATHER): the same kernel with 7 values per node pair (Kuu 2 x 2, Kpu 2, Kpp) and 3 residual
+    // entries; the strides of DevView::hs_RD and the entry codes are those of 3-D.  Rows of the patch overlay are skipped.
     constexpr int HG_DEG = 64;
-    template <bool FULL>
+    template <int dim, bool FULL>
     __global__ __launch_bounds__(256) void k_hanging_gather(DevView v, pfm_params prm, Vals vals, double *__restrict__ res_pde,
                                                             double *__restrict__ res_tot, int residual_only,
                                                             const int32_t *__restrict__ rows, const long long *__restrict__ ptr,
                                                             const HgEntry *__restrict__ list, long long n_rows)
     {
-      constexpr int dim = 3, nc = 4, KCMP = 13;
+      constexpr int nv = 1 << dim, nc = dim + 1, KCMP = dim * dim + dim + 1; // 2-D: 7 values per node pair, 3-D: 13
       __shared__ double s_acc[4][FULL ? HG_DEG * KCMP : 1];
       __shared__ double s_res[4][nc];
       const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
@@ -2001,7 +2134,7 @@ namespace pfm
           acc[slot * KCMP + t] += x;
         else
           {
-            const int c = t < 9 ? t / 3 : 3, d = t < 9 ? t - 3 * c : t - 9;
+            const int c = t < dim * dim ? t / dim : dim, d = t < dim * dim ? t - dim * c : t - dim * dim;
             *val_ptr<dim>(v, vals, P, c, slot, d) += x;
           }
       };
@@ -2030,7 +2163,7 @@ namespace pfm
                 kv[t] = src[t];
             }
           // lane 15 of the group: residual entries of resolved node idx; placeholder diagonal of the vertex that IS node P
-          double rv[nc] = {0.0, 0.0, 0.0, 0.0}, dv[nc] = {0.0, 0.0, 0.0, 0.0};
+          double rv[nc] = {}, dv[nc] = {};
           int dslot = 0xff;
           unsigned dmask = 0;
           if (have && j == 15)
@@ -2046,13 +2179,13 @@ namespace pfm
                   const int cell = *reinterpret_cast<const int32_t *>(rec + PFM_CRES_CELL);
                   int a = idx >= 16 ? idx - 16 : -1;
                   if (a < 0)
-                    for (int a2 = 0; a2 < 8; ++a2)
+                    for (int a2 = 0; a2 < nv; ++a2)
                       if (v.conn[(long long)a2 * v.n_cells + cell] == P)
                         a = a2;
                   if (a >= 0)
                     {
-                      dslot = (int)v.cslot[(long long)cell * 64 + a * 8 + a];
-                      dmask = idx >= 16 ? 0xfu : fP; // the row of a hanging vertex: every component
+                      dslot = (int)v.cslot[(long long)cell * (nv * nv) + a * nv + a];
+                      dmask = idx >= 16 ? (1u << nc) - 1u : fP; // the row of a hanging vertex: every component
 #pragma unroll
                       for (int c = 0; c < nc; ++c)
                         dv[c] = RD[64 + a * 4 + c];
@@ -2068,22 +2201,22 @@ namespace pfm
                   if (pair && slot != 0xff)
                     {
 #pragma unroll
-                      for (int c = 0; c < 3; ++c)
+                      for (int c = 0; c < dim; ++c)
                         if (!((fP >> c) & 1u))
                           {
 #pragma unroll
-                            for (int d = 0; d < 3; ++d)
+                            for (int d = 0; d < dim; ++d)
                               if (!((fQ >> d) & 1u))
-                                add_value(slot, 3 * c + d, kv[3 * c + d]);
+                                add_value(slot, dim * c + d, kv[dim * c + d]);
                           }
-                      if (!((fP >> 3) & 1u))
+                      if (!((fP >> dim) & 1u))
                         {
 #pragma unroll
-                          for (int d = 0; d < 3; ++d)
+                          for (int d = 0; d < dim; ++d)
                             if (!((fQ >> d) & 1u))
-                              add_value(slot, 9 + d, kv[9 + d]);
-                          if (!((fQ >> 3) & 1u))
-                            add_value(slot, 12, kv[12]);
+                              add_value(slot, dim * dim + d, kv[dim * dim + d]);
+                          if (!((fQ >> dim) & 1u))
+                            add_value(slot, KCMP - 1, kv[KCMP - 1]);
                         }
                     }
                   if (have && j == 15)
@@ -2106,7 +2239,7 @@ namespace pfm
 #pragma unroll
                   for (int c = 0; c < nc; ++c)
                     if ((dmask >> c) & 1u)
-                      add_value(dslot, c < 3 ? 4 * c : 12, dv[c]);
+                      add_value(dslot, c < dim ? (dim + 1) * c : KCMP - 1, dv[c]);
                 }
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
               __builtin_amdgcn_wave_barrier();
@@ -2118,7 +2251,7 @@ namespace pfm
         for (int n = lane; n < deg * KCMP; n += 64)
           {
             const int slot = n / KCMP, t = n - slot * KCMP;
-            const int c = t < 9 ? t / 3 : 3, d = t < 9 ? t - 3 * c : t - 9;
+            const int c = t < dim * dim ? t / dim : dim, d = t < dim * dim ? t - dim * c : t - dim * dim;
             const double x = acc[n];
             if (x != 0.0)
               *val_ptr<dim>(v, vals, P, c, slot, d) += x;
@@ -2307,9 +2440,10 @@ namespace pfm
         }
     }
 
-    // DevView::cres, one record per 3-D cell at a hanging vertex: the distinct constraint-resolved nodes of the cell (a vertex
+    // DevView::cres, one record per cell at a hanging vertex (nv = 4: quads, R <= 16 by construction; nv = 8: hexes): the distinct constraint-resolved nodes of the cell (a vertex
     // that does not hang is its own, a hanging one brings its parents), their number R (0xff: more than 16), and slot[i][j] =
     // position of node j in the row of node i (0xff: row not owned / not in the row).  16 threads per cell: thread i fills row i.
+    template <int nv>
     __global__ void k_build_cres(DevView v, uint8_t *__restrict__ cres)
     {
       const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2321,7 +2455,7 @@ namespace pfm
         return;
       int node[16], R = 0;
       bool over = false;
-      for (int a = 0; a < 8; ++a)
+      for (int a = 0; a < nv; ++a)
         {
           const int A = v.conn[(long long)a * v.n_cells + cell];
           const int kA = v.hn_index[A];
@@ -2348,8 +2482,8 @@ namespace pfm
           rec[PFM_CRES_R] = over ? (uint8_t)0xff : (uint8_t)R;
           for (int a = 0; a < 8; ++a)
             {
-              const int A = v.conn[(long long)a * v.n_cells + cell];
-              reinterpret_cast<int32_t *>(rec + PFM_CRES_HV)[a] = v.hn_index[A] >= 0 ? A : -1;
+              const int A = a < nv ? v.conn[(long long)a * v.n_cells + cell] : -1; // (a quad: slots 4..7 stay empty)
+              reinterpret_cast<int32_t *>(rec + PFM_CRES_HV)[a] = (A >= 0 && v.hn_index[A] >= 0) ? A : -1;
             }
           *reinterpret_cast<int32_t *>(rec + PFM_CRES_CELL) = (int32_t)cell;
         }
@@ -2498,8 +2632,10 @@ namespace pfm
         else
           hipLaunchKernelGGL(k_build_cslot_h<3>, dim3(nbh), dim3(bs), 0, s, v, const_cast<uint8_t *>(v.cslot_h));
       }
-    if (v.cres && v.dim == 3)
-      hipLaunchKernelGGL(k_build_cres, dim3((unsigned)((v.n_cells * 16 + bs - 1) / bs)), dim3(bs), 0, s, v, const_cast<uint8_t *>(v.cres));
+    if (v.cres && v.dim == 2)
+      hipLaunchKernelGGL(k_build_cres<4>, dim3((unsigned)((v.n_cells * 16 + bs - 1) / bs)), dim3(bs), 0, s, v, const_cast<uint8_t *>(v.cres));
+    else if (v.cres)
+      hipLaunchKernelGGL(k_build_cres<8>, dim3((unsigned)((v.n_cells * 16 + bs - 1) / bs)), dim3(bs), 0, s, v, const_cast<uint8_t *>(v.cres));
     return check_launch();
   }
 
@@ -2514,9 +2650,16 @@ namespace pfm
         vals.b[b] = d_values[b];
     const dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
     if (residual_only)
-      hipLaunchKernelGGL(k_hanging_gather<false>, grid, block, 0, s, v, p, vals, d_res_pde, d_res_tot, residual_only, rows, ptr, list, (long long)n_rows);
+      {
+        if (v.dim == 2)
+          hipLaunchKernelGGL((k_hanging_gather<2, false>), grid, block, 0, s, v, p, vals, d_res_pde, d_res_tot, residual_only, rows, ptr, list, (long long)n_rows);
+        else
+          hipLaunchKernelGGL((k_hanging_gather<3, false>), grid, block, 0, s, v, p, vals, d_res_pde, d_res_tot, residual_only, rows, ptr, list, (long long)n_rows);
+      }
+    else if (v.dim == 2)
+      hipLaunchKernelGGL((k_hanging_gather<2, true>), grid, block, 0, s, v, p, vals, d_res_pde, d_res_tot, residual_only, rows, ptr, list, (long long)n_rows);
     else
-      hipLaunchKernelGGL(k_hanging_gather<true>, grid, block, 0, s, v, p, vals, d_res_pde, d_res_tot, residual_only, rows, ptr, list, (long long)n_rows);
+      hipLaunchKernelGGL((k_hanging_gather<3, true>), grid, block, 0, s, v, p, vals, d_res_pde, d_res_tot, residual_only, rows, ptr, list, (long long)n_rows);
     return check_launch();
   }
 
@@ -2733,8 +2876,8 @@ namespace pfm
 #define PFM_LAUNCH(DIM, FULLV, SPLITV)                                                                                       \
   do                                                                                                                         \
     {                                                                                                                        \
-      if (atomic && DIM == 3 && !(SPLITV) && v.hs_K)                                                                         \
-        hipLaunchKernelGGL((k_assemble_general<DIM, FULLV, false, true, false, false, DIM == 3>), grid, block, 0, s, v, p,    \
+      if (atomic && v.hs_K)                                                                                                  \
+        hipLaunchKernelGGL((k_assemble_general<DIM, FULLV, SPLITV, true, false, false, true>), grid, block, 0, s, v, p,      \
                            vals, res_pde, res_tot, residual_only, c0, cn);                                                   \
       else if (atomic)                                                                                                       \
         hipLaunchKernelGGL((k_assemble_general<DIM, FULLV, SPLITV, true>), grid, block, 0, s, v, p, vals, res_pde, res_tot,  \

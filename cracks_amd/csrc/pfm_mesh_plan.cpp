@@ -1009,4 +1009,52 @@ namespace pfm
     });
     sort_by_class(col.data(), NC, (dim == 3 ? 8 : 4) + 1, full); // (the last class, of the cells that add atomically, is empty)
   }
+
+  bool hang_gather_lists(const uint8_t *records, int64_t nh, int nv, int kcmp, int32_t n_owned, HangGatherLists &out)
+  {
+    out = HangGatherLists{};
+    const int32_t NO = n_owned;
+    std::vector<int32_t> cnt((size_t)NO + 1, 0);
+    std::vector<long long> off((size_t)nh + 1, 0);
+    for (int64_t hc = 0; hc < nh; ++hc)
+      {
+        const uint8_t *r = records + (size_t)hc * PFM_CRES_BYTES;
+        const int R = r[PFM_CRES_R];
+        if (R > 16)
+          return false;
+        off[(size_t)hc + 1] = off[(size_t)hc] + (long long)R * R * kcmp;
+        const int32_t *node = reinterpret_cast<const int32_t *>(r), *hv = reinterpret_cast<const int32_t *>(r + PFM_CRES_HV);
+        for (int i = 0; i < R; ++i)
+          if (node[i] >= 0 && node[i] < NO)
+            ++cnt[(size_t)node[i]];
+        for (int a = 0; a < nv; ++a)
+          if (hv[a] >= 0 && hv[a] < NO)
+            ++cnt[(size_t)hv[a]];
+      }
+    std::vector<int32_t> row_of((size_t)NO, -1);
+    out.ptr.assign(1, 0);
+    for (int32_t n = 0; n < NO; ++n)
+      if (cnt[(size_t)n])
+        {
+          row_of[(size_t)n] = (int32_t)out.rows.size();
+          out.rows.push_back(n);
+          out.ptr.push_back(out.ptr.back() + cnt[(size_t)n]);
+        }
+    out.list.resize((size_t)out.ptr.back());
+    std::vector<long long> fill(out.ptr.begin(), out.ptr.end() - 1);
+    for (int64_t hc = 0; hc < nh; ++hc)
+      {
+        const uint8_t *r = records + (size_t)hc * PFM_CRES_BYTES;
+        const int R = r[PFM_CRES_R];
+        const int32_t *node = reinterpret_cast<const int32_t *>(r), *hv = reinterpret_cast<const int32_t *>(r + PFM_CRES_HV);
+        for (int i = 0; i < R; ++i)
+          if (node[i] >= 0 && node[i] < NO)
+            out.list[(size_t)fill[(size_t)row_of[(size_t)node[i]]]++] = HgEntry{(int32_t)(hc * 32 + i), R, off[(size_t)hc] + (long long)i * R * kcmp};
+        for (int a = 0; a < nv; ++a)
+          if (hv[a] >= 0 && hv[a] < NO)
+            out.list[(size_t)fill[(size_t)row_of[(size_t)hv[a]]]++] = HgEntry{(int32_t)(hc * 32 + 16 + a), R, 0};
+      }
+    out.off.swap(off);
+    return true;
+  }
 } // namespace pfm

@@ -102,6 +102,27 @@ namespace pfm
   // DevView::cslot_h.  false -- nothing filled -- when a node hangs on more than max_parents parents or no cell is at one.
   bool hanging_cells(const pfm_mesh_desc *m, const int32_t *hn_index, int max_parents, std::vector<int32_t> &hcells, raw_vector<int32_t> &hcell);
 
+  // ---- ordered gather of the cells at hanging vertices (DevView::cres, DevView::hs_*, k_hanging_gather) --------------------
+  // record of one such cell, built on the device (k_build_cres): int32 node[16], uint8 slot[16][16], uint8 R, int32 hv[8], int32 cell
+  constexpr int PFM_CRES_SLOT = 64, PFM_CRES_R = 320, PFM_CRES_HV = 336, PFM_CRES_CELL = 368, PFM_CRES_BYTES = 376;
+  struct HgEntry // one contribution to a row of the gather tables (pfm_ctx::d_hg_list)
+  {
+    int32_t code; // hc * 32 + index: index < 16 = resolved node i of cell hc, 16 + a = the row of the cell's hanging vertex a
+    int32_t R;    // resolved nodes of the cell
+    long long koff; // first double of row i of the cell's K' in DevView::hs_K
+  };
+  // The lists the gather runs over, from nh records: every (cell, owned resolved node) and (cell, owned hanging vertex) pair
+  // under its destination row -- rows ascending, the entries of a row in ascending (cell, index) order, the order the adds take
+  // -- and off[hc], the first double of cell hc's K' (R x R x kcmp each; kcmp = 7 for quads, nv = 4, and 13 for hexes, nv = 8).
+  // Nodes >= n_owned (ghosts) are never listed.  false -- `out` is left empty -- when a record has more than 16 resolved nodes.
+  struct HangGatherLists
+  {
+    std::vector<int32_t> rows;
+    std::vector<long long> ptr, off;
+    std::vector<HgEntry> list;
+  };
+  bool hang_gather_lists(const uint8_t *records, int64_t nh, int nv, int kcmp, int32_t n_owned, HangGatherLists &out);
+
   // ---- cartesian overlay of a general 2-D mesh (DevView::row_patch ..., pfm_kernels.hip: PATCH) -------------------------
   // Every cell that is an axis-parallel rectangle belongs to the lattice of its size (a refinement level); a node is REGULAR
   // when it is owned, neither hanging nor a parent, has exactly four incident cells, all of one level, and none of the nine

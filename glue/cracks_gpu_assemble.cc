@@ -147,6 +147,10 @@ namespace pfm_glue_detail
     //                      split_model).  The Jacobian call's residual_pde still comes from the general family: the two
     //                      agree to rounding, not bit for bit.  Default PFM_SPLIT_ROUTE_GENERAL: nothing changes.
     //                      PFM_SPLIT_ROUTE_LATTICE_ANY does the same under PFM_SPLIT_SPECTRAL as well.
+    //   hanging_mode:      PFM_HANGING_MODE_GATHER sends the cells at hanging vertices through per-cell scratch and an ordered
+    //                      gather instead of atomic adds, in 2-D and under every 3-D law: two assemble() calls of the same state
+    //                      then give the same bytes (pfm_set_hanging_mode; forwarded next to split_route).  Default
+    //                      PFM_HANGING_MODE_DEFAULT: nothing changes.  PFM_HANGING_MODE_ATOMIC: the atomic class everywhere.
     //   line_search_stepwise: line_search() runs the host loop of a rank with ghost peers (vector statements, scatter + halo +
     //                      assembly, pfm_residual_norms, MPI sum / max) also where pfm_line_search_device would do: the two
     //                      forms give the same vectors and the same result (tests/test_gpu_glue_line_search.py).
@@ -159,6 +163,7 @@ namespace pfm_glue_detail
     bool delta_values = false;
     int split_model = PFM_SPLIT_REFERENCE;
     int split_route = PFM_SPLIT_ROUTE_GENERAL;
+    int hanging_mode = PFM_HANGING_MODE_DEFAULT;
     bool residual_to_host = true;
     bool holds_host_pins = false;
     int64_t delta_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // of the last assemble() with delta_values (pfm_values_to_host_delta)
@@ -675,6 +680,7 @@ namespace pfm_glue_detail
       p.use_old_timestep_pf = P.use_old_timestep_pf ? 1 : 0;
       PFM_CALL(ctx, pfm_set_split_model(ctx, split_model));
       PFM_CALL(ctx, pfm_set_split_route(ctx, split_route));
+      PFM_CALL(ctx, pfm_set_hanging_mode(ctx, hanging_mode));
       PFM_CALL(ctx, pfm_set_params(ctx, &p));
 
       // constraints_update minus the hanging-node lines: one flag byte per local node (cracks.cc:2442-2463)

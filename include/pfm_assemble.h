@@ -116,8 +116,9 @@ int pfm_set_params(pfm_ctx *ctx, const pfm_params *prm);
  *                        cracks_amd/split3d.py: voldev_split): sigma+ = K max(tr E, 0) I + 2 mu dev E, sigma- = K min(tr E, 0) I,
  *                        K = lambda + 2 mu / 3.  No eigen-solve, an isotropic tangent per q-point; never
  *                        PFM_ERR_NOT_ORTHOGONAL.  Routed like model 1.  Unlike model 1, the cells at hanging vertices keep
- *                        the scratch + ordered gather, so a model-3 assembly is bitwise reproducible run to run
- *                        (PFM_HANGING_ATOMIC=1: the atomic class).  The tangent is discontinuous at tr E = 0 (h(0) = 1, zero
+ *                        the scratch + ordered gather by default, so a model-3 assembly is bitwise reproducible run to run
+ *                        (PFM_HANGING_ATOMIC=1: the atomic class; model 1 is under PFM_HANGING_MODE_GATHER, see
+ *                        pfm_set_hanging_mode).  The tangent is discontinuous at tr E = 0 (h(0) = 1, zero
  *                        counts as tension) and follows the sign of the trace the device computes: where tr E is zero up to
  *                        rounding (a pure shear on a general mesh) that sign, and with it the matrix, is not determined.
  * Model 1 or 3 on a 2-D context: PFM_ERR_UNSUPPORTED (2-D keeps the reference's closed form).  An unknown model:
@@ -146,10 +147,10 @@ int pfm_set_split_model(pfm_ctx *ctx, int model);
  *                            PFM_SPLIT_VOLDEV it is PFM_SPLIT_ROUTE_LATTICE, bit for bit.  Under PFM_SPLIT_SPECTRAL the eigen
  *                            split runs at the q-points of k_cart_residual3<false, false, true> (split_strain<false> and
  *                            split_stress3 of pfm_split3.h, the statements of the general family), on the same lattices and
- *                            halves.  On a 3-D overlay the cells at hanging vertices stay with the general family, whose
- *                            spectral instantiations have no scratch + gather form and add with atomics: such a residual
- *                            is equal to the general route's to rounding but NOT bitwise reproducible run to run (a box or
- *                            a partitioned sub-box is).  With model 0 it is accepted and has no effect.  The value 2 alone
+ *                            halves.  On a 3-D overlay the cells at hanging vertices stay with the general family, which
+ *                            by default adds them with atomics under this law: such a residual is equal to the general
+ *                            route's to rounding and bitwise reproducible run to run only under PFM_HANGING_MODE_GATHER
+ *                            (pfm_set_hanging_mode; a box or a partitioned sub-box always is).  With model 0 it is accepted and has no effect.  The value 2 alone
  *                            is unassigned and stays refused.
  * May be called at any time on a living context: the next assembly follows it.  An unknown route: PFM_ERR_BAD_ARG.
  * PFM_SPLIT_ROUTE_LATTICE or _ANY on a 2-D context: PFM_ERR_UNSUPPORTED.  PFM_SPLIT_ROUTE_LATTICE with model 0 or 1 is
@@ -165,6 +166,38 @@ enum
 };
 int pfm_set_split_route(pfm_ctx *ctx, int route);
 int pfm_ctx_split_route(const pfm_ctx *ctx, int *route, int *lattice_residual);
+/* How the cells at hanging vertices of a general mesh (2-D or 3-D, with or without a cartesian overlay) reach the outputs.
+ *   PFM_HANGING_MODE_DEFAULT  what every context did before this call existed, bit for bit: 3-D unsplit and model 3 write
+ *                             K' = C^T K C, R' = C^T R and their placeholder diagonals to per-cell scratch, and an ordered
+ *                             gather adds them row by row in list order (no FP64 atomics, bitwise reproducible); 3-D model 1
+ *                             and every 2-D mesh run them as a last class with atomic adds, the cells of the plain classes
+ *                             that share a node with them as well.  PFM_HANGING_ATOMIC=1 and PFM_HANGING_COLOURED=1 at
+ *                             context creation are honoured as before.
+ *   PFM_HANGING_MODE_GATHER   scratch + ordered gather wherever a form exists: 2-D (Jacobian and residual-only, split and
+ *                             unsplit, both layouts, with and without the patch overlay) and 3-D under every law, the
+ *                             spectral one and its route-3 overlay residual included.  The plain classes then run without
+ *                             atomics.  Such an assembly is bitwise reproducible run to run and context to context.
+ *   PFM_HANGING_MODE_ATOMIC   the atomic class everywhere: what PFM_HANGING_ATOMIC=1 selects at creation, settable on a
+ *                             living context for A/B runs.
+ * May be called at any time on a living context: the next assembly follows it.  An unknown mode: PFM_ERR_BAD_ARG (the mode
+ * stays).  PFM_HANGING_MODE_GATHER on a context created under PFM_HANGING_COLOURED=1: PFM_ERR_UNSUPPORTED.  On a context
+ * without hanging nodes every mode is accepted and has no effect.  Silent fallbacks, as in 3-D before: a cell with more than
+ * 16 constraint-resolved nodes makes the context keep its atomic class in every mode (a quad has at most 16 by
+ * construction); after a colour overflow (a node of more than 62 cells) the plain classes keep their atomic adds.
+ * pfm_ctx_hanging_info reports what actually happens: *mode the mode set; out[0] the number of cells at hanging vertices;
+ * out[1] 1 if the next assembly with the current parameters, model, route and forced path sends them through the gather;
+ * out[2] the rows of the gather tables (0 until the first such assembly builds them); out[3] the device bytes held for the
+ * tables and the scratch (counted in pfm_ctx_device_bytes); out[4] 1 if that assembly would issue any floating-point atomic
+ * add (atomic class, ring cells, colour overflow) -- the bitwise promise holds exactly when it is 0.  out[1] and out[4] are
+ * 0 before pfm_set_params; either pointer may be null. */
+enum
+{
+  PFM_HANGING_MODE_DEFAULT = 0,
+  PFM_HANGING_MODE_GATHER = 1,
+  PFM_HANGING_MODE_ATOMIC = 2
+};
+int pfm_set_hanging_mode(pfm_ctx *ctx, int mode);
+int pfm_ctx_hanging_info(const pfm_ctx *ctx, int *mode, int64_t out[5]);
 /* constraints_update minus the hanging nodes: one byte per local node, bit c set <=> dof
  * (node, c) has a homogeneous line (Dirichlet from set_newton_bc cracks.cc:2711-2714, or
  * active set cracks.cc:2878-2879).  Call whenever constraints_update is rebuilt. */
