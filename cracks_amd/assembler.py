@@ -122,7 +122,10 @@ class Context:
         """Which kernels take the residual-only assembly of a 3-D context under a split law (capi.SPLIT_ROUTE_*): 0 the
         general family over all cells (default), 1 the row-owner residual kernel of the box, the sub-box or the level lattices
         with the law at its q-points under model 3 (no effect on model 1), 3 the same kernel under model 3 and under model 1,
-        the spectral law.  At any time on a living context; no effect on full assemblies."""
+        the spectral law.  5 (= 1 | 4) and 7 (= 3 | 4): the same residual-only calls, and under model 3 the full assembly of a
+        box or a partitioned sub-box on the row-owner kernels as well (k_cart_split3_jac; not on the level lattices of an overlay,
+        not under model 1); 4 and 6 are refused.  At any time on a living context; routes 0, 1 and 3 have no effect on full
+        assemblies."""
         self._check(self.lib.pfm_set_split_route(self._h, int(route)), "pfm_set_split_route")
         self.split_route = int(route)
 
@@ -132,6 +135,14 @@ class Context:
         a, b = C.c_int32(-1), C.c_int32(-1)
         self._check(self.lib.pfm_ctx_split_route(self._h, C.byref(a), C.byref(b)), "pfm_ctx_split_route")
         return int(a.value), int(b.value)
+
+    def split_route_plan(self):
+        """(route set, whether the residual-only assembly would run its law on the row-owner kernels, whether the full
+        assembly would, cells with a compressed q-point counted by the last full assembly on those kernels or -1):
+        pfm_ctx_split_route_info, answered from the assembly plan.  split_route_info() keeps its two answers."""
+        out = (C.c_int64 * 4)(-1, -1, -1, -1)
+        self._check(self.lib.pfm_ctx_split_route_info(self._h, out), "pfm_ctx_split_route_info")
+        return tuple(int(x) for x in out)
 
     def set_hanging_mode(self, mode: int):
         """How the cells at hanging vertices reach the outputs (capi.HANGING_MODE_*): 0 as ever (3-D unsplit and model 3:
@@ -689,7 +700,8 @@ class Assembler:
     @property
     def split_route(self) -> int:
         """Where the residual-only assembly of a 3-D mesh under a split law runs (Context.set_split_route): 0 the general
-        family, 1 the row-owner kernels of the lattice under model 3, 3 under models 1 and 3.  May change at any time."""
+        family, 1 the row-owner kernels of the lattice under model 3, 3 under models 1 and 3; 5 and 7: the same, and the full
+        assembly of model 3 on the row-owner kernels too.  May change at any time."""
         return self.ctx.split_route
 
     @split_route.setter

@@ -1709,7 +1709,8 @@ namespace pfm
   // Carries out pl = plan_cart(v, cv, p, ...) on the context's stream s; s_side: the stream the caller has forked off it (for the
   // phase-field kernel of the pair, or under PFM_SIDE_STREAM for the residual kernel: both only read the node state), else s.
   int launch_assemble_cart(const CartPlan &pl, const DevView &v, const CartView &cv_in, const pfm_params &p, double *const *d_values,
-                           double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock)
+                           double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock,
+                           int *n_compressed)
   {
     using ResidualKernel = void (*)(DevView, CartView, Scal, double *, double *, int, int);
     static const ResidualKernel residual_kernel[5][2] = {{nullptr, nullptr}, // by CartResidual and its flag: every instantiation there is
@@ -1733,7 +1734,7 @@ namespace pfm
         const TileGrid &g = pl.grid[flat ? PFM_ZC_RES2 : PFM_ZC_RES3];
         // (CartPlan::voldev: the split law in the q-point form, whatever the scheme)
         const ResidualKernel kernel = pl.spectral ? k_cart_residual3<false, false, true>
-                                      : pl.voldev ? k_cart_residual3<false, true>
+                                      : (pl.voldev || pl.voldev_jac) ? k_cart_residual3<false, true>
                                                   : residual_kernel[pl.residual][pl.residual_flag()];
         if (g.n_tiles != 0)
           hipLaunchKernelGGL(kernel, dim3(flat ? g.n_tiles : xcd_grid(g.n_tiles)), dim3(flat ? 64 : RTX * RTY), 0, s_side, v, cv,
@@ -1743,6 +1744,11 @@ namespace pfm
       }
     // Jacobian of a 3-D box: (u,u) rows first; k_cart_phi4 patches constrained (u,u) diagonals afterwards (same stream, or
     // deferred: the pair) and clears the structurally zero (u,phi) block (cracks.cc:2333-2337) along with its (phi,u) stores
+    if (pl.voldev_jac) // the matrix values of the law (pfm_cart_split3.hip): whole, in phase 0 and in the second half
+      {
+        cv.tile_sel = 0;
+        return pl.split3_jac() ? launch_cart_split3_jac(pl, v, cv, p, d_values, n_compressed, s) : PFM_OK;
+      }
     double *const res_rows = pl.rows_residual ? res_pde : nullptr;
     cv.tile_sel = pl.tile_sel(PFM_ZC_UU3);
     int rc = PFM_OK;

@@ -23,7 +23,7 @@ namespace pfm
     return {p.decompose_stress_matrix > 0 && p.timestep_number > 0, !mono && !penalised, !(p.constant_k < 0.5)};
   }
 
-  // The 3-D law of a split assembly and where its residual may run (pfm_set_split_model, pfm_set_split_route).  The default
+  // The 3-D law of a split assembly and where its residual -- and, bit 4 of the route, its Jacobian -- may run (pfm_set_split_model, pfm_set_split_route).  The default
   // is what a caller of neither gets: every split assembly belongs to the general family.
   struct CartSplit
   {
@@ -93,18 +93,24 @@ namespace pfm
     return g;
   }
 
-  enum CartResidual { PFM_RES_NONE, PFM_RES_3X, PFM_RES_3D, PFM_RES_3, PFM_RES_2M }; // k_cart_residual3x<het>, 3d<het>, 3<linear> (CartPlan::voldev: 3<false, true>; spectral: 3<false, false, true>), 2m<linear>
+  enum CartResidual { PFM_RES_NONE, PFM_RES_3X, PFM_RES_3D, PFM_RES_3, PFM_RES_2M }; // k_cart_residual3x<het>, 3d<het>, 3<linear> (CartPlan::voldev, voldev_jac: 3<false, true>; spectral: 3<false, false, true>), 2m<linear>
   struct CartPlan
   {
     int dim = 0, phase = 0; // 0: the whole assembly; 1, 2: the halves of pfm_assemble_overlapped (ghost import in between)
     bool residual_only = false, supported = false; // not supported (stress split): the general family takes the assembly
     // ... but for the residual-only assembly of a 3-D context under PFM_SPLIT_VOLDEV on PFM_SPLIT_ROUTE_LATTICE: the law is a few
     // scalar statements on the strain and runs in k_cart_residual3<false, true>, for every scheme, cut into halves as an
-    // unsplit PFM_RES_3 is (the Jacobian kernels have no split form: a full assembly stays unsupported)
+    // unsplit PFM_RES_3 is (k_cart_uu3 and k_cart_phi4 have no split form: a full assembly is voldev_jac's, below, or unsupported)
     bool voldev = false;
     // ... and under PFM_SPLIT_SPECTRAL on PFM_SPLIT_ROUTE_LATTICE_ANY: the eigen split of pfm_split3.h at the q-points of
     // k_cart_residual3<false, false, true>.  In every other field the plan is the voldev plan of the same lattice and phase.
     bool spectral = false;
+    // ... and the FULL assembly of a 3-D box under PFM_SPLIT_VOLDEV on a route with PFM_SPLIT_ROUTE_LATTICE_JACOBIAN's bit 4:
+    // k_cart_split3_jac (pfm_cart_split3.hip) writes the matrix values with the law at its q-points, over the tiles and chunks
+    // of k_cart_uu3 (grid[PFM_ZC_UU3]), and k_cart_residual3<false, true> writes residual_pde, cut into halves as an unsplit
+    // PFM_RES_3 is.  The identity R_u = pressure part - K_uu u does not hold when d_mat != d_rhs: rows_residual and pair are
+    // false for every scheme.  Not on a level lattice of the 3-D overlay (CartView::row_of_box).
+    bool voldev_jac = false;
     bool linear = false, interleaved = false, het = false; // scheme; layout; per-cell Lame coefficients (CartView::cell_lam)
     // Full 3-D assembly, linear scheme: every residual row is an exact function of its own matrix row (R_u = pressure part -
     // K_uu u, R_phi = G_c/eps mass - K_phiphi phi), so the Jacobian kernels write it and no residual kernel runs (2.1 of 15.8 ms
@@ -123,7 +129,8 @@ namespace pfm
     // cut into interior / boundary tiles; the Jacobian kernels behind a residual kernel, and k_cart_phi4 always (it patches
     // (u,u) diagonals), run whole in the second half.
     bool cells2() const { return supported && dim == 2 && !residual_only; }
-    bool uu3() const { return supported && dim == 3 && !residual_only && (rows_residual || phase != 1); }
+    bool uu3() const { return supported && dim == 3 && !residual_only && !voldev_jac && (rows_residual || phase != 1); }
+    bool split3_jac() const { return supported && voldev_jac && phase != 1; } // k_cart_split3_jac: whole, behind the residual kernel
     bool phi4() const { return uu3() && phase != 1; }
     bool oldf() const { return !linear; } // k_cart_phi4<OLDF>: q-point loops, old phase fields in the nodal ring
     bool residual_flag() const { return residual <= PFM_RES_3D ? het : linear; }
@@ -142,14 +149,17 @@ namespace pfm
     CartPlan pl;
     pl.dim = v.dim, pl.phase = phase, pl.residual_only = residual_only != 0;
     const bool lattice_law = sc.split && v.dim == 3 && pl.residual_only; // a split residual that the row-owner kernel can carry
+    const int res_route = split.route & PFM_SPLIT_ROUTE_LATTICE_ANY; // bit 4 (the Jacobian) says nothing about the residual-only call
     pl.voldev = lattice_law && split.model == PFM_SPLIT_VOLDEV &&
-                (split.route == PFM_SPLIT_ROUTE_LATTICE || split.route == PFM_SPLIT_ROUTE_LATTICE_ANY);
-    pl.spectral = lattice_law && split.model == PFM_SPLIT_SPECTRAL && split.route == PFM_SPLIT_ROUTE_LATTICE_ANY;
-    pl.supported = (!sc.split || pl.voldev || pl.spectral) && (v.dim == 2 || v.dim == 3);
+                (res_route == PFM_SPLIT_ROUTE_LATTICE || res_route == PFM_SPLIT_ROUTE_LATTICE_ANY);
+    pl.spectral = lattice_law && split.model == PFM_SPLIT_SPECTRAL && res_route == PFM_SPLIT_ROUTE_LATTICE_ANY;
+    pl.voldev_jac = sc.split && v.dim == 3 && !pl.residual_only && split.model == PFM_SPLIT_VOLDEV && (split.route & 4) != 0 &&
+                    (split.route & PFM_SPLIT_ROUTE_LATTICE) != 0 && !cv.row_of_box;
+    pl.supported = (!sc.split || pl.voldev || pl.spectral || pl.voldev_jac) && (v.dim == 2 || v.dim == 3);
     if (!pl.supported)
       return pl;
     pl.linear = sc.linear, pl.interleaved = v.layout == PFM_LAYOUT_INTERLEAVED, pl.het = cv.cell_lam != nullptr;
-    pl.rows_residual = v.dim == 3 && !pl.residual_only && sc.linear && !sc.kappa_large && !sw.res_kernel && !pl.het;
+    pl.rows_residual = v.dim == 3 && !pl.residual_only && sc.linear && !sc.kappa_large && !sw.res_kernel && !pl.het && !pl.voldev_jac;
     pl.pair = pl.rows_residual && phase == 0 && !cv.row_of_box && !sw.jac_sequential && !sw.uu_clock && !sw.phi_clock;
     pl.one_launch = pl.cells2() && Switches::cart2d_one_launch();
     // the whole lexicographic box of a single rank, every byte offset of a node below 4 GiB: planes by transfer
@@ -160,11 +170,11 @@ namespace pfm
     if (v.dim == 2 && pl.residual_only)
       pl.residual = PFM_RES_2M;
     else if (v.dim == 3 && !pl.rows_residual)
-      pl.residual = (!(sc.linear && whole_lex) || pl.voldev || pl.spectral) ? PFM_RES_3
+      pl.residual = (!(sc.linear && whole_lex) || pl.voldev || pl.spectral || pl.voldev_jac) ? PFM_RES_3
                     : (v.fused_solution && !pl.interleaved && v.n_nodes >= 64 && !Switches::res_no_wide_transfers()) ? PFM_RES_3X : PFM_RES_3D;
     pl.uu3_clock = sw.uu_clock && !pl.interleaved && !pl.het;
     pl.phi4_clock = (!pl.interleaved && !pl.het && sc.linear) ? sw.phi_clock : 0;
-    const bool runs[PFM_TILE_KERNELS] = {pl.uu3(), pl.phi4(), pl.residual && v.dim == 3, pl.residual == PFM_RES_2M, pl.cells2()};
+    const bool runs[PFM_TILE_KERNELS] = {pl.uu3() || pl.split3_jac(), pl.phi4(), pl.residual && v.dim == 3, pl.residual == PFM_RES_2M, pl.cells2()};
     for (int k = 0; k < PFM_TILE_KERNELS; ++k)
       if (runs[k])
         {

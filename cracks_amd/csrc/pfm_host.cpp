@@ -1408,7 +1408,8 @@ extern "C"
 
   int pfm_set_split_route(pfm_ctx *c, int route)
   {
-    if (!c || (route != PFM_SPLIT_ROUTE_GENERAL && route != PFM_SPLIT_ROUTE_LATTICE && route != PFM_SPLIT_ROUTE_LATTICE_ANY))
+    if (!c || (route != PFM_SPLIT_ROUTE_GENERAL && route != PFM_SPLIT_ROUTE_LATTICE && route != PFM_SPLIT_ROUTE_LATTICE_ANY &&
+               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN && route != PFM_SPLIT_ROUTE_LATTICE_ALL))
       return c ? fail(c, PFM_ERR_BAD_ARG, "unknown split route") : PFM_ERR_BAD_ARG;
     if (route != PFM_SPLIT_ROUTE_GENERAL && c->v.dim != 3)
       return fail(c, PFM_ERR_UNSUPPORTED, "the lattice routes carry the 3-D split laws");
@@ -2362,7 +2363,7 @@ extern "C"
     // family alone): assemble_overlay
     // (a split assembly keeps its level lattices where plan_cart has a kernel with the law: CartPlan::voldev, CartPlan::spectral)
     if (!p.cart && c->v.dim == 3 && !c->levels3.empty() && c->kernel_path != 0 && !p.nothing)
-      p.level = plan_cart(c->v, c->levels3[0].cv, c->prm, residual_only, 0, cart_n_cu(), cart_split(c));
+      p.level = plan_cart(c->v, c->levels3[0].cv, c->prm, residual_only, 0, cart_n_cu(), cart_split(c)); // (never voldev_jac: row_of_box)
     p.overlay3 = p.level.supported;
     p.patches = (!p.cart && c->v.dim == 2 && c->n_patch_blocks > 0 && c->kernel_path != 0 && !p.nothing) || p.overlay3;
     // cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*) -- wanted.
@@ -2547,8 +2548,26 @@ extern "C"
     cv.up_block_cleared = p.up_block_cleared ? 1 : 0;
     if (!p.pair)
       cv.patch_idx = nullptr, cv.patch_val = nullptr, cv.patch_count = nullptr, cv.patch_cap = 0;
+    int *n_compressed = nullptr;
+    if (p.box.voldev_jac)
+      {
+        // cells with a compressed q-point, for pfm_ctx_split_route_info: counted by the kernel of the (whole or second-half) launch
+        if (!c->buf_compressed.p)
+          {
+            if (hipMalloc(&c->buf_compressed.p, 256) != hipSuccess)
+              return fail(c, PFM_ERR_NOMEM, "compressed-cell counter");
+            c->buf_compressed.bytes = 256;
+            c->allocs.push_back(c->buf_compressed.p);
+            c->device_bytes += 256;
+          }
+        n_compressed = c->buf_compressed.as<int>();
+        if (p.box.split3_jac() && hipMemsetAsync(n_compressed, 0, sizeof(int), c->stream) != hipSuccess)
+          return fail(c, PFM_ERR_HIP, "compressed-cell counter reset");
+      }
     rc = launch_assemble_cart(p.box, c->v, cv, c->prm, d_values, d_res_pde, d_res_tot, c->stream, p.fork ? c->side_stream : c->stream,
-                              c->d_scal, &c->clock);
+                              c->d_scal, &c->clock, n_compressed);
+    if (p.box.split3_jac())
+      c->compressed_valid = rc == PFM_OK;
     if (p.fork)
       if (const int rcj = join_from(c, c->side_stream, c->stream, c->ev_join, "join"))
         return rcj;
@@ -2711,6 +2730,8 @@ extern "C"
       if (const int rcl = ensure_overlap_lists(c))
         return rcl;
     AssemblyPlan plan = plan_assembly(c, residual_only, phase, d_values);
+    if (!residual_only && phase != 1 && !(plan.cart && plan.box.voldev_jac))
+      c->compressed_valid = false; // pfm_ctx_split_route_info: the count belongs to the last full assembly
     bool gather_ready = false;
     if (const int rct = ensure_tables(c, plan, gather_ready))
       return rct;
@@ -3125,6 +3146,34 @@ extern "C"
             const AssemblyPlan p = plan_assembly(c, 1, 0, nullptr);
             *lattice_residual = ((p.cart && (p.box.voldev || p.box.spectral)) || (p.overlay3 && (p.level.voldev || p.level.spectral))) ? 1 : 0;
           }
+      }
+    return PFM_OK;
+  }
+
+  int pfm_ctx_split_route_info(const pfm_ctx *c, int64_t out[4])
+  {
+    if (!c || !out)
+      return PFM_ERR_BAD_ARG;
+    int lattice_residual = 0;
+    (void)pfm_ctx_split_route(c, nullptr, &lattice_residual);
+    out[0] = c->split_route;
+    out[1] = lattice_residual;
+    out[2] = 0;
+    out[3] = -1;
+    if (c->have_params)
+      {
+        // the plan of such an assembly, not a second copy of its conditions
+        double *const no_values[4] = {nullptr, nullptr, nullptr, nullptr};
+        const AssemblyPlan p = plan_assembly(c, 0, 0, no_values);
+        out[2] = (p.cart && p.box.voldev_jac) ? 1 : 0;
+      }
+    if (c->compressed_valid && c->buf_compressed.p)
+      {
+        int n = 0;
+        (void)hipSetDevice(c->device);
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, c->buf_compressed.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+          return PFM_ERR_HIP;
+        out[3] = n;
       }
     return PFM_OK;
   }

@@ -174,7 +174,11 @@ namespace pfm
   // SGPRs in k_cart_phi4).  clock: the context's counters, for a plan that clocks a kernel.
   struct CartPlan;
   int launch_assemble_cart(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
-                           double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock);
+                           double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock,
+                           int *n_compressed = nullptr /* CartPlan::voldev_jac: device counter, zeroed by the caller */);
+  // pfm_cart_split3.hip: the matrix values of a CartPlan::voldev_jac assembly
+  int launch_cart_split3_jac(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
+                             int *n_compressed, hipStream_t s);
   int launch_cart2d(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
                     double *res_pde, double *res_tot, hipStream_t s);
   int launch_cart_uu3(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *vals_uu, hipStream_t s,
@@ -281,6 +285,8 @@ struct pfm_ctx
   bool have_params = false;
   int split_model = 0; // PFM_SPLIT_*: pfm_set_split_model
   int split_route = 0; // PFM_SPLIT_ROUTE_*: pfm_set_split_route
+  pfm::DevBuf buf_compressed;     // CartPlan::voldev_jac: cells with a compressed q-point, counted by k_cart_split3_jac (one int)
+  bool compressed_valid = false;  // ... of the last full assembly, which ran on that kernel (pfm_ctx_split_route_info)
   int n_blocks = 1;
   int kernel_path = 0;
   int force_phase = 0; // pfm_ctx_force_phase (measurement)

@@ -147,6 +147,10 @@ namespace pfm_glue_detail
     //                      split_model).  The Jacobian call's residual_pde still comes from the general family: the two
     //                      agree to rounding, not bit for bit.  Default PFM_SPLIT_ROUTE_GENERAL: nothing changes.
     //                      PFM_SPLIT_ROUTE_LATTICE_ANY does the same under PFM_SPLIT_SPECTRAL as well.
+    //                      PFM_SPLIT_ROUTE_LATTICE_JACOBIAN (= 1 | 4) and PFM_SPLIT_ROUTE_LATTICE_ALL (= 3 | 4) also hand the full
+    //                      assembly of a box or partitioned sub-box under PFM_SPLIT_VOLDEV to row-owner kernels: the Jacobian
+    //                      call's residual_pde and the line-search residuals then come from the same kernel, bit for bit.
+    //                      Not on the level lattices of an overlay, not under PFM_SPLIT_SPECTRAL (general family).
     //   hanging_mode:      PFM_HANGING_MODE_GATHER sends the cells at hanging vertices through per-cell scratch and an ordered
     //                      gather instead of atomic adds, in 2-D and under every 3-D law: two assemble() calls of the same state
     //                      then give the same bytes (pfm_set_hanging_mode; forwarded next to split_route).  Default

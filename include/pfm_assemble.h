@@ -152,20 +152,47 @@ int pfm_set_split_model(pfm_ctx *ctx, int model);
  *                            route's to rounding and bitwise reproducible run to run only under PFM_HANGING_MODE_GATHER
  *                            (pfm_set_hanging_mode; a box or a partitioned sub-box always is).  With model 0 it is accepted and has no effect.  The value 2 alone
  *                            is unassigned and stays refused.
+ *   PFM_SPLIT_ROUTE_LATTICE_JACOBIAN  (= 1 | 4) PFM_SPLIT_ROUTE_LATTICE, and under PFM_SPLIT_VOLDEV the FULL assembly
+ *                            (Jacobian + residual_pde) of a 3-D box or partitioned sub-box on row-owner kernels as well: the
+ *                            matrix values by k_cart_split3_jac with the law at its q-points (every value computed by one
+ *                            lane and written once, bitwise reproducible and independent of the partition), residual_pde by
+ *                            k_cart_residual3<false, true>.  Whole and as both halves of pfm_assemble_overlapped /
+ *                            pfm_ctx_force_phase, for every scheme, both layouts, per-cell Lame coefficients and any
+ *                            decompose_stress_matrix / decompose_stress_rhs weights.  The residual_pde of the Jacobian call
+ *                            and the residual-only (line-search) residuals then come from the same kernel: equal bit for
+ *                            bit.  Residual-only calls are those of PFM_SPLIT_ROUTE_LATTICE, bit for bit.  Under model 1 the
+ *                            full assembly stays with the general family (the spectral law has no form there) and the route
+ *                            acts as PFM_SPLIT_ROUTE_LATTICE (no effect); with model 0 it is accepted and has no effect.  The
+ *                            level lattices of a 3-D overlay keep the general family for the full assembly under this route
+ *                            (deliberately: their residual-only call follows the route as under 1 and 3), and so does a
+ *                            context forced to path 0.  h(tr E) and tr- come from the trace the kernels compute, all three
+ *                            from the same statement on the same operands; where tr E of a q-point is zero up to rounding the
+ *                            matrix is not determined -- as under the general family, which may then pick the other branch.
+ *   PFM_SPLIT_ROUTE_LATTICE_ALL  (= 1 | 2 | 4) the same with the residual-only calls of PFM_SPLIT_ROUTE_LATTICE_ANY: under
+ *                            model 1 the residual-only call runs on the lattice kernels, the full assembly does not.
+ *                            The values 4 and 6 (the Jacobian bit without bit 1) are refused with PFM_ERR_BAD_ARG.
  * May be called at any time on a living context: the next assembly follows it.  An unknown route: PFM_ERR_BAD_ARG.
- * PFM_SPLIT_ROUTE_LATTICE or _ANY on a 2-D context: PFM_ERR_UNSUPPORTED.  PFM_SPLIT_ROUTE_LATTICE with model 0 or 1 is
+ * Any route but PFM_SPLIT_ROUTE_GENERAL on a 2-D context: PFM_ERR_UNSUPPORTED.  PFM_SPLIT_ROUTE_LATTICE with model 0 or 1 is
  * accepted and has no effect.
  * pfm_ctx_split_route: the route set and, lattice_residual, whether a residual-only assembly with the current parameters,
  * model and forced path would run its law, either one, on the row-owner kernels (0 before pfm_set_params); either pointer
- * may be null. */
+ * may be null.
+ * pfm_ctx_split_route_info: answered from the plan of such assemblies.  out[0] the route; out[1] whether a residual-only
+ * assembly would run its law on the row-owner kernels (what pfm_ctx_split_route answers); out[2] whether a full assembly
+ * would (0 before pfm_set_params); out[3] the number of owned cells (cells whose lowest vertex this rank owns) with at least
+ * one compressed q-point, h(tr E) = 0, as counted by k_cart_split3_jac in the last full assembly of this context -- -1 when
+ * that assembly did not run on that kernel or none has run.  Reading out[3] waits for the context's stream. */
 enum
 {
   PFM_SPLIT_ROUTE_GENERAL = 0,
   PFM_SPLIT_ROUTE_LATTICE = 1,
-  PFM_SPLIT_ROUTE_LATTICE_ANY = 3
+  PFM_SPLIT_ROUTE_LATTICE_ANY = 3,
+  PFM_SPLIT_ROUTE_LATTICE_JACOBIAN = 5,
+  PFM_SPLIT_ROUTE_LATTICE_ALL = 7
 };
 int pfm_set_split_route(pfm_ctx *ctx, int route);
 int pfm_ctx_split_route(const pfm_ctx *ctx, int *route, int *lattice_residual);
+int pfm_ctx_split_route_info(const pfm_ctx *ctx, int64_t out[4]);
 /* How the cells at hanging vertices of a general mesh (2-D or 3-D, with or without a cartesian overlay) reach the outputs.
  *   PFM_HANGING_MODE_DEFAULT  what every context did before this call existed, bit for bit: 3-D unsplit and model 3 write
  *                             K' = C^T K C, R' = C^T R and their placeholder diagonals to per-cell scratch, and an ordered

@@ -25,6 +25,13 @@ all arms alternating round by round in one process.  The two routes are compared
 --route general lattice --model spectral does the same for PFM_SPLIT_SPECTRAL: "general" is route 0, the general family over all
 cells, and "lattice" is PFM_SPLIT_ROUTE_LATTICE_ANY, k_cart_residual3<false, false, true>.  Same arms, alternation and JSON
 keys, plus "model".  Without --model spectral the --route run times model 3 as before.
+
+--jacobian --route general lattice --model voldev times the FULL assembly (Jacobian + residual_pde) of PFM_SPLIT_VOLDEV on the box
+context: "general" is route 0 (the general family over all cells), "lattice" is PFM_SPLIT_ROUTE_LATTICE_JACOBIAN
+(k_cart_split3_jac + k_cart_residual3<false, true>), on a state whose traces are of either sign (a deviatoric gradient plus
+noise; the share of cells with a compressed q-point comes from pfm_ctx_split_route_info).  Next to them "lattice_tension", the
+lattice route on a state of pure tension, and "unsplit", the full assembly with the split off (the pair k_cart_uu3 +
+k_cart_phi4).  All arms alternate round by round in one process (--rounds 6 for a record).
 """
 import argparse
 import json
@@ -50,7 +57,10 @@ def main():
     ap.add_argument("--route", choices=["general", "lattice"], nargs="+", default=None,
                     help="time the residual-only assembly of model 3 (--model spectral: of model 1) per split route on the box context "
                          "instead (see above)")
+    ap.add_argument("--jacobian", action="store_true", help="with --route: time the full assembly of model 3 per route (see above)")
     args = ap.parse_args()
+    if args.jacobian and (not args.route or (args.model or ["voldev"]) != ["voldev"]):
+        raise SystemExit("--jacobian goes with --route general lattice and model voldev")
     route_spectral = bool(args.route) and args.model == ["spectral"]  # (--route without --model: model 3, as before)
     args.model = args.model or ["spectral"]
 
@@ -88,6 +98,10 @@ def main():
     asm.set_vectors(sol, old, old)
     asm.allocate_matrix()
 
+    if args.jacobian:
+        dev_grad = 1e-2 * np.array([[0.9, 0.7, -0.3], [0.1, -0.8, 0.5], [0.4, -0.2, -0.1]])  # trace 0: the noise decides the sign
+        mixed = lay.pack(mesh.coords @ dev_grad.T + noise, phi)
+        return bench_jacobian(args, asm, capi, mesh, prm_off, prm_on, {"mixed": mixed, "tension": tension}, old)
     if args.route:
         return bench_routes(args, asm, capi, mesh, prm_off, prm_on, O.make_params(**{"lambda": 121.15}, outer_solver=1, gamma_penal=1e-2, **base),
                             route_spectral)
@@ -198,6 +212,67 @@ def bench_routes(args, asm, capi, mesh, prm_off, prm_on, prm_qpoint, spectral=Fa
     if "lattice" in med:
         rec["lattice_over_unsplit"] = med["lattice"] / med["unsplit"]
         rec["lattice_over_unsplit_qpoint"] = med["lattice"] / med["unsplit_qpoint"]
+    if "lattice" in med and "general" in med:
+        rec["lattice_over_general"] = med["lattice"] / med["general"]
+        rec["lattice_below_general_in_every_round"] = all(np.median(l) < np.median(g) for l, g in zip(ts["lattice"], ts["general"]))
+    print(json.dumps(rec))
+
+
+def bench_jacobian(args, asm, capi, mesh, prm_off, prm_on, states, old):
+    """--jacobian: full-assembly arms on the box context (kernel path 1), alternating round by round"""
+    routes = {"general": capi.SPLIT_ROUTE_GENERAL, "lattice": capi.SPLIT_ROUTE_LATTICE_JACOBIAN, "lattice_tension": capi.SPLIT_ROUTE_LATTICE_JACOBIAN}
+    arms = list(dict.fromkeys(args.route)) + ["lattice_tension", "unsplit"]
+    asm.split_model = capi.SPLIT_VOLDEV
+    current = [None]
+
+    def configure(arm):
+        state = "tension" if arm == "lattice_tension" else "mixed"
+        if current[0] != state:
+            asm.set_vectors(states[state], old, old)
+            current[0] = state
+        asm.split_route = routes.get(arm, capi.SPLIT_ROUTE_GENERAL)
+        asm.set_params(prm_on if arm in routes else prm_off)
+        assert asm.ctx.kernel_path == 1 and asm.ctx.split_route_plan()[2] == int(arm.startswith("lattice"))
+
+    def timed(arm):
+        configure(arm)
+        for _ in range(args.warmup):
+            asm.assemble_system(False)
+        asm.synchronize()
+        asm.ctx.timing_enable(True)
+        for _ in range(args.reps):
+            asm.assemble_system(False)
+        asm.synchronize()
+        ts = asm.ctx.kernel_times_ms()
+        asm.ctx.timing_enable(False)
+        assert ts.size == args.reps
+        return ts
+
+    outs, compressed = {}, {}
+    for arm in [a for a in arms if a in routes]:
+        configure(arm)
+        asm.assemble_system(False)
+        asm.synchronize()
+        compressed[arm] = asm.ctx.split_route_plan()[3]
+        if arm in ("general", "lattice"):
+            outs[arm] = [m.clone() for m in asm.system_pde_matrix] + [asm.system_pde_residual.clone()]
+    rec = {"metric": "split3d_routes_jacobian", "cells": int(mesh.n_cells), "layout": args.layout, "reps": args.reps, "rounds": args.rounds,
+           "arms": arms, "cells_with_a_compressed_q_point": {k: v for k, v in compressed.items() if v >= 0}}
+    if len(outs) == 2:
+        rec["lattice_deviation_from_general"] = max(float((a - b).abs().max() / max(1.0, float(b.abs().max())))
+                                                    for a, b in zip(outs["lattice"], outs["general"]))
+    del outs
+    ts = {arm: [] for arm in arms}
+    for _ in range(args.rounds):
+        for arm in arms:
+            ts[arm].append(timed(arm))
+    med = {arm: float(np.median(np.concatenate(ts[arm]))) for arm in arms}
+    for arm in arms:
+        rec[arm] = {"ms": med[arm], "min_ms": float(np.concatenate(ts[arm]).min()), "round_medians_ms": [float(np.median(t)) for t in ts[arm]],
+                    "ms_per_1e6_cells": med[arm] * 1e6 / mesh.n_cells}
+    if "lattice" in med:
+        rec["lattice_over_unsplit"] = med["lattice"] / med["unsplit"]
+        rec["lattice_tension_over_unsplit"] = med["lattice_tension"] / med["unsplit"]
     if "lattice" in med and "general" in med:
         rec["lattice_over_general"] = med["lattice"] / med["general"]
         rec["lattice_below_general_in_every_round"] = all(np.median(l) < np.median(g) for l, g in zip(ts["lattice"], ts["general"]))
