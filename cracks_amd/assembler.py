@@ -124,7 +124,9 @@ class Context:
         with the law at its q-points under model 3 (no effect on model 1), 3 the same kernel under model 3 and under model 1,
         the spectral law.  5 (= 1 | 4) and 7 (= 3 | 4): the same residual-only calls, and under model 3 the full assembly of a
         box or a partitioned sub-box on the row-owner kernels as well (k_cart_split3_jac; not on the level lattices of an overlay,
-        not under model 1); 4 and 6 are refused.  At any time on a living context; routes 0, 1 and 3 have no effect on full
+        not under model 1); 4 and 6 are refused.  13 (= 5 | 8) and 15 (= 7 | 8): the same, and the level lattices of a 3-D overlay take
+        that full assembly too (level form of k_cart_split3_jac; regular rows then have residual_pde of the full and of the
+        residual-only call bit for bit equal); every other value with bit 8 is refused.  At any time on a living context; routes 0, 1 and 3 have no effect on full
         assemblies."""
         self._check(self.lib.pfm_set_split_route(self._h, int(route)), "pfm_set_split_route")
         self.split_route = int(route)
@@ -701,7 +703,8 @@ class Assembler:
     def split_route(self) -> int:
         """Where the residual-only assembly of a 3-D mesh under a split law runs (Context.set_split_route): 0 the general
         family, 1 the row-owner kernels of the lattice under model 3, 3 under models 1 and 3; 5 and 7: the same, and the full
-        assembly of model 3 on the row-owner kernels too.  May change at any time."""
+        assembly of model 3 on the row-owner kernels too; 13 and 15: also on the level lattices of a 3-D overlay.  May change at any
+        time."""
         return self.ctx.split_route
 
     @split_route.setter

@@ -21,6 +21,7 @@ LAYOUT_INTERLEAVED, LAYOUT_BLOCKED = 0, 1
 SPLIT_REFERENCE, SPLIT_SPECTRAL, SPLIT_VOLDEV = 0, 1, 3  # pfm_set_split_model (2 is unassigned)
 SPLIT_ROUTE_GENERAL, SPLIT_ROUTE_LATTICE, SPLIT_ROUTE_LATTICE_ANY = 0, 1, 3  # pfm_set_split_route (2 is unassigned)
 SPLIT_ROUTE_LATTICE_JACOBIAN, SPLIT_ROUTE_LATTICE_ALL = 5, 7  # ... | 4: the full assembly of model 3 on the row-owner kernels too (4, 6 refused)
+SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS, SPLIT_ROUTE_LATTICE_ALL_LEVELS = 13, 15  # ... | 8: the level lattices of a 3-D overlay take that full assembly too (8-12, 14 refused)
 HANGING_MODE_DEFAULT, HANGING_MODE_GATHER, HANGING_MODE_ATOMIC = 0, 1, 2  # pfm_set_hanging_mode
 
 # every symbol include/pfm_assemble.h declares

@@ -109,7 +109,8 @@ namespace pfm
     // k_cart_split3_jac (pfm_cart_split3.hip) writes the matrix values with the law at its q-points, over the tiles and chunks
     // of k_cart_uu3 (grid[PFM_ZC_UU3]), and k_cart_residual3<false, true> writes residual_pde, cut into halves as an unsplit
     // PFM_RES_3 is.  The identity R_u = pressure part - K_uu u does not hold when d_mat != d_rhs: rows_residual and pair are
-    // false for every scheme.  Not on a level lattice of the 3-D overlay (CartView::row_of_box).
+    // false for every scheme.  On a level lattice of the 3-D overlay (CartView::row_of_box) only with bit 8 of the route
+    // (PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS, _ALL_LEVELS): k_cart_split3_jac<NCOL, true> over grid[PFM_ZC_UU3] of that level.
     bool voldev_jac = false;
     bool linear = false, interleaved = false, het = false; // scheme; layout; per-cell Lame coefficients (CartView::cell_lam)
     // Full 3-D assembly, linear scheme: every residual row is an exact function of its own matrix row (R_u = pressure part -
@@ -149,12 +150,12 @@ namespace pfm
     CartPlan pl;
     pl.dim = v.dim, pl.phase = phase, pl.residual_only = residual_only != 0;
     const bool lattice_law = sc.split && v.dim == 3 && pl.residual_only; // a split residual that the row-owner kernel can carry
-    const int res_route = split.route & PFM_SPLIT_ROUTE_LATTICE_ANY; // bit 4 (the Jacobian) says nothing about the residual-only call
+    const int res_route = split.route & PFM_SPLIT_ROUTE_LATTICE_ANY; // bits 4 and 8 (the Jacobian) say nothing about the residual-only call
     pl.voldev = lattice_law && split.model == PFM_SPLIT_VOLDEV &&
                 (res_route == PFM_SPLIT_ROUTE_LATTICE || res_route == PFM_SPLIT_ROUTE_LATTICE_ANY);
     pl.spectral = lattice_law && split.model == PFM_SPLIT_SPECTRAL && res_route == PFM_SPLIT_ROUTE_LATTICE_ANY;
     pl.voldev_jac = sc.split && v.dim == 3 && !pl.residual_only && split.model == PFM_SPLIT_VOLDEV && (split.route & 4) != 0 &&
-                    (split.route & PFM_SPLIT_ROUTE_LATTICE) != 0 && !cv.row_of_box;
+                    (split.route & PFM_SPLIT_ROUTE_LATTICE) != 0 && (!cv.row_of_box || (split.route & 8) != 0);
     pl.supported = (!sc.split || pl.voldev || pl.spectral || pl.voldev_jac) && (v.dim == 2 || v.dim == 3);
     if (!pl.supported)
       return pl;

@@ -17,6 +17,11 @@
 //   phase-field row and the residual kernel take the sign from the same statement on the same operands.  Where tr E is zero
 //   up to rounding the matrix is not determined (include/pfm_assemble.h).
 //
+//   LEVEL FORM (template parameter LEVEL; PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS / _ALL_LEVELS): the same rows on one
+//   refinement level's lattice of a 3-D overlay.  The rows of the launch are the regular rows of that level
+//   (CartView::row_of_box; -1: the lane passes the node by), slots come from the overlay's nbr_mask / row_perm, Lame
+//   coefficients and cell sizes are the level's.  The box instantiations are the parent's instruction for instruction.
+//
 // Tiles: those of k_cart_uu3 (T3X x T3Y owned nodes, z-chunks of CartPlan::grid[PFM_ZC_UU3]); a workgroup is one wave, its 64
 // lanes two node planes of the tile, marching up its chunk two planes at a time.
 #include "pfm_internal.h"
@@ -496,7 +501,12 @@ namespace pfm
     constexpr int SJ_NT = 64; // one wave: T3X x T3Y nodes of two planes
     static_assert(T3X * T3Y * 2 == SJ_NT, "two node planes of a k_cart_uu3 tile per wave");
 
-    template <int NCOL>
+    // LEVEL (CartPlan::voldev_jac under PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS / _ALL_LEVELS): cv is one refinement level's
+    // lattice of a 3-D overlay (CartView::row_of_box) -- the rows of the launch are those of row_of_box (the statement of cart_row_id, pfm_cart_common.h), -1 = hanging, parent,
+    // mixed-level or ghost node: not a row of this launch, the lane passes it by.  Everything else is the box form: nodes of
+    // other levels inside the bounding box read as absent (local_of_box == -1) and only enter rows that are not written, a
+    // row at a face of the domain has fewer cells and neighbours (nbr_mask, always with bit 31: row_perm), owned_lex is 0.
+    template <int NCOL, bool LEVEL>
     __global__ __launch_bounds__(SJ_NT) void k_cart_split3_jac(SjArgs A)
     {
       const CartView &cv = A.cv;
@@ -525,7 +535,8 @@ namespace pfm
 #pragma unroll 1
       for (int gk = kA + t / (T3X * T3Y); gk < kB; gk += 2)
         {
-          const int row = sj_local_id(cv, gi, gj, gk); // an owned node of the box: its row
+          const int row = LEVEL ? cv.row_of_box[gi + (long long)cv.NX * (gj + (long long)cv.NY * gk)] // a regular row of this level, or -1
+                                : sj_local_id(cv, gi, gj, gk);                                       // an owned node of the box: its row
           if (row < 0 || row >= A.v.n_owned)
             continue;
           const unsigned row_flag = A.v.node_flags[row];
@@ -550,10 +561,13 @@ namespace pfm
     const bool il = pl.interleaved; // one block of values
     SjArgs ka{v, cv, make_sj_scal(p, cv), d_values[0], il ? nullptr : d_values[1], il ? nullptr : d_values[2], il ? nullptr : d_values[3],
               n_compressed, g.zc};
-    if (il)
-      hipLaunchKernelGGL(k_cart_split3_jac<4>, dim3(xcd_grid(g.n_tiles)), dim3(SJ_NT), 0, s, ka);
-    else
-      hipLaunchKernelGGL(k_cart_split3_jac<3>, dim3(xcd_grid(g.n_tiles)), dim3(SJ_NT), 0, s, ka);
+    const bool level = cv.row_of_box != nullptr;
+    if (level && (!cv.nbr_mask || !cv.row_perm || cv.owned_lex))
+      return PFM_ERR_INTERNAL; // (the overlay's row tables: ensure_overlay3_ready)
+    using Kernel = void (*)(SjArgs);
+    static const Kernel kernel[2][2] = {{k_cart_split3_jac<3, false>, k_cart_split3_jac<3, true>}, // by layout and LEVEL
+                                        {k_cart_split3_jac<4, false>, k_cart_split3_jac<4, true>}};
+    hipLaunchKernelGGL(kernel[il][level], dim3(xcd_grid(g.n_tiles)), dim3(SJ_NT), 0, s, ka);
     return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
   }
 } // namespace pfm

@@ -1409,7 +1409,8 @@ extern "C"
   int pfm_set_split_route(pfm_ctx *c, int route)
   {
     if (!c || (route != PFM_SPLIT_ROUTE_GENERAL && route != PFM_SPLIT_ROUTE_LATTICE && route != PFM_SPLIT_ROUTE_LATTICE_ANY &&
-               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN && route != PFM_SPLIT_ROUTE_LATTICE_ALL))
+               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN && route != PFM_SPLIT_ROUTE_LATTICE_ALL &&
+               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS && route != PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS))
       return c ? fail(c, PFM_ERR_BAD_ARG, "unknown split route") : PFM_ERR_BAD_ARG;
     if (route != PFM_SPLIT_ROUTE_GENERAL && c->v.dim != 3)
       return fail(c, PFM_ERR_UNSUPPORTED, "the lattice routes carry the 3-D split laws");
@@ -2363,7 +2364,7 @@ extern "C"
     // family alone): assemble_overlay
     // (a split assembly keeps its level lattices where plan_cart has a kernel with the law: CartPlan::voldev, CartPlan::spectral)
     if (!p.cart && c->v.dim == 3 && !c->levels3.empty() && c->kernel_path != 0 && !p.nothing)
-      p.level = plan_cart(c->v, c->levels3[0].cv, c->prm, residual_only, 0, cart_n_cu(), cart_split(c)); // (never voldev_jac: row_of_box)
+      p.level = plan_cart(c->v, c->levels3[0].cv, c->prm, residual_only, 0, cart_n_cu(), cart_split(c)); // (voldev_jac: bit 8 of the route)
     p.overlay3 = p.level.supported;
     p.patches = (!p.cart && c->v.dim == 2 && c->n_patch_blocks > 0 && c->kernel_path != 0 && !p.nothing) || p.overlay3;
     // cells at hanging vertices: scratch + ordered gather instead of atomics (round 6; DevView::hs_*) -- wanted.
@@ -2386,7 +2387,7 @@ extern "C"
     // off the context's stream (a level lattice of 6e5 nodes fills a third of the chip's dispatch slots; the levels
     // write disjoint rows) when PFM_OVERLAY3_CONCURRENT=1 is set.  Default: one after the other on the context's
     // stream -- measured the better of the two (profiles/r05/ov3_ab.txt: 4.56 against 4.86 ms per Jacobian)
-    p.levels_concurrent = p.overlay3 && c->levels3.size() > 1 && switches().levels_concurrent;
+    p.levels_concurrent = p.overlay3 && c->levels3.size() > 1 && Switches::levels_concurrent();
     // 2-D box, blocked layout: the structurally zero (u,phi) block (cracks.cc:2333-2337) by a fill in front of the kernels,
     // in the whole assembly and in phase 1; phase 2 takes it as cleared by phase 1 (CartView::up_block_cleared).
     // (round 6, measured and removed for 3-D: clearing the block with a fill on a third stream instead of by 21 of the 49
@@ -2521,6 +2522,24 @@ extern "C"
     return e == hipSuccess ? PFM_OK : hipfail(c, e, "zero outputs");
   }
 
+  // CartPlan::voldev_jac: the device counter of the cells with a compressed q-point (pfm_ctx_split_route_info), made on first
+  // use; zero: emptied on the context's stream, in front of the launch (or the first of the launches) that counts
+  static int compressed_counter(pfm_ctx *c, bool zero, int *&n_compressed)
+  {
+    if (!c->buf_compressed.p)
+      {
+        if (hipMalloc(&c->buf_compressed.p, 256) != hipSuccess)
+          return fail(c, PFM_ERR_NOMEM, "compressed-cell counter");
+        c->buf_compressed.bytes = 256;
+        c->allocs.push_back(c->buf_compressed.p);
+        c->device_bytes += 256;
+      }
+    n_compressed = c->buf_compressed.as<int>();
+    if (zero && hipMemsetAsync(n_compressed, 0, sizeof(int), c->stream) != hipSuccess)
+      return fail(c, PFM_ERR_HIP, "compressed-cell counter reset");
+    return PFM_OK;
+  }
+
   // Two statuses, here and in launch_levels / gather_hanging: the return value ends the call at once (its text is set);
   // `rc` (in/out) is the status of the launches, which assemble_impl reports behind the joins and the closing event.
   // cartesian box, 2-D / 3-D: the pair with its deferred placeholder patches, the fork, the fill of the (u,phi) block
@@ -2549,21 +2568,9 @@ extern "C"
     if (!p.pair)
       cv.patch_idx = nullptr, cv.patch_val = nullptr, cv.patch_count = nullptr, cv.patch_cap = 0;
     int *n_compressed = nullptr;
-    if (p.box.voldev_jac)
-      {
-        // cells with a compressed q-point, for pfm_ctx_split_route_info: counted by the kernel of the (whole or second-half) launch
-        if (!c->buf_compressed.p)
-          {
-            if (hipMalloc(&c->buf_compressed.p, 256) != hipSuccess)
-              return fail(c, PFM_ERR_NOMEM, "compressed-cell counter");
-            c->buf_compressed.bytes = 256;
-            c->allocs.push_back(c->buf_compressed.p);
-            c->device_bytes += 256;
-          }
-        n_compressed = c->buf_compressed.as<int>();
-        if (p.box.split3_jac() && hipMemsetAsync(n_compressed, 0, sizeof(int), c->stream) != hipSuccess)
-          return fail(c, PFM_ERR_HIP, "compressed-cell counter reset");
-      }
+    if (p.box.voldev_jac) // counted by the kernel of the (whole or second-half) launch
+      if (const int rcc = compressed_counter(c, p.box.split3_jac(), n_compressed))
+        return rcc;
     rc = launch_assemble_cart(p.box, c->v, cv, c->prm, d_values, d_res_pde, d_res_tot, c->stream, p.fork ? c->side_stream : c->stream,
                               c->d_scal, &c->clock, n_compressed);
     if (p.box.split3_jac())
@@ -2617,6 +2624,11 @@ extern "C"
           rc = upload_mat_scal(c->prm, lv.cv, lv.d_scal, c->stream);
           lv.scal_dirty = rc != PFM_OK;
         }
+    // CartPlan::voldev_jac: one counter for all levels, emptied once, in front of the first level and of the fork
+    int *n_compressed = nullptr;
+    if (p.level.voldev_jac)
+      if (const int rcc = compressed_counter(c, true, n_compressed))
+        return rcc;
     const bool par = p.levels_concurrent && rc == PFM_OK;
     if (par)
       {
@@ -2642,8 +2654,10 @@ extern "C"
         hipStream_t st = par ? c->ov_streams[i] : c->stream;
         const pfm::CartView &lcv = c->levels3[i].cv; // one plan per level lattice
         rc = launch_assemble_cart(plan_cart(c->v, lcv, c->prm, p.residual_only, 0, cart_n_cu(), cart_split(c)), c->v, lcv, c->prm, d_values, d_res_pde,
-                                  d_res_tot, st, st, c->levels3[i].d_scal, &c->clock);
+                                  d_res_tot, st, st, c->levels3[i].d_scal, &c->clock, n_compressed);
       }
+    if (p.level.voldev_jac)
+      c->compressed_valid = rc == PFM_OK;
     for (size_t i = 0; par && i < nl; ++i)
       if (const int rcj = join_from(c, c->ov_streams[i], c->stream, c->ov_events[i], "join (overlay levels)"))
         return rcj;
@@ -2730,7 +2744,7 @@ extern "C"
       if (const int rcl = ensure_overlap_lists(c))
         return rcl;
     AssemblyPlan plan = plan_assembly(c, residual_only, phase, d_values);
-    if (!residual_only && phase != 1 && !(plan.cart && plan.box.voldev_jac))
+    if (!residual_only && phase != 1 && !(plan.cart && plan.box.voldev_jac) && !(plan.overlay3 && plan.level.voldev_jac))
       c->compressed_valid = false; // pfm_ctx_split_route_info: the count belongs to the last full assembly
     bool gather_ready = false;
     if (const int rct = ensure_tables(c, plan, gather_ready))
@@ -3165,7 +3179,7 @@ extern "C"
         // the plan of such an assembly, not a second copy of its conditions
         double *const no_values[4] = {nullptr, nullptr, nullptr, nullptr};
         const AssemblyPlan p = plan_assembly(c, 0, 0, no_values);
-        out[2] = (p.cart && p.box.voldev_jac) ? 1 : 0;
+        out[2] = ((p.cart && p.box.voldev_jac) || (p.overlay3 && p.level.voldev_jac)) ? 1 : 0;
       }
     if (c->compressed_valid && c->buf_compressed.p)
       {

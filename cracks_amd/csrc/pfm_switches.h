@@ -14,7 +14,6 @@ namespace pfm
     // ---- once per process
     const bool jac_sequential = set("PFM_JAC_SEQUENTIAL");         // 3-D box: the two Jacobian kernels in turn, not side by side
     const bool general_sequential = set("PFM_GENERAL_SEQUENTIAL"); // general family: the atomic class behind the colour classes
-    const bool levels_concurrent = set("PFM_OVERLAY3_CONCURRENT"); // 3-D overlay: a stream per level lattice
     const bool res_kernel = set("PFM_RES_KERNEL");                 // 3-D box Jacobian: the quadrature residual kernel runs as well
     const bool no_prio = set("PFM_NO_PRIO");                       // k_cart_phi4 without its wave priorities
     const bool uu_clock = set("PFM_UU_CLK");                       // phase clock of k_cart_uu3 (profiling; pfm_kernel_clock.h)
@@ -29,6 +28,7 @@ namespace pfm
     // the (u,phi) block of a blocked 2-D box by a fill in front of the kernels (PFM_CART2D_NO_FILL: written with the rows)
     static bool cart2d_fill() { return !set("PFM_CART2D_NO_FILL") && !cart2d_one_launch(); }
     static bool fused_scatter() { return !set("PFM_NO_FUSED_SCATTER"); }     // line search: the residual kernel scatters the solution
+    static bool levels_concurrent() { return set("PFM_OVERLAY3_CONCURRENT"); } // 3-D overlay: a stream per level lattice
     static bool res_no_transfers() { return set("PFM_RES_NO_TRANSFERS"); }   // k_cart_residual3 instead of 3x / 3d
     static bool res_no_wide_transfers() { return set("PFM_RES_NO_WIDE_TRANSFERS"); } // k_cart_residual3d instead of 3x
     // ---- per pfm_ctx_create

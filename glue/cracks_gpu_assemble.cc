@@ -151,6 +151,9 @@ namespace pfm_glue_detail
     //                      assembly of a box or partitioned sub-box under PFM_SPLIT_VOLDEV to row-owner kernels: the Jacobian
     //                      call's residual_pde and the line-search residuals then come from the same kernel, bit for bit.
     //                      Not on the level lattices of an overlay, not under PFM_SPLIT_SPECTRAL (general family).
+    //                      PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS (= 5 | 8) and PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS (= 7 | 8): the
+    //                      level lattices of a refined 3-D mesh take that full assembly too; on their regular rows the two
+    //                      residuals are the same bytes, on the rows of the general family equal to rounding.
     //   hanging_mode:      PFM_HANGING_MODE_GATHER sends the cells at hanging vertices through per-cell scratch and an ordered
     //                      gather instead of atomic adds, in 2-D and under every 3-D law: two assemble() calls of the same state
     //                      then give the same bytes (pfm_set_hanging_mode; forwarded next to split_route).  Default

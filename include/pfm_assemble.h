@@ -171,6 +171,30 @@ int pfm_set_split_model(pfm_ctx *ctx, int model);
  *   PFM_SPLIT_ROUTE_LATTICE_ALL  (= 1 | 2 | 4) the same with the residual-only calls of PFM_SPLIT_ROUTE_LATTICE_ANY: under
  *                            model 1 the residual-only call runs on the lattice kernels, the full assembly does not.
  *                            The values 4 and 6 (the Jacobian bit without bit 1) are refused with PFM_ERR_BAD_ARG.
+ *   PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS  (= 1 | 4 | 8) PFM_SPLIT_ROUTE_LATTICE_JACOBIAN, and the level lattices of a 3-D
+ *                            overlay (adaptively refined meshes) take the full assembly under PFM_SPLIT_VOLDEV too: every
+ *                            regular row (a plain 27-neighbour row of one refinement level) has its matrix values from the
+ *                            level form of k_cart_split3_jac and its residual_pde from k_cart_residual3<false, true>; the
+ *                            cells that touch another row stay with the general family in its model-3 form, which skips
+ *                            the regular rows, with the cells at hanging vertices through scratch and the ordered gather by
+ *                            default (PFM_HANGING_ATOMIC=1 and pfm_set_hanging_mode as ever).  The tables, colour lists and
+ *                            zeroing are those of an unsplit overlay assembly.  PROMISED: on every regular row residual_pde
+ *                            of the full assembly and of the residual-only call are the same bytes; the matrix values of a
+ *                            regular row are written once by one lane and depend neither on the z-chunk length nor on
+ *                            PFM_OVERLAY3_CONCURRENT.  NOT PROMISED: the rows of the general family (hanging, parent,
+ *                            mixed-level rows and their neighbours) agree between the two calls to rounding only (measured:
+ *                            see profiles/split_lattice_jacobian_levels/README.md).  A cell next to the seam is evaluated by
+ *                            both families, each with its own tr E: where tr E is zero up to rounding the matrix is not
+ *                            determined, as above.  On a box or a sub-box this route is PFM_SPLIT_ROUTE_LATTICE_JACOBIAN
+ *                            byte for byte; under model 0 or 1, in 2-D (refused as every lattice route), on path 0 and with
+ *                            the split off it acts as that route does.  An overlay under PFM_SPLIT_ROUTE_LATTICE_JACOBIAN
+ *                            or _ALL keeps the general family for its full assembly, as before.  COST: this route is NOT
+ *                            faster than the general route on an overlay -- measured on the block-refined 84^3 mesh (1.1e6
+ *                            cells, 93 % regular rows) 22.4 ms per full assembly against 13.7 ms, above it in every round
+ *                            (profiles/split_lattice_jacobian_levels/README.md).  It is opt-in for the residual guarantee.
+ *   PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS  (= 1 | 2 | 4 | 8) the same with the residual-only calls of
+ *                            PFM_SPLIT_ROUTE_LATTICE_ANY.  Every other value with bit 8 (8, 9, 10, 11, 12, 14) is refused
+ *                            with PFM_ERR_BAD_ARG.
  * May be called at any time on a living context: the next assembly follows it.  An unknown route: PFM_ERR_BAD_ARG.
  * Any route but PFM_SPLIT_ROUTE_GENERAL on a 2-D context: PFM_ERR_UNSUPPORTED.  PFM_SPLIT_ROUTE_LATTICE with model 0 or 1 is
  * accepted and has no effect.
@@ -181,14 +205,18 @@ int pfm_set_split_model(pfm_ctx *ctx, int model);
  * assembly would run its law on the row-owner kernels (what pfm_ctx_split_route answers); out[2] whether a full assembly
  * would (0 before pfm_set_params); out[3] the number of owned cells (cells whose lowest vertex this rank owns) with at least
  * one compressed q-point, h(tr E) = 0, as counted by k_cart_split3_jac in the last full assembly of this context -- -1 when
- * that assembly did not run on that kernel or none has run.  Reading out[3] waits for the context's stream. */
+ * that assembly did not run on that kernel or none has run.  On a 3-D overlay under the _LEVELS routes out[2] is 1 and
+ * out[3] covers the cells of the level kernels only: the cells whose lowest vertex is a regular row, summed over the levels
+ * (the cells of the general family are not counted).  Reading out[3] waits for the context's stream. */
 enum
 {
   PFM_SPLIT_ROUTE_GENERAL = 0,
   PFM_SPLIT_ROUTE_LATTICE = 1,
   PFM_SPLIT_ROUTE_LATTICE_ANY = 3,
   PFM_SPLIT_ROUTE_LATTICE_JACOBIAN = 5,
-  PFM_SPLIT_ROUTE_LATTICE_ALL = 7
+  PFM_SPLIT_ROUTE_LATTICE_ALL = 7,
+  PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS = 13,
+  PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS = 15
 };
 int pfm_set_split_route(pfm_ctx *ctx, int route);
 int pfm_ctx_split_route(const pfm_ctx *ctx, int *route, int *lattice_residual);

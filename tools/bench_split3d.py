@@ -32,6 +32,14 @@ context: "general" is route 0 (the general family over all cells), "lattice" is 
 noise; the share of cells with a compressed q-point comes from pfm_ctx_split_route_info).  Next to them "lattice_tension", the
 lattice route on a state of pure tension, and "unsplit", the full assembly with the split off (the pair k_cart_uu3 +
 k_cart_phi4).  All arms alternate round by round in one process (--rounds 6 for a record).
+
+--jacobian --overlay --route general lattice --model voldev does the same on a mesh with hanging nodes: the block-refined mesh of
+bench.py's overlay_3d (the box of --n^3 hexes, 84 by default as there, with its inner half refined once), which the library runs
+as a 3-D overlay (kernel path 3).  "general" is route 0 -- the parent's path, its code unchanged: the general family over all
+cells with the full colour lists -- and "lattice" is PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS: the level form of
+k_cart_split3_jac + k_cart_residual3<false, true> on the regular rows of both level lattices, the general family over the cells
+that touch any other row.  "unsplit" is the unsplit overlay assembly of the same context (the yardstick).  The arms alternate
+round by round in one process; the state is the deviatoric gradient plus noise, hanging nodes interpolated.
 """
 import argparse
 import json
@@ -48,7 +56,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=100)
+    ap.add_argument("--n", type=int, default=None, help="hexes per direction (default 100; with --overlay 84, bench.py's overlay_3d)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3, help="off / on alternations; the medians of all rounds are reported")
@@ -58,7 +66,12 @@ def main():
                     help="time the residual-only assembly of model 3 (--model spectral: of model 1) per split route on the box context "
                          "instead (see above)")
     ap.add_argument("--jacobian", action="store_true", help="with --route: time the full assembly of model 3 per route (see above)")
+    ap.add_argument("--overlay", action="store_true", help="with --jacobian: on the block-refined mesh of bench.py's overlay_3d (see above)")
     args = ap.parse_args()
+    if args.overlay and not args.jacobian:
+        raise SystemExit("--overlay goes with --jacobian --route general lattice --model voldev")
+    if args.n is None:
+        args.n = 84 if args.overlay else 100
     if args.jacobian and (not args.route or (args.model or ["voldev"]) != ["voldev"]):
         raise SystemExit("--jacobian goes with --route general lattice and model voldev")
     route_spectral = bool(args.route) and args.model == ["spectral"]  # (--route without --model: model 3, as before)
@@ -73,6 +86,8 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("bench_split3d needs the GPU: nothing is measured without it")
+    if args.overlay:
+        return bench_jacobian_overlay(args, capi, M, Assembler, O)
     n = args.n
     mesh = M.box_mesh(3, n, lo=0.0, hi=float(n))
     blocked = args.layout == "blocked"
@@ -273,6 +288,85 @@ def bench_jacobian(args, asm, capi, mesh, prm_off, prm_on, states, old):
     if "lattice" in med:
         rec["lattice_over_unsplit"] = med["lattice"] / med["unsplit"]
         rec["lattice_tension_over_unsplit"] = med["lattice_tension"] / med["unsplit"]
+    if "lattice" in med and "general" in med:
+        rec["lattice_over_general"] = med["lattice"] / med["general"]
+        rec["lattice_below_general_in_every_round"] = all(np.median(l) < np.median(g) for l, g in zip(ts["lattice"], ts["general"]))
+    print(json.dumps(rec))
+
+
+def bench_jacobian_overlay(args, capi, M, Assembler, O):
+    """--jacobian --overlay: full-assembly arms on the overlay context (kernel path 3), alternating round by round"""
+    n = args.n
+    g0 = M.box_mesh(3, (n,) * 3)  # bench.py: overlay_3d
+    cc = g0.coords[g0.cells].mean(axis=1)
+    mesh = M.refine_cells(g0, (np.abs(cc) < 5.0).all(axis=1))
+    blocked = args.layout == "blocked"
+    lay = M.DofLayout(mesh.n_nodes, 3, blocked=blocked)
+    ch = M.hanging_constraints(mesh, lay)
+    rng = np.random.default_rng(0)
+    h = 20.0 / n / 2  # the edge of a refined cell
+    dev_grad = 1e-2 * np.array([[0.9, 0.7, -0.3], [0.1, -0.8, 0.5], [0.4, -0.2, -0.1]])  # trace 0: the noise decides the sign
+    noise = rng.uniform(-2e-4 * h, 2e-4 * h, (mesh.n_nodes, 3))
+    sol = ch.distribute(lay.pack(mesh.coords @ dev_grad.T + noise, rng.uniform(0.3, 0.9, mesh.n_nodes)))
+    old = ch.distribute(lay.pack(np.zeros((mesh.n_nodes, 3)), rng.uniform(0.3, 0.9, mesh.n_nodes)))
+    base = dict(mu=80.77, G_c=2.7, alpha_eps=0.5, constant_k=1e-3, pressure=0.05, timestep=1e-3, time=2e-3, old_timestep=1e-3,
+                old_old_timestep=1e-3, timestep_number=1)
+    prm_off = O.make_params(**{"lambda": 121.15}, **base)
+    prm_on = O.make_params(**{"lambda": 121.15}, decompose_stress_rhs=1.0, decompose_stress_matrix=1.0, **base)
+    asm = Assembler(mesh, blocked)
+    asm.split_model = capi.SPLIT_VOLDEV
+    asm.set_constraints(np.zeros(mesh.n_nodes, np.uint8))
+    asm.set_vectors(sol, old, old)
+    asm.allocate_matrix()
+    rows, general_cells = asm.ctx.overlay_info()
+    assert asm.ctx.kernel_path == 3 and rows > 0
+    routes = {"general": capi.SPLIT_ROUTE_GENERAL, "lattice": capi.SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS}
+    arms = list(dict.fromkeys(args.route)) + ["unsplit"]
+
+    def configure(arm):
+        asm.split_route = routes.get(arm, capi.SPLIT_ROUTE_GENERAL)
+        asm.set_params(prm_on if arm in routes else prm_off)
+        assert asm.ctx.kernel_path == 3 and asm.ctx.split_route_plan()[2] == int(arm == "lattice")
+
+    def timed(arm):
+        configure(arm)
+        for _ in range(args.warmup):
+            asm.assemble_system(False)
+        asm.synchronize()
+        asm.ctx.timing_enable(True)
+        for _ in range(args.reps):
+            asm.assemble_system(False)
+        asm.synchronize()
+        ts = asm.ctx.kernel_times_ms()
+        asm.ctx.timing_enable(False)
+        assert ts.size == args.reps
+        return ts
+
+    outs, compressed = {}, {}
+    for arm in [a for a in arms if a in routes]:
+        configure(arm)
+        asm.assemble_system(False)
+        asm.synchronize()
+        compressed[arm] = asm.ctx.split_route_plan()[3]
+        outs[arm] = [m.clone() for m in asm.system_pde_matrix] + [asm.system_pde_residual.clone()]
+    rec = {"metric": "split3d_routes_jacobian_overlay", "cells": int(mesh.n_cells), "nodes": int(mesh.n_nodes), "hanging_nodes": int(mesh.hn_nodes.size),
+           "regular_rows": int(rows), "regular_row_fraction": rows / mesh.n_nodes, "cells_left_to_the_general_family": int(general_cells),
+           "layout": args.layout, "reps": args.reps, "rounds": args.rounds, "arms": arms,
+           "cells_with_a_compressed_q_point_among_those_of_the_level_kernels": {k: v for k, v in compressed.items() if v >= 0}}
+    if len(outs) == 2:
+        rec["lattice_deviation_from_general"] = max(float((a - b).abs().max() / max(1.0, float(b.abs().max())))
+                                                    for a, b in zip(outs["lattice"], outs["general"]))
+    del outs
+    ts = {arm: [] for arm in arms}
+    for _ in range(args.rounds):
+        for arm in arms:
+            ts[arm].append(timed(arm))
+    med = {arm: float(np.median(np.concatenate(ts[arm]))) for arm in arms}
+    for arm in arms:
+        rec[arm] = {"ms": med[arm], "min_ms": float(np.concatenate(ts[arm]).min()), "round_medians_ms": [float(np.median(t)) for t in ts[arm]],
+                    "ms_per_1e6_cells": med[arm] * 1e6 / mesh.n_cells}
+    if "lattice" in med:
+        rec["lattice_over_unsplit"] = med["lattice"] / med["unsplit"]
     if "lattice" in med and "general" in med:
         rec["lattice_over_general"] = med["lattice"] / med["general"]
         rec["lattice_below_general_in_every_round"] = all(np.median(l) < np.median(g) for l, g in zip(ts["lattice"], ts["general"]))
