@@ -126,7 +126,10 @@ class Context:
         box or a partitioned sub-box on the row-owner kernels as well (k_cart_split3_jac; not on the level lattices of an overlay,
         not under model 1); 4 and 6 are refused.  13 (= 5 | 8) and 15 (= 7 | 8): the same, and the level lattices of a 3-D overlay take
         that full assembly too (level form of k_cart_split3_jac; regular rows then have residual_pde of the full and of the
-        residual-only call bit for bit equal); every other value with bit 8 is refused.  At any time on a living context; routes 0, 1 and 3 have no effect on full
+        residual-only call bit for bit equal); every other value with bit 8 is refused.  21 (= 5 | 16) and 23 (= 7 | 16): routes 5 and 7 with the full assembly of a
+        box or sub-box evaluating the law only where it differs from the unsplit one (k_cart_split3_mark, the unsplit k_cart_uu3
+        and k_cart_phi4 over the whole box, then the sparse form of k_cart_split3_jac over the rows at compressed cells: those rows
+        are route 5's bytes, the others the unsplit kernels'); every other value with bit 16 is refused.  At any time on a living context; routes 0, 1 and 3 have no effect on full
         assemblies."""
         self._check(self.lib.pfm_set_split_route(self._h, int(route)), "pfm_set_split_route")
         self.split_route = int(route)
@@ -144,6 +147,14 @@ class Context:
         pfm_ctx_split_route_info, answered from the assembly plan.  split_route_info() keeps its two answers."""
         out = (C.c_int64 * 4)(-1, -1, -1, -1)
         self._check(self.lib.pfm_ctx_split_route_info(self._h, out), "pfm_ctx_split_route_info")
+        return tuple(int(x) for x in out)
+
+    def split_sparse_info(self):
+        """(whether a full assembly with the current parameters, model, route and forced path would run sparse, nodes whose
+        rows the sparse form of k_cart_split3_jac recomputed in the last full assembly or -1 if that one did not run sparse,
+        tile-chunks flagged in it or -1, tile-chunks of the grid): pfm_ctx_split_sparse_info."""
+        out = (C.c_int64 * 4)(-1, -1, -1, -1)
+        self._check(self.lib.pfm_ctx_split_sparse_info(self._h, out), "pfm_ctx_split_sparse_info")
         return tuple(int(x) for x in out)
 
     def set_hanging_mode(self, mode: int):

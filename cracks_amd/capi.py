@@ -22,12 +22,13 @@ SPLIT_REFERENCE, SPLIT_SPECTRAL, SPLIT_VOLDEV = 0, 1, 3  # pfm_set_split_model (
 SPLIT_ROUTE_GENERAL, SPLIT_ROUTE_LATTICE, SPLIT_ROUTE_LATTICE_ANY = 0, 1, 3  # pfm_set_split_route (2 is unassigned)
 SPLIT_ROUTE_LATTICE_JACOBIAN, SPLIT_ROUTE_LATTICE_ALL = 5, 7  # ... | 4: the full assembly of model 3 on the row-owner kernels too (4, 6 refused)
 SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS, SPLIT_ROUTE_LATTICE_ALL_LEVELS = 13, 15  # ... | 8: the level lattices of a 3-D overlay take that full assembly too (8-12, 14 refused)
+SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE, SPLIT_ROUTE_LATTICE_ALL_SPARSE = 21, 23  # 5 | 16, 7 | 16: that full assembly evaluates the law only at compressed cells (every other value with bit 16 refused)
 HANGING_MODE_DEFAULT, HANGING_MODE_GATHER, HANGING_MODE_ATOMIC = 0, 1, 2  # pfm_set_hanging_mode
 
 # every symbol include/pfm_assemble.h declares
 EXPORTS = [
     "pfm_ctx_create", "pfm_ctx_destroy", "pfm_last_error", "pfm_ctx_set_stream", "pfm_set_params", "pfm_set_split_model",
-    "pfm_set_split_route", "pfm_ctx_split_route", "pfm_ctx_split_route_info", "pfm_set_hanging_mode", "pfm_ctx_hanging_info",
+    "pfm_set_split_route", "pfm_ctx_split_route", "pfm_ctx_split_route_info", "pfm_ctx_split_sparse_info", "pfm_set_hanging_mode", "pfm_ctx_hanging_info",
     "pfm_set_constraints", "pfm_pattern_size", "pfm_pattern_get", "pfm_pattern_bind", "pfm_pattern_bind_i32",
     "pfm_state_set", "pfm_state_set_solution", "pfm_comm_unique_id", "pfm_comm_create", "pfm_comm_wrap", "pfm_comm_destroy", "pfm_comm_aborted", "pfm_comm_info", "pfm_halo_exchange", "pfm_assemble_overlapped",
     "pfm_check_finite",
@@ -138,6 +139,8 @@ def load():
     lib.pfm_ctx_split_route.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     if hasattr(lib, "pfm_ctx_split_route_info"):  # (PFM_LIB may name an older build in an A/B run)
         lib.pfm_ctx_split_route_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    if hasattr(lib, "pfm_ctx_split_sparse_info"):  # (likewise)
+        lib.pfm_ctx_split_sparse_info.argtypes = [vp, C.POINTER(C.c_int64)]
     if hasattr(lib, "pfm_set_hanging_mode"):  # (PFM_LIB may name an older build in an A/B run: calling them there raises)
         lib.pfm_set_hanging_mode.argtypes = [vp, i32]
         lib.pfm_ctx_hanging_info.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_int64)]

@@ -1710,7 +1710,7 @@ namespace pfm
   // phase-field kernel of the pair, or under PFM_SIDE_STREAM for the residual kernel: both only read the node state), else s.
   int launch_assemble_cart(const CartPlan &pl, const DevView &v, const CartView &cv_in, const pfm_params &p, double *const *d_values,
                            double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock,
-                           int *n_compressed)
+                           int *n_compressed, const SplitSparse *sparse)
   {
     using ResidualKernel = void (*)(DevView, CartView, Scal, double *, double *, int, int);
     static const ResidualKernel residual_kernel[5][2] = {{nullptr, nullptr}, // by CartResidual and its flag: every instantiation there is
@@ -1747,7 +1747,28 @@ namespace pfm
     if (pl.voldev_jac) // the matrix values of the law (pfm_cart_split3.hip): whole, in phase 0 and in the second half
       {
         cv.tile_sel = 0;
-        return pl.split3_jac() ? launch_cart_split3_jac(pl, v, cv, p, d_values, n_compressed, s) : PFM_OK;
+        if (!pl.split3_jac())
+          return PFM_OK;
+        if (!pl.voldev_sparse)
+          return launch_cart_split3_jac(pl, v, cv, p, d_values, n_compressed, s);
+        // CartPlan::voldev_sparse: the law only where it differs from the unsplit one.  The mark kernel, then the unsplit
+        // Jacobian kernels over the whole box -- the plan of the same parameters with decompose_stress_matrix = 0, in the
+        // form that writes no residual rows and does not pair, k_cart_phi4 with its (u,u) diagonal patches on s -- then the
+        // sparse form of k_cart_split3_jac over the rows at compressed cells, all on s.
+        if (!sparse || !n_compressed)
+          return PFM_ERR_INTERNAL;
+        int rc = launch_cart_split3_mark(pl, v, cv, p, *sparse, n_compressed, s);
+        pfm_params p0 = p;
+        p0.decompose_stress_matrix = 0.0;
+        CartPlan un = plan_cart(v, cv, p0, 0, 0, cart_n_cu());
+        un.rows_residual = un.pair = false; // (the residual kernel has written residual_pde)
+        if (rc == PFM_OK && !(un.uu3() && un.phi4()))
+          rc = PFM_ERR_INTERNAL;
+        if (rc == PFM_OK)
+          rc = launch_cart_uu3(un, v, cv, p0, d_values[0], s, nullptr, clock);
+        if (rc == PFM_OK)
+          rc = launch_cart_phi4(un, v, cv, d_values, s, d_scal, nullptr, clock);
+        return rc == PFM_OK ? launch_cart_split3_jac(pl, v, cv, p, d_values, n_compressed, s, sparse) : rc;
       }
     double *const res_rows = pl.rows_residual ? res_pde : nullptr;
     cv.tile_sel = pl.tile_sel(PFM_ZC_UU3);

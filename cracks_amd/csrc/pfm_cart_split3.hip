@@ -22,6 +22,14 @@
 //   (CartView::row_of_box; -1: the lane passes the node by), slots come from the overlay's nbr_mask / row_perm, Lame
 //   coefficients and cell sizes are the level's.  The box instantiations are the parent's instruction for instruction.
 //
+//   SPARSE FORM (PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE / _ALL_SPARSE; CartPlan::voldev_sparse): the law is the unsplit law wherever
+//   tr E >= 0, and a row depends on the (up to) eight cells of its node alone.  k_cart_split3_mark writes one byte per lattice
+//   cell (1: a q-point of the cell is compressed, by sj_line_setup / sj_trace / split3::voldev, the statements of the rows),
+//   flags the tile-chunks that own a vertex of such a cell and counts the cells; the unsplit k_cart_uu3 and k_cart_phi4 write
+//   every row (launch_assemble_cart, pfm_cart.hip); k_cart_split3_jac<NCOL, false, true> then writes the rows of the nodes at
+//   compressed cells again, by the same sj_row calls: those rows are the bytes of the plain form, every other row is the
+//   unsplit kernels'.  No compaction pass, no host read-back, no floating-point atomics.
+//
 // Tiles: those of k_cart_uu3 (T3X x T3Y owned nodes, z-chunks of CartPlan::grid[PFM_ZC_UU3]); a workgroup is one wave, its 64
 // lanes two node planes of the tile, marching up its chunk two planes at a time.
 #include "pfm_internal.h"
@@ -303,6 +311,14 @@ namespace pfm
       int *n_compressed;                             // cells with a compressed q-point, counted by the owner of their vertex 0
       int zc;
     };
+    // what the SPARSE form (CartPlan::voldev_sparse) takes on top, written by k_cart_split3_mark in front of its launch -- an
+    // argument of its own: the kernel arguments of the plain instantiations are the parent's byte for byte
+    struct SjSparseArgs
+    {
+      const uint8_t *cell_comp; // [(NX-1)(NY-1)(NZ-1)] lattice cell order: 1 = the cell has a compressed q-point
+      const int *tile_flag;     // [ntx nty nch] of grid[PFM_ZC_UU3]: 1 = the tile-chunk owns a vertex of such a cell
+      int *n_rows;              // nodes whose four rows this launch recomputed
+    };
 
     // One row of the node at (gi, gj, gk): COMP < 3 the displacement row (node, COMP) with its three (u,u) columns per slot,
     // COMP == 3 the phase-field row with (phi,u) and (phi,phi).  NCOL: 3 blocked, 4 interleaved.
@@ -498,6 +514,102 @@ namespace pfm
         }
     }
 
+    // SPARSE: is the node a vertex of a cell whose byte k_cart_split3_mark set?  Cells outside the lattice read as 0.
+    __device__ __forceinline__ bool sj_node_touched(const CartView &cv, const uint8_t *cell_comp, int gi, int gj, int gk)
+    {
+      bool any = false;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        {
+          const int ci = gi - 1 + (e & 1), cj = gj - 1 + ((e >> 1) & 1), ck = gk - 1 + (e >> 2);
+          if (ci >= 0 && ci < cv.NX - 1 && cj >= 0 && cj < cv.NY - 1 && ck >= 0 && ck < cv.NZ - 1)
+            any = any || cell_comp[ci + (long long)(cv.NX - 1) * (cj + (long long)(cv.NY - 1) * ck)] != 0;
+        }
+      return any;
+    }
+
+    // k_cart_split3_mark (CartPlan::voldev_sparse): lane <-> lattice cell, over the cells that touch an owned row -- the cell
+    // range [o0 - 1, o1] of the owned box, cut to the lattice.  tr E at the 27 q-points by the statements of the rows above
+    // (sj_line_setup, sj_trace, split3::voldev: the sign is the same source statement on the same operands); only the
+    // displacements enter.  One byte per cell: 1 = some q-point has h = 0.  Such a cell sets the flag of every tile-chunk of
+    // grid[PFM_ZC_UU3] that holds one of its owned vertices (plain int stores of 1: order-independent) and is counted by the
+    // rule of sj_row: the cell whose lowest vertex is a row of this rank, ballot + one integer atomic per wave.
+    struct SmArgs
+    {
+      DevView v;
+      CartView cv;
+      double ih[3], lam, mu;
+      uint8_t *cell_comp;
+      int *tile_flag, *n_compressed;
+      int c0[3], cn[3]; // first cell and cells per axis of the launch
+      int ntx, nty, zc; // tile-chunks of grid[PFM_ZC_UU3]
+    };
+    constexpr int SM_NT = 256;
+    __global__ __launch_bounds__(SM_NT) void k_cart_split3_mark(SmArgs A)
+    {
+      const CartView &cv = A.cv;
+      const long long id = (long long)blockIdx.x * SM_NT + threadIdx.x, n = (long long)A.cn[0] * A.cn[1] * A.cn[2];
+      const bool in = id < n;
+      bool compressed = false, counted = false;
+      if (in)
+        {
+          const int ci = A.c0[0] + (int)(id % A.cn[0]), cj = A.c0[1] + (int)(id / A.cn[0] % A.cn[1]), ck = A.c0[2] + (int)(id / ((long long)A.cn[0] * A.cn[1]));
+          const long long cidx = ci + (long long)(cv.NX - 1) * (cj + (long long)(cv.NY - 1) * ck);
+          double lam = A.lam, mu = A.mu;
+          if (cv.cell_lam)
+            {
+              lam = cv.cell_lam[cidx];
+              mu = cv.cell_mu[cidx];
+            }
+          double U[6][8];
+#pragma unroll
+          for (int b = 0; b < 8; ++b)
+            {
+              const int nd = sj_local_id(cv, ci + (b & 1), cj + ((b >> 1) & 1), ck + (b >> 2));
+              const bool has = nd >= 0;
+              U[0][b] = has ? A.v.u[0][nd] : 0.0;
+              U[1][b] = has ? A.v.u[1][nd] : 0.0;
+              U[2][b] = has ? A.v.u[2][nd] : 0.0;
+              U[3][b] = U[4][b] = U[5][b] = 0.0; // (the phase fields do not enter the trace)
+            }
+#pragma unroll 1
+          for (int p = 0; p < 9; ++p)
+            {
+              const double eta = sj_gx(p % 3), zeta = sj_gx(p / 3);
+              SjLine ln;
+              sj_line_setup(U, eta, zeta, A.ih, ln);
+#pragma unroll 1
+              for (int qx = 0; qx < 3; ++qx)
+                {
+                  double g00, g11, g22;
+                  const double trE = sj_trace(ln, sj_gx(qx), g00, g11, g22);
+                  const split3::VolDev V = split3::voldev(trE, lam, mu);
+                  compressed = compressed || V.h == 0.0;
+                }
+            }
+          A.cell_comp[cidx] = compressed ? 1 : 0;
+          if (compressed)
+            {
+              const int nch_z = (cv.o1[2] - cv.o0[2] + A.zc) / A.zc;
+#pragma unroll
+              for (int b = 0; b < 8; ++b)
+                {
+                  const int i = ci + (b & 1) - cv.o0[0], j = cj + ((b >> 1) & 1) - cv.o0[1], k = ck + (b >> 2) - cv.o0[2];
+                  if (i >= 0 && i <= cv.o1[0] - cv.o0[0] && j >= 0 && j <= cv.o1[1] - cv.o0[1] && k >= 0 && k <= cv.o1[2] - cv.o0[2] && k / A.zc < nch_z)
+                    A.tile_flag[i / T3X + A.ntx * (j / T3Y + A.nty * (k / A.zc))] = 1;
+                }
+              if (ci >= cv.o0[0] && ci <= cv.o1[0] && cj >= cv.o0[1] && cj <= cv.o1[1] && ck >= cv.o0[2] && ck <= cv.o1[2])
+                {
+                  const int row = sj_local_id(cv, ci, cj, ck);
+                  counted = row >= 0 && row < A.v.n_owned;
+                }
+            }
+        }
+      const unsigned long long m = __ballot(counted);
+      if (m != 0ull && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1))
+        atomicAdd(A.n_compressed, (int)__popcll(m));
+    }
+
     constexpr int SJ_NT = 64; // one wave: T3X x T3Y nodes of two planes
     static_assert(T3X * T3Y * 2 == SJ_NT, "two node planes of a k_cart_uu3 tile per wave");
 
@@ -546,28 +658,107 @@ namespace pfm
           sj_row<3, NCOL>(A, gi, gj, gk, row, row_flag);
         }
     }
+
+    // SPARSE form (CartPlan::voldev_sparse, PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE / _ALL_SPARSE; a box, never a level lattice), a
+    // second template of the same name with an argument of its own: the unsplit kernels have written every row, and this
+    // launch writes again the rows of the nodes that are a vertex of a cell with a compressed q-point (SjSparseArgs::cell_comp),
+    // by the same sj_row calls -- the same bytes as the plain form.  A workgroup whose tile-chunk has no such node
+    // (SjSparseArgs::tile_flag) returns at once, a lane passes every other node by.  It always runs whole (tile_sel 0: no
+    // list of boundary tiles, no skipped tile).  The plain kernel above is left as it was, statement for statement: its four
+    // instantiations are the parent's instruction for instruction, which sharing its body with this one did not give.
+    template <int NCOL, bool LEVEL, bool SPARSE>
+    __global__ __launch_bounds__(SJ_NT) void k_cart_split3_jac(SjArgs A, SjSparseArgs X)
+    {
+      static_assert(SPARSE && !LEVEL, "the sparse form of a box");
+      const CartView &cv = A.cv;
+      const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
+      const int ntx = (OWX + T3X - 1) / T3X, nty = (OWY + T3Y - 1) / T3Y;
+      const int zc = A.zc, nch = (OWZ + zc - 1) / zc;
+      const int bid = (int)((blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3)); // XCD-aware launch, pfm_internal.h
+      if (bid >= ntx * nty * nch)
+        return; // padding of the XCD-aware grid
+      if (X.tile_flag[bid] == 0)
+        return; // no node of this tile-chunk touches a compressed cell: its rows stay the unsplit kernels'
+      const int tix = bid % ntx, tiy = (bid / ntx) % nty, chunk = bid / (ntx * nty);
+      const int i0 = cv.o0[0] + tix * T3X, j0 = cv.o0[1] + tiy * T3Y;
+      const int kA = cv.o0[2] + chunk * zc, kB = min(kA + zc, cv.o1[2] + 1); // node planes [kA, kB)
+      const int t = threadIdx.x, gi = i0 + t % T3X, gj = j0 + (t / T3X) % T3Y;
+      if (gi > cv.o1[0] || gj > cv.o1[1])
+        return; // partial tile (no barrier anywhere: a lane may leave)
+#pragma unroll 1
+      for (int gk = kA + t / (T3X * T3Y); gk < kB; gk += 2)
+        {
+          const int row = sj_local_id(cv, gi, gj, gk); // an owned node of the box: its row
+          const bool touched = row >= 0 && row < A.v.n_owned && sj_node_touched(cv, X.cell_comp, gi, gj, gk);
+          const unsigned long long m = __ballot(touched);
+          if (m != 0ull && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1))
+            atomicAdd(X.n_rows, (int)__popcll(m));
+          if (!touched)
+            continue;
+          const unsigned row_flag = A.v.node_flags[row];
+          sj_row<0, NCOL>(A, gi, gj, gk, row, row_flag);
+          sj_row<1, NCOL>(A, gi, gj, gk, row, row_flag);
+          sj_row<2, NCOL>(A, gi, gj, gk, row, row_flag);
+          sj_row<3, NCOL>(A, gi, gj, gk, row, row_flag);
+        }
+    }
   } // namespace
 
   // The matrix values of pl = plan_cart(...) with CartPlan::voldev_jac: every block, whole (phase 0) or in the second half.
   // n_compressed (device, may be nullptr): zeroed by the caller; gets the number of cells with a compressed q-point.
+  // sparse (CartPlan::voldev_sparse): the buffers k_cart_split3_mark has filled; the count is that kernel's.
   int launch_cart_split3_jac(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
-                             int *n_compressed, hipStream_t s)
+                             int *n_compressed, hipStream_t s, const SplitSparse *sparse)
   {
-    if (!pl.split3_jac())
+    if (!pl.split3_jac() || (pl.voldev_sparse != (sparse != nullptr)))
       return PFM_ERR_UNSUPPORTED;
     const TileGrid &g = pl.grid[PFM_ZC_UU3];
     if (g.n_tiles == 0)
       return PFM_OK;
     const bool il = pl.interleaved; // one block of values
     SjArgs ka{v, cv, make_sj_scal(p, cv), d_values[0], il ? nullptr : d_values[1], il ? nullptr : d_values[2], il ? nullptr : d_values[3],
-              n_compressed, g.zc};
+              sparse ? nullptr : n_compressed, g.zc};
     const bool level = cv.row_of_box != nullptr;
-    if (level && (!cv.nbr_mask || !cv.row_perm || cv.owned_lex))
+    if (level && (!cv.nbr_mask || !cv.row_perm || cv.owned_lex || sparse))
       return PFM_ERR_INTERNAL; // (the overlay's row tables: ensure_overlay3_ready)
     using Kernel = void (*)(SjArgs);
     static const Kernel kernel[2][2] = {{k_cart_split3_jac<3, false>, k_cart_split3_jac<3, true>}, // by layout and LEVEL
                                         {k_cart_split3_jac<4, false>, k_cart_split3_jac<4, true>}};
-    hipLaunchKernelGGL(kernel[il][level], dim3(xcd_grid(g.n_tiles)), dim3(SJ_NT), 0, s, ka);
+    using SparseKernel = void (*)(SjArgs, SjSparseArgs);
+    static const SparseKernel kernel_sparse[2] = {k_cart_split3_jac<3, false, true>, k_cart_split3_jac<4, false, true>};
+    if (sparse)
+      hipLaunchKernelGGL(kernel_sparse[il], dim3(xcd_grid(g.n_tiles)), dim3(SJ_NT), 0, s, ka, SjSparseArgs{sparse->cell_comp, sparse->tile_flag, sparse->n_rows});
+    else
+      hipLaunchKernelGGL(kernel[il][level], dim3(xcd_grid(g.n_tiles)), dim3(SJ_NT), 0, s, ka);
+    return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
+  }
+
+  // CartPlan::voldev_sparse, in front of the unsplit kernels: the cell bytes, the tile-chunk flags of pl.grid[PFM_ZC_UU3] and
+  // the count of the compressed cells (all zeroed by the caller)
+  int launch_cart_split3_mark(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, const SplitSparse &sparse,
+                              int *n_compressed, hipStream_t s)
+  {
+    if (!pl.split3_jac() || !pl.voldev_sparse || cv.row_of_box || !n_compressed)
+      return PFM_ERR_UNSUPPORTED;
+    const TileGrid &g = pl.grid[PFM_ZC_UU3];
+    if (g.n_tiles == 0)
+      return PFM_OK;
+    const int N[3] = {cv.NX, cv.NY, cv.NZ};
+    SmArgs ka{};
+    ka.v = v, ka.cv = cv, ka.lam = p.lambda, ka.mu = p.mu;
+    ka.cell_comp = sparse.cell_comp, ka.tile_flag = sparse.tile_flag, ka.n_compressed = n_compressed;
+    ka.ntx = g.ntx, ka.nty = g.nty, ka.zc = g.zc;
+    long long n = 1;
+    for (int d = 0; d < 3; ++d)
+      {
+        ka.ih[d] = 1.0 / cv.h[d]; // (make_sj_scal's statement)
+        ka.c0[d] = std::max(cv.o0[d] - 1, 0);
+        ka.cn[d] = std::min(cv.o1[d], N[d] - 2) - ka.c0[d] + 1;
+        if (ka.cn[d] <= 0)
+          return PFM_OK; // no cell
+        n *= ka.cn[d];
+      }
+    hipLaunchKernelGGL(k_cart_split3_mark, dim3((unsigned)((n + SM_NT - 1) / SM_NT)), dim3(SM_NT), 0, s, ka);
     return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
   }
 } // namespace pfm

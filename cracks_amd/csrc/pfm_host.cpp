@@ -1410,7 +1410,8 @@ extern "C"
   {
     if (!c || (route != PFM_SPLIT_ROUTE_GENERAL && route != PFM_SPLIT_ROUTE_LATTICE && route != PFM_SPLIT_ROUTE_LATTICE_ANY &&
                route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN && route != PFM_SPLIT_ROUTE_LATTICE_ALL &&
-               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS && route != PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS))
+               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS && route != PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS &&
+               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE && route != PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE))
       return c ? fail(c, PFM_ERR_BAD_ARG, "unknown split route") : PFM_ERR_BAD_ARG;
     if (route != PFM_SPLIT_ROUTE_GENERAL && c->v.dim != 3)
       return fail(c, PFM_ERR_UNSUPPORTED, "the lattice routes carry the 3-D split laws");
@@ -2540,6 +2541,53 @@ extern "C"
     return PFM_OK;
   }
 
+  // CartPlan::voldev_sparse: the cell bytes, the tile-chunk flags of grid[PFM_ZC_UU3] and the row counter, made on first use
+  // (grow-only) and emptied on the context's stream in front of k_cart_split3_mark
+  static int sparse_reserve(pfm_ctx *c, pfm::DevBuf &b, size_t bytes, const char *what)
+  {
+    if (b.p && b.bytes >= bytes)
+      return PFM_OK;
+    if (b.p) // (a longer lattice of flags after pfm_ctx_force_zchunk) queued work may still use the old buffer
+      {
+        (void)hipStreamSynchronize(c->stream);
+        c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), b.p), c->allocs.end());
+        (void)hipFree(b.p);
+        c->device_bytes -= (int64_t)b.bytes;
+        b = pfm::DevBuf{};
+      }
+    bytes = std::max<size_t>(bytes, 256);
+    if (hipMalloc(&b.p, bytes) != hipSuccess)
+      {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return fail(c, PFM_ERR_NOMEM, what);
+      }
+    c->allocs.push_back(b.p);
+    b.bytes = bytes;
+    c->device_bytes += (int64_t)bytes;
+    return PFM_OK;
+  }
+  static int sparse_buffers(pfm_ctx *c, const CartPlan &pl, pfm::SplitSparse &sp)
+  {
+    const pfm::CartView &cv = c->cv;
+    const TileGrid &g = pl.grid[PFM_ZC_UU3];
+    const size_t n_cells = (size_t)std::max(cv.NX - 1, 0) * (size_t)std::max(cv.NY - 1, 0) * (size_t)std::max(cv.NZ - 1, 0);
+    const size_t n_tiles = (size_t)g.ntx * g.nty * g.nch;
+    if (const int rc = sparse_reserve(c, c->buf_sparse_cells, n_cells, "cell bytes of the sparse split Jacobian"))
+      return rc;
+    if (const int rc = sparse_reserve(c, c->buf_sparse_flags, n_tiles * sizeof(int), "tile-chunk flags of the sparse split Jacobian"))
+      return rc;
+    if (const int rc = sparse_reserve(c, c->buf_sparse_rows, sizeof(int), "row counter of the sparse split Jacobian"))
+      return rc;
+    sp = {c->buf_sparse_cells.as<uint8_t>(), c->buf_sparse_flags.as<int>(), c->buf_sparse_rows.as<int>()};
+    if ((n_cells && hipMemsetAsync(sp.cell_comp, 0, n_cells, c->stream) != hipSuccess) ||
+        (n_tiles && hipMemsetAsync(sp.tile_flag, 0, n_tiles * sizeof(int), c->stream) != hipSuccess) ||
+        hipMemsetAsync(sp.n_rows, 0, sizeof(int), c->stream) != hipSuccess)
+      return fail(c, PFM_ERR_HIP, "sparse split Jacobian: buffer reset");
+    c->sparse_tiles = (int64_t)n_tiles;
+    return PFM_OK;
+  }
+
   // Two statuses, here and in launch_levels / gather_hanging: the return value ends the call at once (its text is set);
   // `rc` (in/out) is the status of the launches, which assemble_impl reports behind the joins and the closing event.
   // cartesian box, 2-D / 3-D: the pair with its deferred placeholder patches, the fork, the fill of the (u,phi) block
@@ -2571,10 +2619,17 @@ extern "C"
     if (p.box.voldev_jac) // counted by the kernel of the (whole or second-half) launch
       if (const int rcc = compressed_counter(c, p.box.split3_jac(), n_compressed))
         return rcc;
+    pfm::SplitSparse sparse{};
+    const bool run_sparse = p.box.voldev_sparse && p.box.split3_jac();
+    if (run_sparse)
+      if (const int rcs = sparse_buffers(c, p.box, sparse))
+        return rcs;
     rc = launch_assemble_cart(p.box, c->v, cv, c->prm, d_values, d_res_pde, d_res_tot, c->stream, p.fork ? c->side_stream : c->stream,
-                              c->d_scal, &c->clock, n_compressed);
+                              c->d_scal, &c->clock, n_compressed, run_sparse ? &sparse : nullptr);
     if (p.box.split3_jac())
       c->compressed_valid = rc == PFM_OK;
+    if (run_sparse)
+      c->sparse_valid = rc == PFM_OK;
     if (p.fork)
       if (const int rcj = join_from(c, c->side_stream, c->stream, c->ev_join, "join"))
         return rcj;
@@ -2746,6 +2801,8 @@ extern "C"
     AssemblyPlan plan = plan_assembly(c, residual_only, phase, d_values);
     if (!residual_only && phase != 1 && !(plan.cart && plan.box.voldev_jac) && !(plan.overlay3 && plan.level.voldev_jac))
       c->compressed_valid = false; // pfm_ctx_split_route_info: the count belongs to the last full assembly
+    if (!residual_only && phase != 1 && !(plan.cart && plan.box.voldev_sparse))
+      c->sparse_valid = false; // pfm_ctx_split_sparse_info: likewise
     bool gather_ready = false;
     if (const int rct = ensure_tables(c, plan, gather_ready))
       return rct;
@@ -3188,6 +3245,39 @@ extern "C"
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, c->buf_compressed.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
           return PFM_ERR_HIP;
         out[3] = n;
+      }
+    return PFM_OK;
+  }
+
+  int pfm_ctx_split_sparse_info(const pfm_ctx *c, int64_t out[4])
+  {
+    if (!c || !out)
+      return PFM_ERR_BAD_ARG;
+    out[0] = 0, out[1] = -1, out[2] = -1, out[3] = 0;
+    if (c->have_params)
+      {
+        // the plan of such an assembly, not a second copy of its conditions
+        double *const no_values[4] = {nullptr, nullptr, nullptr, nullptr};
+        const AssemblyPlan p = plan_assembly(c, 0, 0, no_values);
+        if (p.cart && p.box.voldev_sparse)
+          {
+            const TileGrid &g = p.box.grid[PFM_ZC_UU3];
+            out[0] = 1;
+            out[3] = (int64_t)g.ntx * g.nty * g.nch;
+          }
+      }
+    if (c->sparse_valid && c->buf_sparse_rows.p && c->buf_sparse_flags.p)
+      {
+        int n = 0;
+        std::vector<int> flags((size_t)c->sparse_tiles);
+        (void)hipSetDevice(c->device);
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, c->buf_sparse_rows.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+            (!flags.empty() && hipMemcpy(flags.data(), c->buf_sparse_flags.p, flags.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+          return PFM_ERR_HIP;
+        out[1] = n;
+        out[2] = 0;
+        for (const int f : flags)
+          out[2] += f != 0;
       }
     return PFM_OK;
   }

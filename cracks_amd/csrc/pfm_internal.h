@@ -173,12 +173,23 @@ namespace pfm
   // d_scal: the MatScal of the current parameters on the device (upload_mat_scal; by value it would pin 900 bytes of
   // SGPRs in k_cart_phi4).  clock: the context's counters, for a plan that clocks a kernel.
   struct CartPlan;
+  // CartPlan::voldev_sparse: the context's buffers of one sparse full assembly, zeroed by the caller in front of it
+  struct SplitSparse
+  {
+    uint8_t *cell_comp; // [(NX-1)(NY-1)(NZ-1)] one byte per lattice cell: 1 = a q-point of the cell is compressed (k_cart_split3_mark)
+    int *tile_flag;     // [ntx nty nch of grid[PFM_ZC_UU3]] 1 = the tile-chunk owns a vertex of such a cell
+    int *n_rows;        // nodes whose rows the sparse form of k_cart_split3_jac recomputed
+  };
   int launch_assemble_cart(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
                            double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock,
-                           int *n_compressed = nullptr /* CartPlan::voldev_jac: device counter, zeroed by the caller */);
-  // pfm_cart_split3.hip: the matrix values of a CartPlan::voldev_jac assembly
+                           int *n_compressed = nullptr /* CartPlan::voldev_jac: device counter, zeroed by the caller */,
+                           const SplitSparse *sparse = nullptr /* CartPlan::voldev_sparse */);
+  // pfm_cart_split3.hip: the matrix values of a CartPlan::voldev_jac assembly (sparse: its rows at compressed cells alone,
+  // behind launch_cart_split3_mark and the unsplit kernels)
   int launch_cart_split3_jac(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
-                             int *n_compressed, hipStream_t s);
+                             int *n_compressed, hipStream_t s, const SplitSparse *sparse = nullptr);
+  int launch_cart_split3_mark(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, const SplitSparse &sparse,
+                              int *n_compressed, hipStream_t s);
   int launch_cart2d(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
                     double *res_pde, double *res_tot, hipStream_t s);
   int launch_cart_uu3(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *vals_uu, hipStream_t s,
@@ -287,6 +298,11 @@ struct pfm_ctx
   int split_route = 0; // PFM_SPLIT_ROUTE_*: pfm_set_split_route
   pfm::DevBuf buf_compressed;     // CartPlan::voldev_jac: cells with a compressed q-point, counted by k_cart_split3_jac (one int)
   bool compressed_valid = false;  // ... of the last full assembly, which ran on that kernel (pfm_ctx_split_route_info)
+  // CartPlan::voldev_sparse: cell bytes, tile-chunk flags and the row counter of k_cart_split3_mark / the sparse form of
+  // k_cart_split3_jac (made on first use, emptied in front of every sparse assembly); pfm_ctx_split_sparse_info
+  pfm::DevBuf buf_sparse_cells, buf_sparse_flags, buf_sparse_rows;
+  int64_t sparse_tiles = 0;       // tile-chunks of the last sparse full assembly (entries of buf_sparse_flags in use)
+  bool sparse_valid = false;      // the last full assembly ran sparse
   int n_blocks = 1;
   int kernel_path = 0;
   int force_phase = 0; // pfm_ctx_force_phase (measurement)

@@ -154,6 +154,10 @@ namespace pfm_glue_detail
     //                      PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS (= 5 | 8) and PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS (= 7 | 8): the
     //                      level lattices of a refined 3-D mesh take that full assembly too; on their regular rows the two
     //                      residuals are the same bytes, on the rows of the general family equal to rounding.
+    //                      PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE (= 5 | 16) and PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE (= 7 | 16): the
+    //                      full assembly of a box or sub-box evaluates the law only at the rows next to compressed cells and
+    //                      takes every other row from the unsplit Jacobian kernels -- for runs that are in tension almost
+    //                      everywhere (slower than route 5 where about half of the cells are compressed).
     //   hanging_mode:      PFM_HANGING_MODE_GATHER sends the cells at hanging vertices through per-cell scratch and an ordered
     //                      gather instead of atomic adds, in 2-D and under every 3-D law: two assemble() calls of the same state
     //                      then give the same bytes (pfm_set_hanging_mode; forwarded next to split_route).  Default

@@ -195,6 +195,39 @@ int pfm_set_split_model(pfm_ctx *ctx, int model);
  *   PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS  (= 1 | 2 | 4 | 8) the same with the residual-only calls of
  *                            PFM_SPLIT_ROUTE_LATTICE_ANY.  Every other value with bit 8 (8, 9, 10, 11, 12, 14) is refused
  *                            with PFM_ERR_BAD_ARG.
+ *   PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE  (= 1 | 4 | 16) PFM_SPLIT_ROUTE_LATTICE_JACOBIAN with the law evaluated only where
+ *                            it differs from the unsplit one.  Under PFM_SPLIT_VOLDEV the law is the unsplit law wherever
+ *                            tr E >= 0 (h = 1: the tangent weight is lambda g, sigma+ = sigma).  The FULL assembly of a 3-D box
+ *                            or partitioned sub-box becomes, on the context's stream: residual_pde from
+ *                            k_cart_residual3<false, true> exactly as under route 5; k_cart_split3_mark, a lane per lattice
+ *                            cell, writes one byte per cell (1: some q-point has h(tr E) = 0, by the trace statement of
+ *                            k_cart_split3_jac), flags the tile-chunks that own a vertex of such a cell and counts them;
+ *                            the unsplit k_cart_uu3 and k_cart_phi4 (the plan of the same parameters with
+ *                            decompose_stress_matrix = 0, no residual rows, not paired) write every row; the sparse form
+ *                            of k_cart_split3_jac leaves a tile-chunk without a flag at once, passes by every node none of
+ *                            whose (up to) eight cells has its byte set, and writes the four rows of the other nodes again
+ *                            as under route 5.  No compaction pass, no host read-back.  In an overlapped assembly all of
+ *                            this but the residual kernel runs whole in the second half.  PROMISED: a row of a node that
+ *                            is a vertex of a local cell with a q-point where the device's tr E < 0 holds, in all four
+ *                            blocks, the bytes of route 5 on the same context and state, for any z-chunk length; every
+ *                            other row holds what those unsplit kernels wrote; residual_pde is route 5's bytes (and the
+ *                            residual-only call's); the assembly is bitwise reproducible run to run and on a fresh
+ *                            context; the (u,phi) block holds exact zeros.  NOT PROMISED: the bytes of the untouched rows
+ *                            against an unsplit assembly that runs other instantiations (the pair with residual rows:
+ *                            equal to rounding), against the general route, or between a box and its sub-boxes (to
+ *                            rounding); and, as everywhere under this law, where tr E is zero up to rounding the matrix is
+ *                            not determined.  Residual-only calls are those of route 5 bit for bit.  Under model 0 or 1,
+ *                            with the split off, on path 0 and on the level lattices of an overlay the route acts as route
+ *                            5 does (an overlay context keeps the general family for its full assembly).  COST: the
+ *                            route pays the unsplit kernels and the mark kernel everywhere and the split kernel where
+ *                            cells are compressed.  Measured per full assembly at 1e6 hexes against route 5's 10.2 ms
+ *                            (profiles/split_lattice_jacobian_sparse/README.md): 1.34 ms with no compressed cell, 4.92 ms
+ *                            with a slab of 5 % of the cells compressed, below route 5 in every round -- and 11.49 ms,
+ *                            1.13 times route 5 and above it in every round, where nearly every cell has a compressed
+ *                            q-point: on such a state it is SLOWER than route 5.
+ *   PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE  (= 1 | 2 | 4 | 16) the same with the residual-only calls of
+ *                            PFM_SPLIT_ROUTE_LATTICE_ANY.  Every other value with bit 16 (16-20, 22, 24-31: bit 16 without
+ *                            the Jacobian route, or together with bit 8) is refused with PFM_ERR_BAD_ARG.
  * May be called at any time on a living context: the next assembly follows it.  An unknown route: PFM_ERR_BAD_ARG.
  * Any route but PFM_SPLIT_ROUTE_GENERAL on a 2-D context: PFM_ERR_UNSUPPORTED.  PFM_SPLIT_ROUTE_LATTICE with model 0 or 1 is
  * accepted and has no effect.
@@ -207,7 +240,13 @@ int pfm_set_split_model(pfm_ctx *ctx, int model);
  * one compressed q-point, h(tr E) = 0, as counted by k_cart_split3_jac in the last full assembly of this context -- -1 when
  * that assembly did not run on that kernel or none has run.  On a 3-D overlay under the _LEVELS routes out[2] is 1 and
  * out[3] covers the cells of the level kernels only: the cells whose lowest vertex is a regular row, summed over the levels
- * (the cells of the general family are not counted).  Reading out[3] waits for the context's stream. */
+ * (the cells of the general family are not counted).  Reading out[3] waits for the context's stream.  Under the _SPARSE
+ * routes out[2] is 1 and out[3] is the count of k_cart_split3_mark: on any state the number route 5 reports.
+ * pfm_ctx_split_sparse_info: out[0] whether a full assembly with the current parameters, model, route and forced path would
+ * run sparse (0 before pfm_set_params); out[1] the nodes whose rows the sparse form of k_cart_split3_jac recomputed in the
+ * last full assembly of this context, -1 when that one did not run sparse or none has run; out[2] the tile-chunks flagged
+ * in that assembly (-1 likewise); out[3] the tile-chunks of the grid (of the plan of out[0]; 0 when out[0] is 0).  Reading
+ * out[1] and out[2] waits for the context's stream. */
 enum
 {
   PFM_SPLIT_ROUTE_GENERAL = 0,
@@ -216,11 +255,14 @@ enum
   PFM_SPLIT_ROUTE_LATTICE_JACOBIAN = 5,
   PFM_SPLIT_ROUTE_LATTICE_ALL = 7,
   PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS = 13,
-  PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS = 15
+  PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS = 15,
+  PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE = 21,
+  PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE = 23
 };
 int pfm_set_split_route(pfm_ctx *ctx, int route);
 int pfm_ctx_split_route(const pfm_ctx *ctx, int *route, int *lattice_residual);
 int pfm_ctx_split_route_info(const pfm_ctx *ctx, int64_t out[4]);
+int pfm_ctx_split_sparse_info(const pfm_ctx *ctx, int64_t out[4]);
 /* How the cells at hanging vertices of a general mesh (2-D or 3-D, with or without a cartesian overlay) reach the outputs.
  *   PFM_HANGING_MODE_DEFAULT  what every context did before this call existed, bit for bit: 3-D unsplit and model 3 write
  *                             K' = C^T K C, R' = C^T R and their placeholder diagonals to per-cell scratch, and an ordered

@@ -40,6 +40,14 @@ cells with the full colour lists -- and "lattice" is PFM_SPLIT_ROUTE_LATTICE_JAC
 k_cart_split3_jac + k_cart_residual3<false, true> on the regular rows of both level lattices, the general family over the cells
 that touch any other row.  "unsplit" is the unsplit overlay assembly of the same context (the yardstick).  The arms alternate
 round by round in one process; the state is the deviatoric gradient plus noise, hanging nodes interpolated.
+
+--jacobian --route lattice sparse --model voldev --compressed {tension,slab,half} times PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE
+("sparse": k_cart_split3_mark, the unsplit k_cart_uu3 + k_cart_phi4, the sparse form of k_cart_split3_jac) next to its two
+yardsticks on the same state -- "lattice", route 5, and "unsplit", the full assembly with the split off -- alternating round
+by round in one process.  The states: "tension" (a dilation plus noise: no compressed cell), "slab" (the same with the node
+planes z <= 5 h compressed: about 5 % of the cells of the default box) and "half" (the deviatoric gradient plus noise of the
+run above: about half of the cells).  The record carries the compressed cells, the rows the split kernel recomputed, the
+flagged tile-chunks and whether the sparse arm's round median is below route 5's in every round.
 """
 import argparse
 import json
@@ -62,12 +70,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="off / on alternations; the medians of all rounds are reported")
     ap.add_argument("--layout", choices=["blocked", "interleaved"], default="blocked")
     ap.add_argument("--model", choices=["spectral", "voldev"], nargs="+", default=None, help="the split law(s) to time (default: spectral)")
-    ap.add_argument("--route", choices=["general", "lattice"], nargs="+", default=None,
+    ap.add_argument("--route", choices=["general", "lattice", "sparse"], nargs="+", default=None,
                     help="time the residual-only assembly of model 3 (--model spectral: of model 1) per split route on the box context "
                          "instead (see above)")
     ap.add_argument("--jacobian", action="store_true", help="with --route: time the full assembly of model 3 per route (see above)")
     ap.add_argument("--overlay", action="store_true", help="with --jacobian: on the block-refined mesh of bench.py's overlay_3d (see above)")
+    ap.add_argument("--compressed", choices=["tension", "slab", "half"], default=None,
+                    help="with --jacobian --route lattice sparse: the state the sparse route is timed on (see above)")
     args = ap.parse_args()
+    if ("sparse" in (args.route or [])) != (args.compressed is not None) or (args.compressed and (not args.jacobian or args.overlay)):
+        raise SystemExit("--compressed goes with --jacobian --route lattice sparse --model voldev")
     if args.overlay and not args.jacobian:
         raise SystemExit("--overlay goes with --jacobian --route general lattice --model voldev")
     if args.n is None:
@@ -116,6 +128,12 @@ def main():
     if args.jacobian:
         dev_grad = 1e-2 * np.array([[0.9, 0.7, -0.3], [0.1, -0.8, 0.5], [0.4, -0.2, -0.1]])  # trace 0: the noise decides the sign
         mixed = lay.pack(mesh.coords @ dev_grad.T + noise, phi)
+        if args.compressed:
+            u = 1e-2 * mesh.coords + noise
+            low = mesh.coords[:, 2] <= 5.0  # unit cells: the five cell layers below z = 5 are compressed by 1e-2
+            u[low] -= 2e-2 * mesh.coords[low]
+            state = {"tension": tension, "slab": lay.pack(u, phi), "half": mixed}[args.compressed]
+            return bench_jacobian_sparse(args, asm, capi, mesh, prm_off, prm_on, state, old)
         return bench_jacobian(args, asm, capi, mesh, prm_off, prm_on, {"mixed": mixed, "tension": tension}, old)
     if args.route:
         return bench_routes(args, asm, capi, mesh, prm_off, prm_on, O.make_params(**{"lambda": 121.15}, outer_solver=1, gamma_penal=1e-2, **base),
@@ -292,6 +310,68 @@ def bench_jacobian(args, asm, capi, mesh, prm_off, prm_on, states, old):
         rec["lattice_over_general"] = med["lattice"] / med["general"]
         rec["lattice_below_general_in_every_round"] = all(np.median(l) < np.median(g) for l, g in zip(ts["lattice"], ts["general"]))
     print(json.dumps(rec))
+
+
+def bench_jacobian_sparse(args, asm, capi, mesh, prm_off, prm_on, state, old):
+    """--jacobian --route lattice sparse --compressed: route 21 next to route 5 and the unsplit assembly on one state"""
+    routes = {"lattice": capi.SPLIT_ROUTE_LATTICE_JACOBIAN, "sparse": capi.SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE}
+    arms = ["lattice", "sparse", "unsplit"]
+    asm.split_model = capi.SPLIT_VOLDEV
+    asm.set_vectors(state, old, old)
+
+    def configure(arm):
+        asm.split_route = routes.get(arm, capi.SPLIT_ROUTE_GENERAL)
+        asm.set_params(prm_on if arm in routes else prm_off)
+        assert asm.ctx.kernel_path == 1 and asm.ctx.split_route_plan()[2] == int(arm in routes) and asm.ctx.split_sparse_info()[0] == int(arm == "sparse")
+
+    def timed(arm):
+        configure(arm)
+        for _ in range(args.warmup):
+            asm.assemble_system(False)
+        asm.synchronize()
+        asm.ctx.timing_enable(True)
+        for _ in range(args.reps):
+            asm.assemble_system(False)
+        asm.synchronize()
+        ts = asm.ctx.kernel_times_ms()
+        asm.ctx.timing_enable(False)
+        assert ts.size == args.reps
+        return ts
+
+    outs, compressed = {}, {}
+    for arm in routes:
+        configure(arm)
+        asm.assemble_system(False)
+        asm.synchronize()
+        compressed[arm] = asm.ctx.split_route_plan()[3]
+        outs[arm] = [m.clone() for m in asm.system_pde_matrix] + [asm.system_pde_residual.clone()]
+    info = asm.ctx.split_sparse_info()
+    rec = {"metric": "split3d_routes_jacobian_sparse", "state": args.compressed, "cells": int(mesh.n_cells), "nodes": int(mesh.n_nodes),
+           "layout": args.layout, "reps": args.reps, "rounds": args.rounds, "arms": arms, "cells_with_a_compressed_q_point": compressed,
+           "compressed_cell_fraction": compressed["sparse"] / mesh.n_cells, "rows_recomputed": info[1], "rows_recomputed_fraction": info[1] / mesh.n_nodes,
+           "tile_chunks_flagged": info[2], "tile_chunks": info[3],
+           "sparse_deviation_from_lattice": max(float((a - b).abs().max() / max(1.0, float(b.abs().max()))) for a, b in zip(outs["sparse"], outs["lattice"])),
+           "residual_pde_same_bytes": bool(torch_equal(outs["sparse"][-1], outs["lattice"][-1]))}
+    del outs
+    ts = {arm: [] for arm in arms}
+    for _ in range(args.rounds):
+        for arm in arms:
+            ts[arm].append(timed(arm))
+    med = {arm: float(np.median(np.concatenate(ts[arm]))) for arm in arms}
+    for arm in arms:
+        rec[arm] = {"ms": med[arm], "min_ms": float(np.concatenate(ts[arm]).min()), "round_medians_ms": [float(np.median(t)) for t in ts[arm]],
+                    "ms_per_1e6_cells": med[arm] * 1e6 / mesh.n_cells}
+    rec["sparse_over_lattice"] = med["sparse"] / med["lattice"]
+    rec["sparse_over_unsplit"] = med["sparse"] / med["unsplit"]
+    rec["lattice_over_unsplit"] = med["lattice"] / med["unsplit"]
+    rec["sparse_below_lattice_in_every_round"] = all(np.median(a) < np.median(b) for a, b in zip(ts["sparse"], ts["lattice"]))
+    print(json.dumps(rec))
+
+
+def torch_equal(a, b):
+    import torch
+
+    return torch.equal(a, b)
 
 
 def bench_jacobian_overlay(args, capi, M, Assembler, O):
