@@ -129,7 +129,11 @@ class Context:
         residual-only call bit for bit equal); every other value with bit 8 is refused.  21 (= 5 | 16) and 23 (= 7 | 16): routes 5 and 7 with the full assembly of a
         box or sub-box evaluating the law only where it differs from the unsplit one (k_cart_split3_mark, the unsplit k_cart_uu3
         and k_cart_phi4 over the whole box, then the sparse form of k_cart_split3_jac over the rows at compressed cells: those rows
-        are route 5's bytes, the others the unsplit kernels'); every other value with bit 16 is refused.  At any time on a living context; routes 0, 1 and 3 have no effect on full
+        are route 5's bytes, the others the unsplit kernels'); every other value with bit 16 is refused.  61 (= 13 | 16 | 32) and
+        63 (= 15 | 16 | 32): routes 13 and 15 with that sparse full assembly on every level lattice of a 3-D overlay (the level forms
+        of k_cart_split3_mark and of the sparse k_cart_split3_jac around the unsplit level kernels: the regular rows at compressed
+        cells are route 13's bytes, the other regular rows the unsplit level kernels', the general family as under 13); on a
+        box they are 21 and 23; every other value with bit 32 is refused.  At any time on a living context; routes 0, 1 and 3 have no effect on full
         assemblies."""
         self._check(self.lib.pfm_set_split_route(self._h, int(route)), "pfm_set_split_route")
         self.split_route = int(route)
@@ -152,7 +156,8 @@ class Context:
     def split_sparse_info(self):
         """(whether a full assembly with the current parameters, model, route and forced path would run sparse, nodes whose
         rows the sparse form of k_cart_split3_jac recomputed in the last full assembly or -1 if that one did not run sparse,
-        tile-chunks flagged in it or -1, tile-chunks of the grid): pfm_ctx_split_sparse_info."""
+        tile-chunks flagged in it or -1, tile-chunks of the grid): pfm_ctx_split_sparse_info.  On a 3-D overlay under routes 61 /
+        63 the rows, flags and tile-chunks are summed over the level lattices."""
         out = (C.c_int64 * 4)(-1, -1, -1, -1)
         self._check(self.lib.pfm_ctx_split_sparse_info(self._h, out), "pfm_ctx_split_sparse_info")
         return tuple(int(x) for x in out)
@@ -714,8 +719,9 @@ class Assembler:
     def split_route(self) -> int:
         """Where the residual-only assembly of a 3-D mesh under a split law runs (Context.set_split_route): 0 the general
         family, 1 the row-owner kernels of the lattice under model 3, 3 under models 1 and 3; 5 and 7: the same, and the full
-        assembly of model 3 on the row-owner kernels too; 13 and 15: also on the level lattices of a 3-D overlay.  May change at any
-        time."""
+        assembly of model 3 on the row-owner kernels too; 13 and 15: also on the level lattices of a 3-D overlay; 21 and 23: 5 and 7 with
+        the law evaluated only at compressed cells (boxes); 61 and 63: 13 and 15 likewise, on the level lattices too.  May change at
+        any time."""
         return self.ctx.split_route
 
     @split_route.setter

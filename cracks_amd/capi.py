@@ -23,6 +23,7 @@ SPLIT_ROUTE_GENERAL, SPLIT_ROUTE_LATTICE, SPLIT_ROUTE_LATTICE_ANY = 0, 1, 3  # p
 SPLIT_ROUTE_LATTICE_JACOBIAN, SPLIT_ROUTE_LATTICE_ALL = 5, 7  # ... | 4: the full assembly of model 3 on the row-owner kernels too (4, 6 refused)
 SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS, SPLIT_ROUTE_LATTICE_ALL_LEVELS = 13, 15  # ... | 8: the level lattices of a 3-D overlay take that full assembly too (8-12, 14 refused)
 SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE, SPLIT_ROUTE_LATTICE_ALL_SPARSE = 21, 23  # 5 | 16, 7 | 16: that full assembly evaluates the law only at compressed cells (every other value with bit 16 refused)
+SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE, SPLIT_ROUTE_LATTICE_ALL_LEVELS_SPARSE = 61, 63  # 13 | 16 | 32, 15 | 16 | 32: the same on the level lattices of a 3-D overlay too (every other value with bit 32 refused)
 HANGING_MODE_DEFAULT, HANGING_MODE_GATHER, HANGING_MODE_ATOMIC = 0, 1, 2  # pfm_set_hanging_mode
 
 # every symbol include/pfm_assemble.h declares

@@ -1569,7 +1569,9 @@ namespace pfm
                   const int fe_nbo = (fe_o9 % 3 - 1) + PH * (fe_o9 / 3 - 1); // halo offset of the neighbour node
                   double *src = (fe_oz == 0) ? (fe_pp ? pp_m1 : pu_m1) : (fe_oz == 1 ? (fe_pp ? pp_z0 : pu_z0) : (fe_pp ? pp_p1 : pu_p1));
                   src += fe_src;
-                  if (fast)
+                  // (interleaved: a tile-plane of a level lattice none of whose nodes is a row of this launch leaves
+                  // s.irregular at 0 -- every s.off is -1 there, and this path has no guard: s.incomplete sends it below)
+                  if (fast && (NCOL == 3 || regular_or_permuted))
                     {
                       // interleaved layout, interior plane: free of control flow so that the LDS reads of several
                       // rows are in flight together

@@ -112,10 +112,12 @@ namespace pfm
     // false for every scheme.  On a level lattice of the 3-D overlay (CartView::row_of_box) only with bit 8 of the route
     // (PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS, _ALL_LEVELS): k_cart_split3_jac<NCOL, true> over grid[PFM_ZC_UU3] of that level.
     bool voldev_jac = false;
-    // ... with bit 16 of the route (PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE, _ALL_SPARSE) on a box, not on a level lattice: the
+    // ... with bit 16 of the route (PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE, _ALL_SPARSE) on a box: the
     // law only where it differs from the unsplit one.  k_cart_split3_mark finds the cells with a compressed q-point, the
     // unsplit k_cart_uu3 and k_cart_phi4 write every row, the sparse form of k_cart_split3_jac writes the rows at those cells
     // again (launch_assemble_cart).  In every other field the plan is the voldev_jac plan of the route without the bit.
+    // On a level lattice only with bits 8, 16 and 32 (PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE, _ALL_LEVELS_SPARSE): the same
+    // sequence with the level forms of the mark kernel and of the sparse kernel, per level.
     bool voldev_sparse = false;
     bool linear = false, interleaved = false, het = false; // scheme; layout; per-cell Lame coefficients (CartView::cell_lam)
     // Full 3-D assembly, linear scheme: every residual row is an exact function of its own matrix row (R_u = pressure part -
@@ -161,7 +163,7 @@ namespace pfm
     pl.spectral = lattice_law && split.model == PFM_SPLIT_SPECTRAL && res_route == PFM_SPLIT_ROUTE_LATTICE_ANY;
     pl.voldev_jac = sc.split && v.dim == 3 && !pl.residual_only && split.model == PFM_SPLIT_VOLDEV && (split.route & 4) != 0 &&
                     (split.route & PFM_SPLIT_ROUTE_LATTICE) != 0 && (!cv.row_of_box || (split.route & 8) != 0);
-    pl.voldev_sparse = pl.voldev_jac && (split.route & 16) != 0 && !cv.row_of_box;
+    pl.voldev_sparse = pl.voldev_jac && (split.route & 16) != 0 && (!cv.row_of_box || (split.route & 32) != 0);
     pl.supported = (!sc.split || pl.voldev || pl.spectral || pl.voldev_jac) && (v.dim == 2 || v.dim == 3);
     if (!pl.supported)
       return pl;

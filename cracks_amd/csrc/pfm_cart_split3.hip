@@ -30,6 +30,12 @@
 //   compressed cells again, by the same sj_row calls: those rows are the bytes of the plain form, every other row is the
 //   unsplit kernels'.  No compaction pass, no host read-back, no floating-point atomics.
 //
+//   SPARSE LEVEL FORM (PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE / _ALL_LEVELS_SPARSE; voldev_sparse on a lattice with
+//   CartView::row_of_box): both of the above on one level lattice of a 3-D overlay.  k_cart_split3_mark<true> takes the cells
+//   whose eight vertices all exist on the level, flags the tile-chunks that own a regular row among them and counts by the rule
+//   of the level form; the unsplit level kernels write every regular row; k_cart_split3_jac<NCOL, true, true> writes the regular
+//   rows at compressed cells again: the bytes of the level form.
+//
 // Tiles: those of k_cart_uu3 (T3X x T3Y owned nodes, z-chunks of CartPlan::grid[PFM_ZC_UU3]); a workgroup is one wave, its 64
 // lanes two node planes of the tile, marching up its chunk two planes at a time.
 #include "pfm_internal.h"
@@ -544,7 +550,11 @@ namespace pfm
       int c0[3], cn[3]; // first cell and cells per axis of the launch
       int ntx, nty, zc; // tile-chunks of grid[PFM_ZC_UU3]
     };
+    // LEVEL: cv is a level lattice of a 3-D overlay.  A cell takes part only if all of its eight vertices exist on the level
+    // (local_of_box >= 0: every cell of a regular row does); the owned vertices are the regular rows (row_of_box), and the
+    // count is that of the level form of k_cart_split3_jac: the cell whose lowest vertex is a regular row of this rank.
     constexpr int SM_NT = 256;
+    template <bool LEVEL>
     __global__ __launch_bounds__(SM_NT) void k_cart_split3_mark(SmArgs A)
     {
       const CartView &cv = A.cv;
@@ -562,18 +572,20 @@ namespace pfm
               mu = cv.cell_mu[cidx];
             }
           double U[6][8];
+          bool whole = true;
 #pragma unroll
           for (int b = 0; b < 8; ++b)
             {
               const int nd = sj_local_id(cv, ci + (b & 1), cj + ((b >> 1) & 1), ck + (b >> 2));
               const bool has = nd >= 0;
+              whole = whole && has;
               U[0][b] = has ? A.v.u[0][nd] : 0.0;
               U[1][b] = has ? A.v.u[1][nd] : 0.0;
               U[2][b] = has ? A.v.u[2][nd] : 0.0;
               U[3][b] = U[4][b] = U[5][b] = 0.0; // (the phase fields do not enter the trace)
             }
 #pragma unroll 1
-          for (int p = 0; p < 9; ++p)
+          for (int p = 0; p < (LEVEL && !whole ? 0 : 9); ++p)
             {
               const double eta = sj_gx(p % 3), zeta = sj_gx(p / 3);
               SjLine ln;
@@ -596,11 +608,19 @@ namespace pfm
                 {
                   const int i = ci + (b & 1) - cv.o0[0], j = cj + ((b >> 1) & 1) - cv.o0[1], k = ck + (b >> 2) - cv.o0[2];
                   if (i >= 0 && i <= cv.o1[0] - cv.o0[0] && j >= 0 && j <= cv.o1[1] - cv.o0[1] && k >= 0 && k <= cv.o1[2] - cv.o0[2] && k / A.zc < nch_z)
-                    A.tile_flag[i / T3X + A.ntx * (j / T3Y + A.nty * (k / A.zc))] = 1;
+                    {
+                      if constexpr (LEVEL)
+                        {
+                          const int row = cv.row_of_box[(ci + (b & 1)) + (long long)cv.NX * ((cj + ((b >> 1) & 1)) + (long long)cv.NY * (ck + (b >> 2)))];
+                          if (row < 0 || row >= A.v.n_owned)
+                            continue; // no row of this launch
+                        }
+                      A.tile_flag[i / T3X + A.ntx * (j / T3Y + A.nty * (k / A.zc))] = 1;
+                    }
                 }
               if (ci >= cv.o0[0] && ci <= cv.o1[0] && cj >= cv.o0[1] && cj <= cv.o1[1] && ck >= cv.o0[2] && ck <= cv.o1[2])
                 {
-                  const int row = sj_local_id(cv, ci, cj, ck);
+                  const int row = LEVEL ? cv.row_of_box[ci + (long long)cv.NX * (cj + (long long)cv.NY * ck)] : sj_local_id(cv, ci, cj, ck);
                   counted = row >= 0 && row < A.v.n_owned;
                 }
             }
@@ -659,7 +679,8 @@ namespace pfm
         }
     }
 
-    // SPARSE form (CartPlan::voldev_sparse, PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE / _ALL_SPARSE; a box, never a level lattice), a
+    // SPARSE form (CartPlan::voldev_sparse, PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE / _ALL_SPARSE; LEVEL: on a level lattice,
+    // PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE / _ALL_LEVELS_SPARSE, the rows of the launch are those of row_of_box as above), a
     // second template of the same name with an argument of its own: the unsplit kernels have written every row, and this
     // launch writes again the rows of the nodes that are a vertex of a cell with a compressed q-point (SjSparseArgs::cell_comp),
     // by the same sj_row calls -- the same bytes as the plain form.  A workgroup whose tile-chunk has no such node
@@ -669,7 +690,7 @@ namespace pfm
     template <int NCOL, bool LEVEL, bool SPARSE>
     __global__ __launch_bounds__(SJ_NT) void k_cart_split3_jac(SjArgs A, SjSparseArgs X)
     {
-      static_assert(SPARSE && !LEVEL, "the sparse form of a box");
+      static_assert(SPARSE, "the sparse form");
       const CartView &cv = A.cv;
       const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
       const int ntx = (OWX + T3X - 1) / T3X, nty = (OWY + T3Y - 1) / T3Y;
@@ -688,7 +709,8 @@ namespace pfm
 #pragma unroll 1
       for (int gk = kA + t / (T3X * T3Y); gk < kB; gk += 2)
         {
-          const int row = sj_local_id(cv, gi, gj, gk); // an owned node of the box: its row
+          const int row = LEVEL ? cv.row_of_box[gi + (long long)cv.NX * (gj + (long long)cv.NY * gk)] // a regular row of this level, or -1
+                                : sj_local_id(cv, gi, gj, gk);                                       // an owned node of the box: its row
           const bool touched = row >= 0 && row < A.v.n_owned && sj_node_touched(cv, X.cell_comp, gi, gj, gk);
           const unsigned long long m = __ballot(touched);
           if (m != 0ull && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1))
@@ -719,15 +741,16 @@ namespace pfm
     SjArgs ka{v, cv, make_sj_scal(p, cv), d_values[0], il ? nullptr : d_values[1], il ? nullptr : d_values[2], il ? nullptr : d_values[3],
               sparse ? nullptr : n_compressed, g.zc};
     const bool level = cv.row_of_box != nullptr;
-    if (level && (!cv.nbr_mask || !cv.row_perm || cv.owned_lex || sparse))
+    if (level && (!cv.nbr_mask || !cv.row_perm || cv.owned_lex))
       return PFM_ERR_INTERNAL; // (the overlay's row tables: ensure_overlay3_ready)
     using Kernel = void (*)(SjArgs);
     static const Kernel kernel[2][2] = {{k_cart_split3_jac<3, false>, k_cart_split3_jac<3, true>}, // by layout and LEVEL
                                         {k_cart_split3_jac<4, false>, k_cart_split3_jac<4, true>}};
     using SparseKernel = void (*)(SjArgs, SjSparseArgs);
-    static const SparseKernel kernel_sparse[2] = {k_cart_split3_jac<3, false, true>, k_cart_split3_jac<4, false, true>};
+    static const SparseKernel kernel_sparse[2][2] = {{k_cart_split3_jac<3, false, true>, k_cart_split3_jac<3, true, true>},
+                                                     {k_cart_split3_jac<4, false, true>, k_cart_split3_jac<4, true, true>}};
     if (sparse)
-      hipLaunchKernelGGL(kernel_sparse[il], dim3(xcd_grid(g.n_tiles)), dim3(SJ_NT), 0, s, ka, SjSparseArgs{sparse->cell_comp, sparse->tile_flag, sparse->n_rows});
+      hipLaunchKernelGGL(kernel_sparse[il][level], dim3(xcd_grid(g.n_tiles)), dim3(SJ_NT), 0, s, ka, SjSparseArgs{sparse->cell_comp, sparse->tile_flag, sparse->n_rows});
     else
       hipLaunchKernelGGL(kernel[il][level], dim3(xcd_grid(g.n_tiles)), dim3(SJ_NT), 0, s, ka);
     return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
@@ -738,7 +761,7 @@ namespace pfm
   int launch_cart_split3_mark(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, const SplitSparse &sparse,
                               int *n_compressed, hipStream_t s)
   {
-    if (!pl.split3_jac() || !pl.voldev_sparse || cv.row_of_box || !n_compressed)
+    if (!pl.split3_jac() || !pl.voldev_sparse || !n_compressed)
       return PFM_ERR_UNSUPPORTED;
     const TileGrid &g = pl.grid[PFM_ZC_UU3];
     if (g.n_tiles == 0)
@@ -758,7 +781,7 @@ namespace pfm
           return PFM_OK; // no cell
         n *= ka.cn[d];
       }
-    hipLaunchKernelGGL(k_cart_split3_mark, dim3((unsigned)((n + SM_NT - 1) / SM_NT)), dim3(SM_NT), 0, s, ka);
+    hipLaunchKernelGGL(cv.row_of_box ? k_cart_split3_mark<true> : k_cart_split3_mark<false>, dim3((unsigned)((n + SM_NT - 1) / SM_NT)), dim3(SM_NT), 0, s, ka);
     return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
   }
 } // namespace pfm

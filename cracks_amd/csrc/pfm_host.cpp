@@ -1411,7 +1411,8 @@ extern "C"
     if (!c || (route != PFM_SPLIT_ROUTE_GENERAL && route != PFM_SPLIT_ROUTE_LATTICE && route != PFM_SPLIT_ROUTE_LATTICE_ANY &&
                route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN && route != PFM_SPLIT_ROUTE_LATTICE_ALL &&
                route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS && route != PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS &&
-               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE && route != PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE))
+               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE && route != PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE &&
+               route != PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE && route != PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS_SPARSE))
       return c ? fail(c, PFM_ERR_BAD_ARG, "unknown split route") : PFM_ERR_BAD_ARG;
     if (route != PFM_SPLIT_ROUTE_GENERAL && c->v.dim != 3)
       return fail(c, PFM_ERR_UNSUPPORTED, "the lattice routes carry the 3-D split laws");
@@ -2567,24 +2568,29 @@ extern "C"
     c->device_bytes += (int64_t)bytes;
     return PFM_OK;
   }
-  static int sparse_buffers(pfm_ctx *c, const CartPlan &pl, pfm::SplitSparse &sp)
+  // the row counter: one for the box, one for all level lattices of an overlay (emptied once, on the context's stream)
+  static int sparse_row_counter(pfm_ctx *c)
   {
-    const pfm::CartView &cv = c->cv;
+    if (const int rc = sparse_reserve(c, c->buf_sparse_rows, sizeof(int), "row counter of the sparse split Jacobian"))
+      return rc;
+    return hipMemsetAsync(c->buf_sparse_rows.p, 0, sizeof(int), c->stream) == hipSuccess ? PFM_OK : fail(c, PFM_ERR_HIP, "sparse split Jacobian: counter reset");
+  }
+  // the cell bytes and tile-chunk flags of lattice cv (the box, or one level lattice with buffers of its own), emptied on s
+  static int sparse_buffers(pfm_ctx *c, const pfm::CartView &cv, const CartPlan &pl, pfm::DevBuf &cells, pfm::DevBuf &flags, int64_t &tiles,
+                            hipStream_t s, pfm::SplitSparse &sp)
+  {
     const TileGrid &g = pl.grid[PFM_ZC_UU3];
     const size_t n_cells = (size_t)std::max(cv.NX - 1, 0) * (size_t)std::max(cv.NY - 1, 0) * (size_t)std::max(cv.NZ - 1, 0);
     const size_t n_tiles = (size_t)g.ntx * g.nty * g.nch;
-    if (const int rc = sparse_reserve(c, c->buf_sparse_cells, n_cells, "cell bytes of the sparse split Jacobian"))
+    if (const int rc = sparse_reserve(c, cells, n_cells, "cell bytes of the sparse split Jacobian"))
       return rc;
-    if (const int rc = sparse_reserve(c, c->buf_sparse_flags, n_tiles * sizeof(int), "tile-chunk flags of the sparse split Jacobian"))
+    if (const int rc = sparse_reserve(c, flags, n_tiles * sizeof(int), "tile-chunk flags of the sparse split Jacobian"))
       return rc;
-    if (const int rc = sparse_reserve(c, c->buf_sparse_rows, sizeof(int), "row counter of the sparse split Jacobian"))
-      return rc;
-    sp = {c->buf_sparse_cells.as<uint8_t>(), c->buf_sparse_flags.as<int>(), c->buf_sparse_rows.as<int>()};
-    if ((n_cells && hipMemsetAsync(sp.cell_comp, 0, n_cells, c->stream) != hipSuccess) ||
-        (n_tiles && hipMemsetAsync(sp.tile_flag, 0, n_tiles * sizeof(int), c->stream) != hipSuccess) ||
-        hipMemsetAsync(sp.n_rows, 0, sizeof(int), c->stream) != hipSuccess)
+    sp = {cells.as<uint8_t>(), flags.as<int>(), c->buf_sparse_rows.as<int>()};
+    if ((n_cells && hipMemsetAsync(sp.cell_comp, 0, n_cells, s) != hipSuccess) ||
+        (n_tiles && hipMemsetAsync(sp.tile_flag, 0, n_tiles * sizeof(int), s) != hipSuccess))
       return fail(c, PFM_ERR_HIP, "sparse split Jacobian: buffer reset");
-    c->sparse_tiles = (int64_t)n_tiles;
+    tiles = (int64_t)n_tiles;
     return PFM_OK;
   }
 
@@ -2622,14 +2628,18 @@ extern "C"
     pfm::SplitSparse sparse{};
     const bool run_sparse = p.box.voldev_sparse && p.box.split3_jac();
     if (run_sparse)
-      if (const int rcs = sparse_buffers(c, p.box, sparse))
-        return rcs;
+      {
+        if (const int rcs = sparse_row_counter(c))
+          return rcs;
+        if (const int rcs = sparse_buffers(c, c->cv, p.box, c->buf_sparse_cells, c->buf_sparse_flags, c->sparse_tiles, c->stream, sparse))
+          return rcs;
+      }
     rc = launch_assemble_cart(p.box, c->v, cv, c->prm, d_values, d_res_pde, d_res_tot, c->stream, p.fork ? c->side_stream : c->stream,
                               c->d_scal, &c->clock, n_compressed, run_sparse ? &sparse : nullptr);
     if (p.box.split3_jac())
       c->compressed_valid = rc == PFM_OK;
     if (run_sparse)
-      c->sparse_valid = rc == PFM_OK;
+      c->sparse_valid = rc == PFM_OK, c->sparse_levels = false;
     if (p.fork)
       if (const int rcj = join_from(c, c->side_stream, c->stream, c->ev_join, "join"))
         return rcj;
@@ -2684,6 +2694,10 @@ extern "C"
     if (p.level.voldev_jac)
       if (const int rcc = compressed_counter(c, true, n_compressed))
         return rcc;
+    // CartPlan::voldev_sparse: likewise one row counter; the cell bytes and tile-chunk flags are the level's own (below)
+    if (p.level.voldev_sparse)
+      if (const int rcs = sparse_row_counter(c))
+        return rcs;
     const bool par = p.levels_concurrent && rc == PFM_OK;
     if (par)
       {
@@ -2707,12 +2721,20 @@ extern "C"
     for (size_t i = 0; i < nl && rc == PFM_OK; ++i)
       {
         hipStream_t st = par ? c->ov_streams[i] : c->stream;
-        const pfm::CartView &lcv = c->levels3[i].cv; // one plan per level lattice
-        rc = launch_assemble_cart(plan_cart(c->v, lcv, c->prm, p.residual_only, 0, cart_n_cu(), cart_split(c)), c->v, lcv, c->prm, d_values, d_res_pde,
-                                  d_res_tot, st, st, c->levels3[i].d_scal, &c->clock, n_compressed);
+        pfm_ctx::OverlayLevel &lv = c->levels3[i];
+        const pfm::CartView &lcv = lv.cv; // one plan per level lattice
+        const CartPlan lpl = plan_cart(c->v, lcv, c->prm, p.residual_only, 0, cart_n_cu(), cart_split(c));
+        pfm::SplitSparse sparse{};
+        if (lpl.voldev_sparse) // emptied on the level's stream in front of its mark kernel
+          if (const int rcs = sparse_buffers(c, lcv, lpl, lv.buf_sparse_cells, lv.buf_sparse_flags, lv.sparse_tiles, st, sparse))
+            return rcs;
+        rc = launch_assemble_cart(lpl, c->v, lcv, c->prm, d_values, d_res_pde, d_res_tot, st, st, lv.d_scal, &c->clock, n_compressed,
+                                  lpl.voldev_sparse ? &sparse : nullptr);
       }
     if (p.level.voldev_jac)
       c->compressed_valid = rc == PFM_OK;
+    if (p.level.voldev_sparse)
+      c->sparse_valid = rc == PFM_OK, c->sparse_levels = true;
     for (size_t i = 0; par && i < nl; ++i)
       if (const int rcj = join_from(c, c->ov_streams[i], c->stream, c->ov_events[i], "join (overlay levels)"))
         return rcj;
@@ -2801,7 +2823,7 @@ extern "C"
     AssemblyPlan plan = plan_assembly(c, residual_only, phase, d_values);
     if (!residual_only && phase != 1 && !(plan.cart && plan.box.voldev_jac) && !(plan.overlay3 && plan.level.voldev_jac))
       c->compressed_valid = false; // pfm_ctx_split_route_info: the count belongs to the last full assembly
-    if (!residual_only && phase != 1 && !(plan.cart && plan.box.voldev_sparse))
+    if (!residual_only && phase != 1 && !(plan.cart && plan.box.voldev_sparse) && !(plan.overlay3 && plan.level.voldev_sparse))
       c->sparse_valid = false; // pfm_ctx_split_sparse_info: likewise
     bool gather_ready = false;
     if (const int rct = ensure_tables(c, plan, gather_ready))
@@ -3265,19 +3287,38 @@ extern "C"
             out[0] = 1;
             out[3] = (int64_t)g.ntx * g.nty * g.nch;
           }
+        else if (p.overlay3 && p.level.voldev_sparse) // the level lattices of an overlay: summed over the levels
+          {
+            out[0] = 1;
+            for (const auto &lv : c->levels3)
+              {
+                const TileGrid g = plan_cart(c->v, lv.cv, c->prm, 0, 0, cart_n_cu(), cart_split(c)).grid[PFM_ZC_UU3];
+                out[3] += (int64_t)g.ntx * g.nty * g.nch;
+              }
+          }
       }
-    if (c->sparse_valid && c->buf_sparse_rows.p && c->buf_sparse_flags.p)
+    if (c->sparse_valid && c->buf_sparse_rows.p)
       {
         int n = 0;
-        std::vector<int> flags((size_t)c->sparse_tiles);
         (void)hipSetDevice(c->device);
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, c->buf_sparse_rows.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-            (!flags.empty() && hipMemcpy(flags.data(), c->buf_sparse_flags.p, flags.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, c->buf_sparse_rows.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
           return PFM_ERR_HIP;
+        int64_t flagged = 0;
+        auto count = [&](const pfm::DevBuf &b, int64_t tiles) {
+          std::vector<int> flags((size_t)tiles);
+          if (!flags.empty() && (!b.p || hipMemcpy(flags.data(), b.p, flags.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+            return false;
+          for (const int f : flags)
+            flagged += f != 0;
+          return true;
+        };
+        if (!c->sparse_levels && !count(c->buf_sparse_flags, c->sparse_tiles))
+          return PFM_ERR_HIP;
+        for (size_t i = 0; c->sparse_levels && i < c->levels3.size(); ++i)
+          if (!count(c->levels3[i].buf_sparse_flags, c->levels3[i].sparse_tiles))
+            return PFM_ERR_HIP;
         out[1] = n;
-        out[2] = 0;
-        for (const int f : flags)
-          out[2] += f != 0;
+        out[2] = flagged;
       }
     return PFM_OK;
   }

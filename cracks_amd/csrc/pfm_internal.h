@@ -303,6 +303,7 @@ struct pfm_ctx
   pfm::DevBuf buf_sparse_cells, buf_sparse_flags, buf_sparse_rows;
   int64_t sparse_tiles = 0;       // tile-chunks of the last sparse full assembly (entries of buf_sparse_flags in use)
   bool sparse_valid = false;      // the last full assembly ran sparse
+  bool sparse_levels = false;     // ... on the level lattices of an overlay (OverlayLevel::buf_sparse_*; the row counter is this one)
   int n_blocks = 1;
   int kernel_path = 0;
   int force_phase = 0; // pfm_ctx_force_phase (measurement)
@@ -371,6 +372,8 @@ struct pfm_ctx
     void *d_scal = nullptr; // the level's MatScal (its cell size)
     bool scal_dirty = true;
     int64_t n_rows = 0;
+    pfm::DevBuf buf_sparse_cells, buf_sparse_flags; // CartPlan::voldev_sparse on this level lattice: as the context's, below
+    int64_t sparse_tiles = 0;
   };
   std::vector<OverlayLevel> levels3;
   uint32_t *d_nbr_mask3 = nullptr;

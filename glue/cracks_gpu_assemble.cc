@@ -158,6 +158,10 @@ namespace pfm_glue_detail
     //                      full assembly of a box or sub-box evaluates the law only at the rows next to compressed cells and
     //                      takes every other row from the unsplit Jacobian kernels -- for runs that are in tension almost
     //                      everywhere (slower than route 5 where about half of the cells are compressed).
+    //                      PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE (= 13 | 16 | 32) and PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS_SPARSE
+    //                      (= 15 | 16 | 32): the same on the level lattices of a refined 3-D mesh -- the regular rows next to
+    //                      compressed cells are route 13's bytes, the other regular rows come from the unsplit level kernels,
+    //                      the residuals are route 13's; for predictor-corrector runs whose compressed region is small.
     //   hanging_mode:      PFM_HANGING_MODE_GATHER sends the cells at hanging vertices through per-cell scratch and an ordered
     //                      gather instead of atomic adds, in 2-D and under every 3-D law: two assemble() calls of the same state
     //                      then give the same bytes (pfm_set_hanging_mode; forwarded next to split_route).  Default

@@ -228,6 +228,52 @@ int pfm_set_split_model(pfm_ctx *ctx, int model);
  *   PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE  (= 1 | 2 | 4 | 16) the same with the residual-only calls of
  *                            PFM_SPLIT_ROUTE_LATTICE_ANY.  Every other value with bit 16 (16-20, 22, 24-31: bit 16 without
  *                            the Jacobian route, or together with bit 8) is refused with PFM_ERR_BAD_ARG.
+ *   PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE  (= 1 | 4 | 8 | 16 | 32) PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS with the law
+ *                            evaluated only where it differs from the unsplit one, on the level lattices of a 3-D overlay
+ *                            too (bit 32: valid only together with bits 8 and 16).  The FULL assembly of a 3-D overlay under
+ *                            PFM_SPLIT_VOLDEV with the split on, for every scheme, both layouts, per-cell Lame coefficients
+ *                            and any decompose_stress_matrix / decompose_stress_rhs weights, becomes per level lattice, on
+ *                            that level's stream (the context's, or its own under PFM_OVERLAY3_CONCURRENT=1):
+ *                            k_cart_residual3<false, true> writes residual_pde of the regular rows exactly as under route
+ *                            13; the level form of k_cart_split3_mark, a lane per cell of the level lattice, takes the cells
+ *                            whose eight vertices all exist on that level, writes one byte per cell (1: some q-point has
+ *                            h(tr E) = 0, by the trace statement of k_cart_split3_jac), flags the tile-chunks that own a
+ *                            regular row among the cell's vertices and counts the cell if its lowest vertex is a regular row
+ *                            of this rank (route 13's rule); the unsplit k_cart_uu3 and k_cart_phi4 of the level (the plan
+ *                            of the same parameters with decompose_stress_matrix = 0, no residual rows) write every regular
+ *                            row; k_cart_split3_jac<NCOL, true, true> leaves a tile-chunk without a flag at once, passes by
+ *                            every node that is no regular row or none of whose (up to) eight level cells has its byte set,
+ *                            and writes the four rows of the other nodes again as under route 13.  The general family runs
+ *                            exactly as under route 13.  No compaction pass, no host read-back, no floating-point atomics in
+ *                            these kernels.  PROMISED: a regular row whose node is a vertex of a level cell with a q-point
+ *                            where the device's tr E < 0 holds route 13's bytes in all four blocks, for any z-chunk length;
+ *                            every non-regular row holds route 13's bytes as long as pfm_ctx_hanging_info out[4] is 0;
+ *                            residual_pde is route 13's bytes on every row, and on the regular rows the residual-only
+ *                            call's; every other regular row holds what the unsplit level kernels wrote; the (u,phi) block
+ *                            holds exact zeros; the assembly is bitwise reproducible run to run, on a fresh context and
+ *                            under PFM_OVERLAY3_CONCURRENT=1.  NOT PROMISED: the untouched rows against an unsplit overlay
+ *                            assembly that runs other instantiations (homogeneous material in the linear scheme: residual
+ *                            rows in the Jacobian kernels; or time step 0 under the monolithic scheme, which drops the
+ *                            penalty term: with per-cell Lame coefficients and decompose_stress_matrix = 0 on the same
+ *                            context they are the same bytes), the untouched rows against the general route, and, as
+ *                            everywhere under this law, the matrix where tr E is zero up to rounding.  On a box or
+ *                            partitioned sub-box the route is PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE byte for byte (values,
+ *                            residual_pde, both info calls, both halves of the overlapped assembly); with the split off,
+ *                            under model 0 or 1 and on path 0 it acts as route 13, bit for bit; residual-only calls are
+ *                            those of route 13.  An overlay under PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE or _ALL_SPARSE
+ *                            keeps the general family for its full assembly, as before.  COST: per level the unsplit
+ *                            kernels and the mark kernel everywhere, the split kernel where cells are compressed, plus the
+ *                            general-family part of route 13.  Measured per full assembly on the block-refined 84^3 mesh
+ *                            (1.1e6 cells, 93 % regular rows) in one process against the general route's 13.6-13.8 ms,
+ *                            route 13's 22.2 ms and the unsplit overlay assembly's 3.76 ms
+ *                            (profiles/split_lattice_jacobian_levels_sparse/README.md): 4.10 ms with no compressed cell
+ *                            and 8.92 ms with a slab of 6.6 % of the cells compressed (8.1 % of the regular rows
+ *                            recomputed), below both routes in every round -- and 25.6 ms, 1.88 times the general route
+ *                            and 1.15 times route 13, above both in every round, where nearly every regular row touches a
+ *                            compressed cell: on such a state it is SLOWER than the general route.
+ *   PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS_SPARSE  (= 1 | 2 | 4 | 8 | 16 | 32) the same with the residual-only calls of
+ *                            PFM_SPLIT_ROUTE_LATTICE_ANY (route 15's); on a box PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE.  Every
+ *                            other value with bit 32 (32-60, 62, and anything above 63) is refused with PFM_ERR_BAD_ARG.
  * May be called at any time on a living context: the next assembly follows it.  An unknown route: PFM_ERR_BAD_ARG.
  * Any route but PFM_SPLIT_ROUTE_GENERAL on a 2-D context: PFM_ERR_UNSUPPORTED.  PFM_SPLIT_ROUTE_LATTICE with model 0 or 1 is
  * accepted and has no effect.
@@ -241,12 +287,16 @@ int pfm_set_split_model(pfm_ctx *ctx, int model);
  * that assembly did not run on that kernel or none has run.  On a 3-D overlay under the _LEVELS routes out[2] is 1 and
  * out[3] covers the cells of the level kernels only: the cells whose lowest vertex is a regular row, summed over the levels
  * (the cells of the general family are not counted).  Reading out[3] waits for the context's stream.  Under the _SPARSE
- * routes out[2] is 1 and out[3] is the count of k_cart_split3_mark: on any state the number route 5 reports.
+ * routes out[2] is 1 and out[3] is the count of k_cart_split3_mark: on any state the number route 5 reports (on an overlay
+ * under the _LEVELS_SPARSE routes: the number route 13 reports, summed over the levels).
  * pfm_ctx_split_sparse_info: out[0] whether a full assembly with the current parameters, model, route and forced path would
  * run sparse (0 before pfm_set_params); out[1] the nodes whose rows the sparse form of k_cart_split3_jac recomputed in the
  * last full assembly of this context, -1 when that one did not run sparse or none has run; out[2] the tile-chunks flagged
  * in that assembly (-1 likewise); out[3] the tile-chunks of the grid (of the plan of out[0]; 0 when out[0] is 0).  Reading
- * out[1] and out[2] waits for the context's stream. */
+ * out[1] and out[2] waits for the context's stream.  On a 3-D overlay under the _LEVELS_SPARSE routes out[0] is 1 when a full
+ * assembly would run sparse on the level lattices, out[1] the regular rows recomputed and out[2] the tile-chunks flagged in
+ * the last full assembly, both summed over the levels, out[3] the tile-chunks of all level grids; under the _SPARSE routes
+ * out[0] stays 0 there. */
 enum
 {
   PFM_SPLIT_ROUTE_GENERAL = 0,
@@ -257,7 +307,9 @@ enum
   PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS = 13,
   PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS = 15,
   PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_SPARSE = 21,
-  PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE = 23
+  PFM_SPLIT_ROUTE_LATTICE_ALL_SPARSE = 23,
+  PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE = 61,
+  PFM_SPLIT_ROUTE_LATTICE_ALL_LEVELS_SPARSE = 63
 };
 int pfm_set_split_route(pfm_ctx *ctx, int route);
 int pfm_ctx_split_route(const pfm_ctx *ctx, int *route, int *lattice_residual);

@@ -48,6 +48,15 @@ by round in one process.  The states: "tension" (a dilation plus noise: no compr
 planes z <= 5 h compressed: about 5 % of the cells of the default box) and "half" (the deviatoric gradient plus noise of the
 run above: about half of the cells).  The record carries the compressed cells, the rows the split kernel recomputed, the
 flagged tile-chunks and whether the sparse arm's round median is below route 5's in every round.
+
+--jacobian --overlay --route general lattice sparse --model voldev --compressed {tension,slab,half} times
+PFM_SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE ("sparse", route 61: per level the mark kernel, the unsplit level kernels and the
+sparse level form of k_cart_split3_jac) on the block-refined mesh next to "lattice" (route 13), "general" (route 0, the parent's
+path) and "unsplit" (the yardstick), all arms alternating round by round in one process.  The states: "tension" (a dilation plus
+noise: no compressed cell), "slab" (the same with the node planes |z| <= 0.5 compressed, a slab through the refined block and
+the coarse cells around it: about 5 % of the height) and "half" (the deviatoric gradient plus noise of the run above).  The
+record carries the compressed cells, the recomputed rows, the flagged tile-chunks and whether the sparse arm's round median is
+below the general arm's and below route 13's in every round.
 """
 import argparse
 import json
@@ -78,8 +87,8 @@ def main():
     ap.add_argument("--compressed", choices=["tension", "slab", "half"], default=None,
                     help="with --jacobian --route lattice sparse: the state the sparse route is timed on (see above)")
     args = ap.parse_args()
-    if ("sparse" in (args.route or [])) != (args.compressed is not None) or (args.compressed and (not args.jacobian or args.overlay)):
-        raise SystemExit("--compressed goes with --jacobian --route lattice sparse --model voldev")
+    if ("sparse" in (args.route or [])) != (args.compressed is not None) or (args.compressed and not args.jacobian):
+        raise SystemExit("--compressed goes with --jacobian [--overlay] --route lattice sparse --model voldev")
     if args.overlay and not args.jacobian:
         raise SystemExit("--overlay goes with --jacobian --route general lattice --model voldev")
     if args.n is None:
@@ -387,7 +396,14 @@ def bench_jacobian_overlay(args, capi, M, Assembler, O):
     h = 20.0 / n / 2  # the edge of a refined cell
     dev_grad = 1e-2 * np.array([[0.9, 0.7, -0.3], [0.1, -0.8, 0.5], [0.4, -0.2, -0.1]])  # trace 0: the noise decides the sign
     noise = rng.uniform(-2e-4 * h, 2e-4 * h, (mesh.n_nodes, 3))
-    sol = ch.distribute(lay.pack(mesh.coords @ dev_grad.T + noise, rng.uniform(0.3, 0.9, mesh.n_nodes)))
+    phi = rng.uniform(0.3, 0.9, mesh.n_nodes)
+    sol = ch.distribute(lay.pack(mesh.coords @ dev_grad.T + noise, phi))
+    if args.compressed in ("tension", "slab"):
+        u = 1e-2 * mesh.coords + noise
+        if args.compressed == "slab":  # the cells between the node planes |z| <= 0.5 are compressed by 1e-2, those across its faces stretched
+            low = np.abs(mesh.coords[:, 2]) <= 0.5
+            u[low] -= 2e-2 * mesh.coords[low]
+        sol = ch.distribute(lay.pack(u, phi))
     old = ch.distribute(lay.pack(np.zeros((mesh.n_nodes, 3)), rng.uniform(0.3, 0.9, mesh.n_nodes)))
     base = dict(mu=80.77, G_c=2.7, alpha_eps=0.5, constant_k=1e-3, pressure=0.05, timestep=1e-3, time=2e-3, old_timestep=1e-3,
                 old_old_timestep=1e-3, timestep_number=1)
@@ -400,13 +416,15 @@ def bench_jacobian_overlay(args, capi, M, Assembler, O):
     asm.allocate_matrix()
     rows, general_cells = asm.ctx.overlay_info()
     assert asm.ctx.kernel_path == 3 and rows > 0
-    routes = {"general": capi.SPLIT_ROUTE_GENERAL, "lattice": capi.SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS}
+    routes = {"general": capi.SPLIT_ROUTE_GENERAL, "lattice": capi.SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS,
+              "sparse": capi.SPLIT_ROUTE_LATTICE_JACOBIAN_LEVELS_SPARSE}
     arms = list(dict.fromkeys(args.route)) + ["unsplit"]
 
     def configure(arm):
         asm.split_route = routes.get(arm, capi.SPLIT_ROUTE_GENERAL)
         asm.set_params(prm_on if arm in routes else prm_off)
-        assert asm.ctx.kernel_path == 3 and asm.ctx.split_route_plan()[2] == int(arm == "lattice")
+        assert asm.ctx.kernel_path == 3 and asm.ctx.split_route_plan()[2] == int(arm in ("lattice", "sparse"))
+        assert asm.ctx.split_sparse_info()[0] == int(arm == "sparse")
 
     def timed(arm):
         configure(arm)
@@ -428,14 +446,25 @@ def bench_jacobian_overlay(args, capi, M, Assembler, O):
         asm.assemble_system(False)
         asm.synchronize()
         compressed[arm] = asm.ctx.split_route_plan()[3]
+        if arm == "sparse":
+            info = asm.ctx.split_sparse_info()
         outs[arm] = [m.clone() for m in asm.system_pde_matrix] + [asm.system_pde_residual.clone()]
     rec = {"metric": "split3d_routes_jacobian_overlay", "cells": int(mesh.n_cells), "nodes": int(mesh.n_nodes), "hanging_nodes": int(mesh.hn_nodes.size),
            "regular_rows": int(rows), "regular_row_fraction": rows / mesh.n_nodes, "cells_left_to_the_general_family": int(general_cells),
            "layout": args.layout, "reps": args.reps, "rounds": args.rounds, "arms": arms,
            "cells_with_a_compressed_q_point_among_those_of_the_level_kernels": {k: v for k, v in compressed.items() if v >= 0}}
-    if len(outs) == 2:
+    if "lattice" in outs and "general" in outs:
         rec["lattice_deviation_from_general"] = max(float((a - b).abs().max() / max(1.0, float(b.abs().max())))
                                                     for a, b in zip(outs["lattice"], outs["general"]))
+    if "sparse" in outs:
+        rec.update({"state": args.compressed, "compressed_cell_fraction_of_the_level_kernels": compressed["sparse"] / mesh.n_cells, "rows_recomputed": info[1],
+                    "rows_recomputed_fraction_of_the_regular_rows": info[1] / rows, "tile_chunks_flagged": info[2], "tile_chunks": info[3]})
+        for other in ("lattice", "general"):
+            if other in outs:
+                rec[f"sparse_deviation_from_{other}"] = max(float((a - b).abs().max() / max(1.0, float(b.abs().max())))
+                                                            for a, b in zip(outs["sparse"], outs[other]))
+        if "lattice" in outs:
+            rec["residual_pde_same_bytes_as_lattice"] = bool(torch_equal(outs["sparse"][-1], outs["lattice"][-1]))
     del outs
     ts = {arm: [] for arm in arms}
     for _ in range(args.rounds):
@@ -445,6 +474,12 @@ def bench_jacobian_overlay(args, capi, M, Assembler, O):
     for arm in arms:
         rec[arm] = {"ms": med[arm], "min_ms": float(np.concatenate(ts[arm]).min()), "round_medians_ms": [float(np.median(t)) for t in ts[arm]],
                     "ms_per_1e6_cells": med[arm] * 1e6 / mesh.n_cells}
+    if "sparse" in med:
+        rec["sparse_over_unsplit"] = med["sparse"] / med["unsplit"]
+        for other in ("lattice", "general"):
+            if other in med:
+                rec[f"sparse_over_{other}"] = med["sparse"] / med[other]
+                rec[f"sparse_below_{other}_in_every_round"] = all(np.median(a) < np.median(b) for a, b in zip(ts["sparse"], ts[other]))
     if "lattice" in med:
         rec["lattice_over_unsplit"] = med["lattice"] / med["unsplit"]
     if "lattice" in med and "general" in med:
