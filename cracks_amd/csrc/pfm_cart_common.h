@@ -191,12 +191,14 @@ namespace pfm
     // the same from ONE nodal field: staggered scheme (no clamping of the old fields at the q-points), where pf_extra is
     // linear in (phi_old, phi_oldold) up to its final clamp -- pw = phi_old if use_old_timestep_pf, else
     // phi_oldold + tfac (phi_old - phi_oldold), formed per node by the caller
+    // valid = false (a cell outside the mesh): the z-weight that multiplies all nine results is zero, so every w*g is +0
+    // as long as the interpolated values are finite (absent nodes hold zeros) -- two selects instead of one per result
     template <bool LIT = false /* Gauss data as literals instead of c_g1 */, class MatScalRef>
-    __device__ __forceinline__ void cell_wg_plane_lin(const double pw[8], const MatScalRef &S, int qz, double wg[9])
+    __device__ __forceinline__ void cell_wg_plane_lin(const double pw[8], const MatScalRef &S, int qz, double wg[9], bool valid = true)
     {
       auto N = [](int a, int q) __attribute__((always_inline)) { return LIT ? g1_n(a, q) : c_g1.n[a][q]; };
       auto Wt = [](int q) __attribute__((always_inline)) { return LIT ? g1_w(q) : c_g1.w[q]; };
-      const double nz1 = gauss_n1(qz), nz0 = 1.0 - nz1, wz = gauss_w(qz); // q_z is a per-lane run-time index
+      const double nz1 = gauss_n1(qz), nz0 = 1.0 - nz1, wz = valid ? gauss_w(qz) : 0.0; // q_z is a per-lane run-time index
       double a[4];
 #pragma unroll
       for (int v = 0; v < 4; ++v)
@@ -221,11 +223,11 @@ namespace pfm
     // weights w*g(q) of one cell at the 9 q-points of one z-level (cracks.cc:2262-2277)
     template <bool LIT = false, class MatScalRef>
     __device__ __forceinline__ void cell_wg_plane(const double po[8], const double poo[8], const MatScalRef &S, int qz,
-                                                  double wg[9])
+                                                  double wg[9], bool valid = true /* as in cell_wg_plane_lin */)
     {
       auto N = [](int a, int q) __attribute__((always_inline)) { return LIT ? g1_n(a, q) : c_g1.n[a][q]; };
       auto Wt = [](int q) __attribute__((always_inline)) { return LIT ? g1_w(q) : c_g1.w[q]; };
-      const double nz1 = gauss_n1(qz), nz0 = 1.0 - nz1, wz = gauss_w(qz);
+      const double nz1 = gauss_n1(qz), nz0 = 1.0 - nz1, wz = valid ? gauss_w(qz) : 0.0;
       double a[4], b[4];
 #pragma unroll
       for (int v = 0; v < 4; ++v)

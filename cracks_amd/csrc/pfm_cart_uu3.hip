@@ -280,6 +280,16 @@ namespace pfm
               }
           }
       });
+      // RES: the products of the dot are formed in front of the lane swaps.  A swap overwrites both of its operands; behind
+      // it the own parts stay alive for the products (which wait for the u values from LDS) and every operand of a swap is
+      // copied first: four moves per pair sum.  The empty statements make the operands of the swaps depend on the
+      // finished dot (a scheduling barrier alone does not order the products, which have no side effects)
+      if constexpr (PLANE && RES)
+        {
+#pragma unroll
+          for (int sl = 0; sl < NS; ++sl)
+            asm volatile("" : "+v"(dot), "+v"(val[sl][0]), "+v"(val[sl][1]), "+v"(val[sl][2]));
+        }
       if constexpr (PLANE)
         {
           if constexpr (NS == 1)
@@ -343,7 +353,25 @@ namespace pfm
       int anyflag[4][2];               // per ring slot and request wave: some node of the plane carries a displacement flag
       int irregular[2];                // by plane parity: bit 0 = some row is not a full, lattice-ordered 27-neighbour row,
                                        // bit 1 = some row's CSR slots are a permutation of the lattice order (bit 31 of its mask)
+      unsigned wgidx[3 * CS3];         // w*g phase: (cell, z-level) of a thread, written once in the prologue (wg_word)
     };
+    // thread t of the w*g phase <-> cell slot cs = t % CS3 (layer l, cell (cx, cy)) at the z-level qz = t / CS3: in-plane halo
+    // index of the cell's first node | l << 6 | qz << 7 | (index of its first result in the w*g scratch [qz][q][cs]) << 9
+    __host__ __device__ constexpr unsigned wg_word(int t)
+    {
+      const int cs = t % CS3, qz = t / CS3;
+      const int l = cs / CL3, cy = (cs % CL3) / C3X, cx = cs % C3X;
+      return (unsigned)((cx + H3X * cy) | (l << 6) | (qz << 7) | ((qz * 9 * CS3 + cs) << 9));
+    }
+    // what cell_wg_plane_lin reads of MatScal, with use_old as a constant of the call
+    template <int USE_OLD>
+    struct WgScal
+    {
+      double kappa, vol;
+      static constexpr int use_old = USE_OLD;
+    };
+    static_assert((C3X - 1) + H3X * (C3Y - 1) < 64&& wg_word(3 * CS3 - 1) >> 9 == 2 * 9 * CS3 + CS3 - 1, "the fields of wg_word hold their values");
+    static_assert(sizeof(UuShared<false, true>) <= 64 * 1280 && sizeof(UuShared<true, false>) <= 64 * 1280, "two workgroups per CU");
     static_assert(27 * CS3 <= NN3 * STG, "w*g scratch must fit in the staging buffer");
     static_assert(NN3 * STG <= 4 * TGRP3 && 2 * 8 * NN3 <= TGRP3, "second staging buffer in front of group 4, the residual sums inside it");
     using UuSharedRes_ = UuShared<false, true>;
@@ -375,6 +403,7 @@ namespace pfm
   const MatScal &S = A.S;                                                                                                    \
   int t = threadIdx.x;                                                                                                       \
   asm volatile("" : "+v"(t));                                                                                                \
+  __builtin_assume(t >= 0 && t < NT3); /* (the range is lost with the value: clamps and guards that never act) */            \
   const int lane = t & 63;                                                                                                   \
   (void)v;                                                                                                                   \
   (void)cv;                                                                                                                  \
@@ -524,6 +553,8 @@ namespace pfm
             if (nl == 0)
               sh.irregular[0] = (irr != 0 ? 1 : 0) | (prm != 0 ? 2 : 0);
           }
+        if (t < 3 * CS3)
+          sh.wgidx[t] = wg_word(t); // read in every w*g phase, behind the top barrier of the plane
         stamp(7); // thread 0: its own halo loads have returned and are stored
       }
 
@@ -684,12 +715,15 @@ namespace pfm
             UU_ENV();
             if (t < 3 * CS3)
               {
-                const int cs = t % CS3, qz = t / CS3;
-                const int l = cs / CL3, cy = (cs % CL3) / C3X, cx = cs % C3X;
-                const int hq = cx + H3X * cy;
+                // (cell, z-level) of the thread from the word of the prologue (wg_word): one LDS read per plane instead of
+                // the division chains; only the ring slots of the planes are arithmetic
+                const unsigned word = sh.wgidx[t];
+                const int hq = word & 63, l = (word >> 6) & 1, qz = (word >> 7) & 3;
+                double *const wq = s_stage + (word >> 9);
                 const int pa = (l ? s1 : s0) * NHP3 + hq, pb = (l ? s2 : s1) * NHP3 + hq; // lower / upper nodal plane of the layer
                 // all reads of the cell in one batch (the two validity bytes next to the nodal values: one LDS round trip);
-                // a cell outside the mesh reads zeros and is zeroed
+                // a cell outside the mesh reads zeros and gets a zero z-weight: every w*g of it is +0 (the values of its
+                // nodes are finite, absent ones are zero) for two selects instead of eighteen on the nine results
                 const bool valid = sh.ok[pa] && sh.ok[pb + 1 + H3X];
                 double wg[9];
                 {
@@ -702,7 +736,11 @@ namespace pfm
                           po[b] = sh.po[pa + (b & 1) + H3X * ((b >> 1) & 1)];
                           po[b + 4] = sh.po[pb + (b & 1) + H3X * ((b >> 1) & 1)];
                         }
-                      cell_wg_plane_lin<true>(po, S, qz, wg);
+                      // use_old is uniform: one scalar branch around two evaluations, not two selects per q-point
+                      if (S.use_old)
+                        cell_wg_plane_lin<true>(po, WgScal<1>{S.kappa, S.vol}, qz, wg, valid);
+                      else
+                        cell_wg_plane_lin<true>(po, WgScal<0>{S.kappa, S.vol}, qz, wg, valid);
                     }
                   else
                     {
@@ -715,15 +753,12 @@ namespace pfm
                           poo[b] = sh.poo[RES ? 0 : ha];
                           poo[b + 4] = sh.poo[RES ? 0 : hb];
                         }
-                      cell_wg_plane<true>(po, poo, S, qz, wg);
+                      cell_wg_plane<true>(po, poo, S, qz, wg, valid);
                     }
                 }
 #pragma unroll
                 for (int q = 0; q < 9; ++q)
-                  wg[q] = valid ? wg[q] : 0.0;
-#pragma unroll
-                for (int q = 0; q < 9; ++q)
-                  s_stage[(qz * 9 + q) * CS3 + cs] = wg[q];
+                  wq[q * CS3] = wg[q];
               }
           }
           lds_barrier();
@@ -942,6 +977,7 @@ namespace pfm
                   constexpr int NG = 12, NIT = 3;
                   int tq = t;
                   asm volatile("" : "+v"(tq)); // (g, ep) are recomputed per component, not kept live across the node phases
+                  __builtin_assume(tq >= 0 && tq < NT3); // g < NG: no clamp and no guard for the first two nodes of a thread
                   // (round 6: the 32 single values go with wave 0, whose slot set is the lightest, instead of wave 7, whose is
                   // the heaviest -- the wave that runs both arms of this branch was the one every barrier waited for)
                   if (tq >= 32)
