@@ -320,6 +320,23 @@ class Context:
         self._check(self.lib.pfm_values_delta_info(self._h, out), "pfm_values_delta_info")
         return {"chunk_bytes": int(out[0]), "slab_bytes": int(out[1]), "device_bytes": int(out[2]), "valid": bool(out[3])}
 
+    def values_keep_up_block(self, ptr: int):
+        """``pfm_values_keep_up_block``: clears the (u,phi) block at device address ``ptr`` once (synchronous) and promises
+        that nothing but the library writes it from here on; assemblies whose ``value_ptrs[1]`` is ``ptr`` then leave it
+        untouched.  Blocked layout only.  Withdraw the promise (``values_release_up_block``, ``close``) before the array
+        is freed."""
+        self._check(self.lib.pfm_values_keep_up_block(self._h, C.c_void_p(ptr)), "pfm_values_keep_up_block")
+
+    def values_release_up_block(self):
+        """withdraws the promise of ``values_keep_up_block`` (harmless without one)"""
+        self._check(self.lib.pfm_values_keep_up_block(self._h, None), "pfm_values_keep_up_block")
+
+    def values_up_block_kept(self) -> int:
+        """``pfm_values_up_block_kept``: the device address of the kept (u,phi) block, 0 if there is none."""
+        p = C.c_void_p()
+        self._check(self.lib.pfm_values_up_block_kept(self._h, C.byref(p)), "pfm_values_up_block_kept")
+        return int(p.value or 0)
+
     def assemble_host(self, sol, old, oldold, residual_only: bool, out=None):
         """``pfm_assemble``: synchronous, host numpy in / host numpy out (single rank).  ``out`` = (values, res_pde,
         res_tot): arrays of an earlier call to write into again (what a host with its own matrix storage does; with
@@ -702,8 +719,26 @@ class Assembler:
         z = lambda: torch.zeros(n, dtype=torch.float64, device=self.dev)
         self.solution, self.old_solution, self.old_old_solution = z(), z(), z()
         self.system_pde_residual, self.system_total_residual = z(), z()
-        self.system_pde_matrix: List = []
+        self._system_pde_matrix: List = []
         self.halo = halo
+
+    @property
+    def system_pde_matrix(self) -> List:
+        return self._system_pde_matrix
+
+    @system_pde_matrix.setter
+    def system_pde_matrix(self, blocks):
+        # the promise on the (u,phi) block of allocate_matrix goes before the tensors do: the caching allocator may hand
+        # the address to someone else.  Only that promise: one the caller gave for an array of its own
+        # (ctx.values_keep_up_block) stays
+        if (self._system_pde_matrix and self._keeps_up_block()
+                and self.ctx.values_up_block_kept() == self._system_pde_matrix[1].data_ptr() != 0):
+            self.ctx.values_release_up_block()
+        self._system_pde_matrix = list(blocks) if blocks else []
+
+    def _keeps_up_block(self) -> bool:
+        # (PFM_LIB may name an older build in an A/B run)
+        return self.ctx.n_blocks == 4 and hasattr(self.ctx.lib, "pfm_values_keep_up_block") and bool(getattr(self.ctx, "_h", None))
 
     @property
     def split_model(self) -> int:
@@ -738,11 +773,27 @@ class Assembler:
     def hanging_mode(self, mode: int):
         self.ctx.set_hanging_mode(mode)
 
-    def allocate_matrix(self):
-        if not self.system_pde_matrix:
+    def allocate_matrix(self, keep_up_block: bool = False):
+        """The value vectors, once.  ``keep_up_block`` (blocked layout; what ``assemble_system`` passes when it allocates
+        them itself): the structurally zero (u,phi) block is cleared here and kept (Context.values_keep_up_block) -- the
+        tensors are this object's own and nothing but the library writes them; a caller who does write
+        ``system_pde_matrix[1]`` afterwards calls ``ctx.values_release_up_block()`` first.  A caller who allocates the
+        matrix itself takes the tensors in hand before the first assembly, may prefill them, and gets no promise.
+
+        Two consequences.  (1) After ``assemble_system`` has allocated the matrix, whatever a caller writes into
+        ``system_pde_matrix[1]`` without withdrawing the promise STAYS there: the next assembly does not overwrite it
+        (a caller that refills every block between assemblies allocates the matrix itself for that reason).
+        (2) Callers that allocate first run unkept and measure the kernels that write the block; they pass
+        ``keep_up_block=True`` to run the kept form.  A promise the caller has given the context for an array of its own
+        is left in place."""
+        if not self._system_pde_matrix:
             t = self.torch
-            self.system_pde_matrix = [t.empty(self.ctx.pattern_size(b)[1], dtype=t.float64, device=self.dev)
-                                      for b in range(self.ctx.n_blocks)]
+            self._system_pde_matrix = [t.empty(self.ctx.pattern_size(b)[1], dtype=t.float64, device=self.dev)
+                                       for b in range(self.ctx.n_blocks)]
+            # (on the context's stream: assemble_system has set it to torch's current one)
+            if (keep_up_block and self._keeps_up_block() and self._system_pde_matrix[1].numel() > 0
+                    and self.ctx.values_up_block_kept() == 0):
+                self.ctx.values_keep_up_block(self._system_pde_matrix[1].data_ptr())
 
     def set_params(self, prm):
         self.ctx.set_params(prm)
@@ -774,7 +825,7 @@ class Assembler:
             self.ctx.state_set_device(self.solution.data_ptr(), self.old_solution.data_ptr(),
                                       self.old_old_solution.data_ptr())
         if not residual_only:
-            self.allocate_matrix()
+            self.allocate_matrix(keep_up_block=True)
         ptrs = [m.data_ptr() for m in self.system_pde_matrix] if not residual_only else []
         # PFM_OVERLAP=1: the ghost import on the context's side stream next to the interior tiles.  Off by default: on one
         # node the import is ~0.05 ms (pack + unpack 0.02 ms measured, ~7 messages of <= 0.6 MB over xGMI) while cutting

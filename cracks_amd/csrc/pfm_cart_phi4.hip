@@ -997,10 +997,12 @@ namespace pfm
               bool RES = false /* also writes the phase-field rows of the residual (res_pde) */,
               bool OLDF = false /* the general form: q-point loops along x (clamped phase field of the monolithic scheme,
                                    penalisation term) and phi_old / phi_oldold in the nodal ring; else the x-contraction from
-                                   coefficients, the old fields fetched where the rare placeholder path needs them */>
+                                   coefficients, the old fields fetched where the rare placeholder path needs them */,
+              bool KEEPUP = false /* blocked layout: vals_up is a kept block (CartView::up_block_cleared) -- it holds its zeros
+                                     already and no copy-out stores to it */>
     __global__ __launch_bounds__(NT4, 2) void k_cart_phi4(DevView v, CartView cv, const MatScal *__restrict__ Sp, double *__restrict__ vals_pu,
                                                           double *__restrict__ vals_pp, double *__restrict__ vals_uu,
-                                                          double *__restrict__ vals_up /* blocked layout: structurally zero (u,phi) block, cleared here */,
+                                                          double *__restrict__ vals_up /* blocked layout: structurally zero (u,phi) block, cleared here (KEEPUP: left alone) */,
                                                           int zc_in /* node planes per chunk */,
                                                           unsigned long long *__restrict__ dbg, double *__restrict__ res_pde)
     {
@@ -1162,6 +1164,10 @@ namespace pfm
       __syncthreads();
       if (t < NPH && s.flag[(kA - 1) & 3][2 * t])
         s.anyflag[(kA - 1) & 3] = 1;
+      // the unconditional vector-memory instructions of a wave in a fast blocked copy-out: per y-line (phi,u) at uq and at
+      // uq + NT4, and the same two of (u,phi) unless that block is kept
+      constexpr int NST_FAST = (KEEPUP ? 2 : 4) * PN;
+      static_assert(NST_FAST == 14 || NST_FAST == 28, "the wait counts below are literals");
       int nst = 0;       // lower bound of the vector-memory instructions this wave has issued behind its last requests
 #pragma unroll 1
       for (int ck = kA - 1; ck < kB; ++ck)
@@ -1174,9 +1180,15 @@ namespace pfm
           // plane ck + 1 and the rows of plane ck were requested before the previous step's copy-out.  vmcnt counts loads
           // and stores in issue order: with at least 28 stores issued behind the requests (fast blocked copy-out: 7 y-lines x
           // 4 unconditional stores per wave), "at most 28 outstanding" means the requests have landed -- the wave does not
-          // wait for its own stores to drain, they have the whole next role phase for that
-          if (nst >= 28)
-            asm volatile("s_waitcnt vmcnt(28)" ::: "memory");
+          // wait for its own stores to drain, they have the whole next role phase for that.  KEEPUP: two of the four are the
+          // zeros of the (u,phi) block and are not issued -- 7 x 2 = 14 (NST_FAST; DESIGN.md 4.2 has the count from the ISA)
+          if (nst >= NST_FAST)
+            {
+              if constexpr (NST_FAST == 14)
+                asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
+              else
+                asm volatile("s_waitcnt vmcnt(28)" ::: "memory");
+            }
           else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           nst = 0;
@@ -1449,15 +1461,18 @@ namespace pfm
                     {
                       double *bpu = vals_pu + 3 * off0[ny], *bup = vals_up + 3 * off0[ny], *bpp = vals_pp + off0[ny];
                       bpu[uq] = val[ny][0];
-                      bup[uq] = 0.0;
+                      if constexpr (!KEEPUP)
+                        bup[uq] = 0.0;
                       bpu[uq + NT4] = val[ny][1];
-                      bup[uq + NT4] = 0.0;
+                      if constexpr (!KEEPUP)
+                        bup[uq + NT4] = 0.0;
                       spu[0][ny * (PN * 27)] = 0.0; // these slabs are the next planes' accumulators
                       spu[1][ny * (PN * 27)] = 0.0;
                       if (act2)
                         {
                           bpu[uq + 2 * NT4] = val[ny][2];
-                          bup[uq + 2 * NT4] = 0.0;
+                          if constexpr (!KEEPUP)
+                            bup[uq + 2 * NT4] = 0.0;
                           spu[2][ny * (PN * 27)] = 0.0;
                         }
                       if (actp)
@@ -1466,7 +1481,7 @@ namespace pfm
                           spp[ny * (PN * 9)] = 0.0;
                         }
                     }
-                  nst = 4 * PN;
+                  nst = NST_FAST;
                 }
               else if (NCOL == 3 && regular_or_permuted && !masked && tile_full)
                 {
@@ -1536,15 +1551,18 @@ namespace pfm
                   for (int ny = 0; ny < PN; ++ny)
                     {
                       vals_pu[dpu[ny][0]] = val[ny][0];
-                      vals_up[dpu[ny][0]] = 0.0;
+                      if constexpr (!KEEPUP)
+                        vals_up[dpu[ny][0]] = 0.0;
                       vals_pu[dpu[ny][1]] = val[ny][1];
-                      vals_up[dpu[ny][1]] = 0.0;
+                      if constexpr (!KEEPUP)
+                        vals_up[dpu[ny][1]] = 0.0;
                       spu[0][ny * (PN * 27)] = 0.0; // these slabs are the next planes' accumulators
                       spu[1][ny * (PN * 27)] = 0.0;
                       if (act2)
                         {
                           vals_pu[dpu[ny][2]] = val[ny][2];
-                          vals_up[dpu[ny][2]] = 0.0;
+                          if constexpr (!KEEPUP)
+                            vals_up[dpu[ny][2]] = 0.0;
                           spu[2][ny * (PN * 27)] = 0.0;
                         }
                       if (actp)
@@ -1553,7 +1571,7 @@ namespace pfm
                           spp[ny * (PN * 9)] = 0.0;
                         }
                     }
-                  nst = 4 * PN;
+                  nst = NST_FAST;
                 }
               else if (t < 2 * 108)
                 {
@@ -1648,7 +1666,8 @@ namespace pfm
                                   else
                                     {
                                       vals_pu[3 * off + sl * 3 + fe_d] = val;
-                                      vals_up[3 * off + sl * 3 + fe_d] = 0.0; // any bijection onto the node's 3 rows
+                                      if constexpr (!KEEPUP)
+                                        vals_up[3 * off + sl * 3 + fe_d] = 0.0; // any bijection onto the node's 3 rows
                                     }
                                 }
                               else // interleaved layout: row (node, 3) holds [u_x u_y u_z phi] per neighbour slot
@@ -1741,15 +1760,21 @@ namespace pfm
     // residual, the general form (OLDF; never with the residual rows), and plain / OLDF for heterogeneous material (the
     // residual kernel runs); clocked (1 per phase, 2 per role): blocked, homogeneous, !OLDF.
     using PhiKernel = void (*)(DevView, CartView, const MatScal *, double *, double *, double *, double *, int, unsigned long long *, double *);
-    PhiKernel phi4_kernel(const CartPlan &pl)
+    PhiKernel phi4_kernel(const CartPlan &pl, bool keep_up)
     {
+      // blocked layout with a kept (u,phi) block (CartView::up_block_cleared): the same five, without a store to that block
+      static const PhiKernel kept[5] = {k_cart_phi4<3, 0, false, false, false, true>, k_cart_phi4<3, 0, false, true, false, true>,
+                                        k_cart_phi4<3, 0, false, false, true, true>, k_cart_phi4<3, 0, true, false, false, true>,
+                                        k_cart_phi4<3, 0, true, false, true, true>};
       static const PhiKernel plain[2][5] = {{k_cart_phi4<3, 0, false, false, false>, k_cart_phi4<3, 0, false, true, false>, k_cart_phi4<3, 0, false, false, true>,
                                              k_cart_phi4<3, 0, true, false, false>, k_cart_phi4<3, 0, true, false, true>},
                                             {k_cart_phi4<4, 0, false, false, false>, k_cart_phi4<4, 0, false, true, false>, k_cart_phi4<4, 0, false, false, true>,
                                              k_cart_phi4<4, 0, true, false, false>, k_cart_phi4<4, 0, true, false, true>}};
       static const PhiKernel clocked[2][2] = {{k_cart_phi4<3, 1>, k_cart_phi4<3, 1, false, true>}, {k_cart_phi4<3, 2>, k_cart_phi4<3, 2, false, true>}};
       if (pl.phi4_clock)
-        return clocked[pl.phi4_clock - 1][pl.rows_residual];
+        return clocked[pl.phi4_clock - 1][pl.rows_residual]; // (profiling: they write a kept block's zeros again, which is harmless)
+      if (keep_up && !pl.interleaved)
+        return kept[pl.het ? 3 + pl.oldf() : pl.oldf() ? 2 : pl.rows_residual];
       return plain[pl.interleaved][pl.het ? 3 + pl.oldf() : pl.oldf() ? 2 : pl.rows_residual];
     }
 
@@ -1790,7 +1815,7 @@ namespace pfm
     if (pl.phi4_clock && !(dbg = clock ? clock->reserve(nd, s) : nullptr))
       return PFM_ERR_HIP;
     const bool il = pl.interleaved; // one block of values: no (phi,u), (phi,phi) and (u,phi) blocks of their own
-    const PhiKernel kernel = phi4_kernel(pl);
+    const PhiKernel kernel = phi4_kernel(pl, cv.up_block_cleared != 0);
     hipLaunchKernelGGL(kernel, grid, block, 0, s, v, cv, static_cast<const MatScal *>(d_scal), il ? nullptr : d_values[2], il ? nullptr : d_values[3], d_values[0],
                        il ? nullptr : d_values[1], zc, dbg, res_pde);
     if (hipGetLastError() != hipSuccess)

@@ -482,7 +482,8 @@ namespace pfm
               {
                 double *dst = A.vals_uu + 9 * off + (long long)COMP * 3 * deg + sl * 3;
                 dst[0] = val[0], dst[1] = val[1], dst[2] = val[2];
-                A.vals_up[3 * off + (long long)COMP * deg + sl] = 0.0;
+                if (!cv.up_block_cleared) // (kernel-uniform) a kept (u,phi) block holds its zeros already
+                  A.vals_up[3 * off + (long long)COMP * deg + sl] = 0.0;
               }
           }
       });

@@ -1376,6 +1376,40 @@ extern "C"
     return PFM_OK;
   }
 
+  // The kept (u,phi) block (include/pfm_assemble.h; plan_assembly decides per call whether d_values[1] is it).  Off the hot
+  // path: the fill is complete on return, so no later pfm_ctx_set_stream can put an assembly in front of it.
+  int pfm_values_keep_up_block(pfm_ctx *c, double *d_values_up)
+  {
+    if (!c)
+      return PFM_ERR_BAD_ARG;
+    if (c->n_blocks != 4)
+      return fail(c, PFM_ERR_BAD_ARG, "pfm_values_keep_up_block: the interleaved layout has no (u,phi) block of its own");
+    if (!d_values_up)
+      {
+        c->kept_up_block = nullptr;
+        return PFM_OK;
+      }
+    if (c->block_nnz(1) <= 0)
+      return fail(c, PFM_ERR_BAD_ARG, "pfm_values_keep_up_block: the (u,phi) block is empty");
+    c->kept_up_block = nullptr; // no promise while the array is not known to be clear
+    (void)hipSetDevice(c->device);
+    hipError_t e = hipMemsetAsync(d_values_up, 0, sizeof(double) * (size_t)c->block_nnz(1), c->stream);
+    if (e == hipSuccess)
+      e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess)
+      return hipfail(c, e, "pfm_values_keep_up_block");
+    c->kept_up_block = d_values_up;
+    return PFM_OK;
+  }
+
+  int pfm_values_up_block_kept(const pfm_ctx *c, const double **d_values_up)
+  {
+    if (!c || !d_values_up)
+      return PFM_ERR_BAD_ARG;
+    *d_values_up = c->kept_up_block;
+    return PFM_OK;
+  }
+
   int pfm_set_params(pfm_ctx *c, const pfm_params *p)
   {
     if (!c || !p)
@@ -2340,6 +2374,7 @@ extern "C"
     int phase = 0; // 0: the whole assembly; 1, 2: the halves of pfm_assemble_overlapped
     bool residual_only = false, split = false, cart = false, patches = false, overlay3 = false, overlay_uu = false, nothing = false;
     bool pair = false, fork = false, levels_concurrent = false, fill_up_block = false, up_block_cleared = false;
+    bool keep_up_block = false; // d_values[1] is a kept (u,phi) block: nothing of this call writes it
     bool gather = false, fork_general = false, atomic_stream = false; // final behind the lazy tables: after_tables
     CartPlan box;   // cart: what the launchers of the cartesian family do (plan_cart)
     CartPlan level; // overlay3: the same for the first level lattice (every level shares its scheme, law and kernels)
@@ -2392,12 +2427,18 @@ extern "C"
     p.levels_concurrent = p.overlay3 && c->levels3.size() > 1 && Switches::levels_concurrent();
     // 2-D box, blocked layout: the structurally zero (u,phi) block (cracks.cc:2333-2337) by a fill in front of the kernels,
     // in the whole assembly and in phase 1; phase 2 takes it as cleared by phase 1 (CartView::up_block_cleared).
-    // (round 6, measured and removed for 3-D: clearing the block with a fill on a third stream instead of by 21 of the 49
-    // store instructions of every copy-out of k_cart_phi4 -- 10.95 -> 11.35 ms per assembly at 216^3,
-    // profiles/r06/ab_up_fill.txt: the fill takes bandwidth in a burst and dispatch slots from the pair)
+    // A kept block (pfm_values_keep_up_block; the library's own staging block, cleared when pfm_assemble allocated it)
+    // holds its zeros from one assembly to the next: no fill, and in both dimensions no store of any row-owner kernel
+    // (k_cart2d_cells, k_cart_phi4, k_cart_split3_jac) and no memset of the general family.  Without a promise the 3-D
+    // kernels write the block with their rows: 21 of the 49 store instructions of every copy-out of k_cart_phi4, 6.6 of
+    // the 38 GB a 216^3 assembly writes.  Moving those stores elsewhere never paid (a fill on a third stream: 10.95 ->
+    // 11.35 ms, profiles/r06/ab_up_fill.txt); not doing them at all does (profiles/keep_up_block/README.md).
+    // PFM_NO_KEEP_UP_BLOCK=1: the promise is ignored.
+    const double *up = (!residual_only && c->n_blocks == 4 && d_values) ? d_values[1] : nullptr;
+    p.keep_up_block = up && (up == c->kept_up_block || (c->stage_up_kept && up == c->d_stage_val[1])) && Switches::keep_up_block();
     const bool blocked2 = p.cart && c->v.dim == 2 && !residual_only && c->v.layout == PFM_LAYOUT_BLOCKED;
-    p.fill_up_block = blocked2 && phase <= 1 && c->n_blocks == 4 && d_values[1] && Switches::cart2d_fill();
-    p.up_block_cleared = p.fill_up_block || (blocked2 && phase == 2 && Switches::cart2d_fill());
+    p.fill_up_block = blocked2 && phase <= 1 && c->n_blocks == 4 && d_values[1] && Switches::cart2d_fill() && !p.keep_up_block;
+    p.up_block_cleared = p.keep_up_block || p.fill_up_block || (blocked2 && phase == 2 && Switches::cart2d_fill());
     return p;
   }
 
@@ -2501,8 +2542,10 @@ extern "C"
   }
 
   // zero the outputs (cracks.cc:2133-2137).  The row-owner kernels write every entry exactly once -- the structurally zero
-  // (u,phi) block of the blocked layout included (k_cart_phi4) -- and need no zeroing pass: of a box nothing is zeroed, of
-  // an overlay the residuals and the rows of the general family.
+  // (u,phi) block of the blocked layout included (k_cart_phi4), unless it is a kept block (AssemblyPlan::keep_up_block), which
+  // nobody writes or zeroes -- and need no zeroing pass: of a box nothing is zeroed, of an overlay the residuals and the
+  // rows of the general family (launch_zero_rows and the scatter of the general family can only write or add zeros to a
+  // kept block: they stay as they are).
   static int zero_outputs(pfm_ctx *c, const AssemblyPlan &p, double *const *d_values, double *d_res_pde, double *d_res_tot)
   {
     hipError_t e = hipSuccess;
@@ -2515,7 +2558,7 @@ extern "C"
         {
           if (!d_values[b] && c->block_nnz(b) > 0)
             return fail(c, PFM_ERR_BAD_ARG, "null matrix block");
-          if (!p.cart && !p.patches)
+          if (!p.cart && !p.patches && !(b == 1 && p.keep_up_block))
             e = hipMemsetAsync(d_values[b], 0, sizeof(double) * (size_t)c->block_nnz(b), c->stream);
         }
     if (e == hipSuccess && p.patches && !p.residual_only && c->n_rows_general > 0 &&
@@ -2722,7 +2765,8 @@ extern "C"
       {
         hipStream_t st = par ? c->ov_streams[i] : c->stream;
         pfm_ctx::OverlayLevel &lv = c->levels3[i];
-        const pfm::CartView &lcv = lv.cv; // one plan per level lattice
+        pfm::CartView lcv = lv.cv; // one plan per level lattice
+        lcv.up_block_cleared = p.keep_up_block ? 1 : 0;
         const CartPlan lpl = plan_cart(c->v, lcv, c->prm, p.residual_only, 0, cart_n_cu(), cart_split(c));
         pfm::SplitSparse sparse{};
         if (lpl.voldev_sparse) // emptied on the level's stream in front of its mark kernel
@@ -3148,6 +3192,17 @@ extern "C"
             if (e != hipSuccess)
               return hipfail(c, e, "hipMalloc stage values");
             c->device_bytes += (int64_t)bytes;
+            if (c->n_blocks == 4 && b == 1 && bytes)
+              {
+                // the staging (u,phi) block is the library's own: cleared once, here, and kept (plan_assembly) -- complete
+                // before any assembly on any stream; an unregistered h_values[1] keeps receiving these zeros by its copy
+                e = hipMemsetAsync(c->d_stage_val[b], 0, bytes, c->stream);
+                if (e == hipSuccess)
+                  e = hipStreamSynchronize(c->stream);
+                if (e != hipSuccess)
+                  return hipfail(c, e, "clear the staged (u,phi) block");
+                c->stage_up_kept = true;
+              }
           }
     rc = pfm_assemble_device(c, residual_only, c->d_stage_val, c->d_stage_res[0], c->d_stage_res[1]);
     if (rc)

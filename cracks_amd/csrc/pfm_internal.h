@@ -111,7 +111,9 @@ namespace pfm
     // launch -- hanging, parent, mixed-level or ghost nodes stay with the general family).  nullptr: every owned node of
     // the box is a row (uniform boxes).
     const int32_t *row_of_box;
-    int up_block_cleared;             // 2-D boxes, blocked layout: the caller has cleared the structurally zero (u,phi) block with a fill
+    int up_block_cleared;             // blocked layout: the structurally zero (u,phi) block holds its zeros already and the kernels of
+                                      // this launch leave it alone -- a kept block (pfm_values_keep_up_block), or a 2-D box whose
+                                      // assembly has cleared it with a fill in front of the launch (AssemblyPlan::up_block_cleared)
     int tile_sel;                     // 0: every tile; 1: only tiles that read no ghost node ("interior"); 2: only the
                                       // others -- the two launches of pfm_assemble_overlapped, between which the ghost
                                       // import lands (cracks.cc:2147-2154 next to the cell loop instead of in front of it)
@@ -332,6 +334,10 @@ struct pfm_ctx
   double *d_stage_vec[3] = {nullptr, nullptr, nullptr};
   double *d_stage_res[2] = {nullptr, nullptr};
   double *d_stage_val[4] = {nullptr, nullptr, nullptr, nullptr};
+  // pfm_values_keep_up_block: the caller's (u,phi) block that holds its zeros and that nobody but the library writes
+  // (nullptr: no promise).  stage_up_kept: d_stage_val[1] was cleared when it was allocated; only pfm_assemble writes it
+  double *kept_up_block = nullptr;
+  bool stage_up_kept = false;
   // host arrays the caller page-locked through pfm_host_register (DMA at the link rate instead of the pageable path);
   // zeroed: the array is the (u,phi) block of a matrix and has been cleared once (pfm_values_to_host never copies it)
   struct HostPin

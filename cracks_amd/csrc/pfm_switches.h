@@ -27,6 +27,8 @@ namespace pfm
     static bool cart2d_one_launch() { return set("PFM_CART2D_ONE_LAUNCH"); } // k_cart2d_cells: one launch for both row groups
     // the (u,phi) block of a blocked 2-D box by a fill in front of the kernels (PFM_CART2D_NO_FILL: written with the rows)
     static bool cart2d_fill() { return !set("PFM_CART2D_NO_FILL") && !cart2d_one_launch(); }
+    // a kept (u,phi) block (pfm_values_keep_up_block) is left alone (PFM_NO_KEEP_UP_BLOCK: the promise is ignored, every path writes it)
+    static bool keep_up_block() { return !set("PFM_NO_KEEP_UP_BLOCK"); }
     static bool fused_scatter() { return !set("PFM_NO_FUSED_SCATTER"); }     // line search: the residual kernel scatters the solution
     static bool levels_concurrent() { return set("PFM_OVERLAY3_CONCURRENT"); } // 3-D overlay: a stream per level lattice
     static bool res_no_transfers() { return set("PFM_RES_NO_TRANSFERS"); }   // k_cart_residual3 instead of 3x / 3d

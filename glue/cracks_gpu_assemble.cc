@@ -204,7 +204,7 @@ namespace pfm_glue_detail
     void release()
     {
       if (ctx)
-        pfm_ctx_destroy(ctx); // (unregisters every host array of the context)
+        pfm_ctx_destroy(ctx); // (unregisters every host array of the context, withdraws the promise on d_val[1])
       ctx = nullptr;
       holds_host_pins = false;
       for (double *&p : d_vec)
@@ -414,6 +414,10 @@ namespace pfm_glue_detail
             AssertThrow(nnz[block] == n_entries, ExcMessage("pattern size mismatch"));
             AssertThrow(hipMalloc((void **)&d_val[block], sizeof(double) * (size_t)std::max<int64_t>(nnz[block], 1)) == hipSuccess,
                         ExcMessage("hipMalloc (matrix values)"));
+            // the structurally zero (u,phi) block: this array is ours and only the library writes it -- cleared once, here,
+            // and left alone by every assembly (withdrawn by pfm_ctx_destroy in release(), in front of the hipFree)
+            if (blocked && block == 1 && nnz[block] > 0)
+              PFM_CALL(ctx, pfm_values_keep_up_block(ctx, d_val[block]));
             // Epetra's value array receives 35 GB per Jacobian at 1e7 cells: page-locked, the transfer is DMA at the link
             // rate (pageable memory: a fraction of it).  Best effort: if the pages cannot be locked the copy still works.
             // Opt-in (pin_host_matrix): the lock must be gone BEFORE the matrix is reinitialised in setup_system --

@@ -481,6 +481,27 @@ int pfm_assemble(pfm_ctx *ctx, const double *sol, const double *old, const doubl
                  int residual_only, double *const *values, double *residual_pde,
                  double *residual_total);
 
+/* A kept (u,phi) block (4-block layout only).  The block is identically zero on every path of the library and of the
+ * reference (cracks.cc:2333-2337), yet it is 3/16 of the matrix values and 18.5 % of every byte a blocked 3-D Jacobian
+ * assembly writes.  With a promise from the caller the library writes it once and never again.
+ *   pfm_values_keep_up_block   clears block_nnz(1) doubles at d_values_up to +0.0 (on the context's stream, complete on
+ *                              return) and remembers the pointer.  From then on the caller promises that nothing but this
+ *                              library writes that array; in turn every pfm_assemble_device / pfm_assemble_overlapped whose
+ *                              d_values[1] EQUALS that pointer may leave the block untouched.  A call with any other
+ *                              d_values[1] behaves as without a promise and leaves the promise in place.  One promise per
+ *                              context: another pointer replaces it, the same pointer again clears the array again.  NULL
+ *                              withdraws it.  PFM_ERR_BAD_ARG for the interleaved layout and for a non-NULL pointer when
+ *                              block_nnz(1) == 0.  The array stays the caller's; the promise must be withdrawn (NULL here;
+ *                              pfm_ctx_destroy does it too) BEFORE the array is freed or reallocated (setup_system after
+ *                              refine_mesh).  It survives pfm_set_params, pfm_set_constraints, pfm_pattern_bind*,
+ *                              pfm_set_split_model / _route, pfm_set_hanging_mode, pfm_ctx_force_path / _phase / _zchunk and
+ *                              pfm_ctx_set_stream.  PFM_NO_KEEP_UP_BLOCK=1 (read per call): the promise is ignored and every
+ *                              path writes the block.
+ *   pfm_values_up_block_kept   the kept pointer, NULL if there is none.
+ * pfm_assemble (host pointers) keeps the block of its own staging arrays itself, without a promise from anyone. */
+int pfm_values_keep_up_block(pfm_ctx *ctx, double *d_values_up /* NULL: withdraw */);
+int pfm_values_up_block_kept(const pfm_ctx *ctx, const double **d_values_up);
+
 /* Delta transfer of the matrix values ("Delta transfer"): within a time step most of the Jacobian does not
  * change between Newton iterations (without the stress split the displacement rows depend on the lagged phase field
  * only), and the library finds out itself which values did.

@@ -48,6 +48,7 @@ def main():
         a.set_constraints(flags)
         pack = lambda uu, pp: np.concatenate([uu.reshape(-1), pp])
         a.set_vectors(pack(u, phi), pack(0 * u, po), pack(0 * u, poo))
+        a.allocate_matrix()  # allocated here: this tool writes every block itself, so no (u,phi) block is kept
         a.assemble_system(False)
         a.synchronize()
         ref = [m.clone() for m in a.system_pde_matrix] + [a.system_pde_residual.clone()]
@@ -70,6 +71,7 @@ def main():
     a = problem(n)
     if len(sys.argv) > 2 and sys.argv[2] == "general":  # python tools/stress.py 64 general: the colour classes of the general family
         a.ctx.force_path(0)
+    a.allocate_matrix()  # (as above: every block is overwritten below, no kept (u,phi) block)
     a.assemble_system(False)
     a.synchronize()
     ref = [m.clone() for m in a.system_pde_matrix] + [a.system_pde_residual.clone()]
