@@ -74,7 +74,7 @@ def build_native(force: bool = False, verbose: bool = False) -> str:
 
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
         list(ex.map(run, jobs))
-    # RCCL (the in-library ghost exchange, pfm_halo_exchange) is resolved at run time (dlopen in pfm_host.cpp): the
+    # RCCL (the in-library ghost exchange, pfm_halo_exchange) is resolved at run time (dlopen in pfm_halo.cpp): the
     # library loads on hosts without RCCL and binds to whatever copy the process already carries (torch's, or ROCm's)
     run([cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB, "-ldl"])
     return LIB

@@ -1,5 +1,5 @@
-// pfm_internal.h — context layout shared by the host side (pfm_host.cpp) and the
-// kernel launchers (pfm_kernels.hip).  Not part of the ABI.
+// pfm_internal.h — the context (pfm_ctx), the device views and the launcher declarations shared by the host-side files
+// of the C ABI (pfm_host.h names them) and the kernel files (*.hip).  Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -275,7 +275,7 @@ namespace pfm
     size_t h_pack_bytes = 0;
     hipEvent_t ev_cmp[2] = {nullptr, nullptr}, ev_dma[2] = {nullptr, nullptr};
   };
-  // the transfer path of pfm_values_to_host for one piece of a caller-owned array (pfm_host.cpp: d2h_user)
+  // the transfer path of pfm_values_to_host for one piece of a caller-owned array (pfm_transfer.cpp: d2h_user)
   hipError_t d2h_user_piece(pfm_ctx *c, void *h, const void *d, size_t bytes, hipStream_t s);
   // pfm_host_unregister of p (nullptr: all), pfm_ctx_destroy
   void delta_forget_host(pfm_ctx *c, const void *p);
@@ -317,7 +317,7 @@ struct pfm_ctx
   std::vector<int32_t> h_nadj;
   // Lattice meshes: the 27-wide host node graph (h_nadj), its device copy (v.nadj) and the slot table of the general
   // cell kernel (v.cslot) are 1.1 + 1.1 + 0.65 GB at 1e7 cells and are only needed by pfm_pattern_get / _bind and by the
-  // general family: built on first use (ensure_host_graph, ensure_general_tables in pfm_host.cpp)
+  // general family: built on first use (ensure_host_graph, ensure_general_tables in pfm_ctx_build.cpp)
   bool graph_positional = false; // uniform box, node n at lattice position n, no ghosts: row pointers and colour lists are made on the device
   bool hanging_coloured = false; // 3-D: cells at hanging vertices sit in plain colour classes (reduced scatter, no atomics)
   int32_t n_hanging = 0;

@@ -5,7 +5,7 @@
 //   pfm_active_set_device   active-set predicate + cycle counter      cracks.cc:2837-2886, 2903-2909
 //                           + constraints_hanging_nodes.distribute    cracks.cc:2888-2890
 //   pfm_active_set_owned_device, pfm_halo_pack_flags_all / _unpack_flags_all, pfm_distribute_hanging_device
-//                           the same block in the pieces of a rank with ghost peers (pfm_active_set_exchange, pfm_host.cpp)
+//                           the same block in the pieces of a rank with ghost peers (pfm_active_set_exchange, pfm_halo.cpp)
 //   pfm_functionals         compute_energy, compute_tcv               cracks.cc:3615-3701, 3553-3611
 //
 // All three work on any Q1 mesh (MappingQ1 geometry per cell) with the node state / tables of the context.  The Q1

@@ -246,7 +246,7 @@ int main(int argc, char **argv)
           put_colours(mode ? "redh" : "red", red);
         }
     }
-  // ---- the scan of the pool header (pfm_host.cpp: row pointers of a lattice), against a serial one; not part of the result file
+  // ---- the scan of the pool header (pfm_ctx_build.cpp: row pointers of a lattice), against a serial one; not part of the result file
   {
     std::vector<long long> a(200000), b(a.size());
     for (size_t i = 0; i < a.size(); ++i)

@@ -1,4 +1,4 @@
-"""The assembly dispatch of pfm_host.cpp (plan_assembly, assemble_box / assemble_overlay / assemble_general) on paths the
+"""The assembly dispatch of pfm_dispatch.cpp (plan_assembly, assemble_box / assemble_overlay / assemble_general) on paths the
 other suites do not reach: every entry point in sequence on one context, the level lattices of the 3-D overlay on streams
 of their own, the timing intervals of whole and half assemblies, and the error returns in front of the kernels."""
 import os

@@ -95,7 +95,7 @@ def test_hanging_3d_topologies_in_every_mode(make, mode, monkeypatch):
 
 def test_colour_overflow_next_to_the_gather_every_time():
     """fan3d_41_hanging in the default mode: the cells that found no colour add atomically from the side stream while the
-    colour classes run, so the colour classes must add atomically too (pfm_host.cpp: general_view keeps DevView::cell_ring
+    colour classes run, so the colour classes must add atomically too (pfm_dispatch.cpp: general_view keeps DevView::cell_ring
     when colours overflowed).  Plain read-modify-writes next to those atomics lose an update now and then, not every
     time: twenty Jacobians on one context, each against the oracle."""
     import scipy.sparse as sp

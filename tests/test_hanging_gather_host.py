@@ -43,5 +43,6 @@ def test_both_dimensions_were_exercised(output):
 def test_the_host_side_calls_the_builder_it_tests():
     """ensure_hang_gather has no list code of its own left: it hands the records to pfm::hang_gather_lists."""
     text = open(os.path.join(CSRC, "pfm_host.cpp")).read()
-    body = text[text.index("static bool ensure_hang_gather"):text.index("static int ensure_halo_buffers")]
+    start = text.index("bool ensure_hang_gather(pfm_ctx *c)\n")  # its definition, up to the next one of the file
+    body = text[start:text.index("int pfm_ctx_destroy(pfm_ctx *c)\n", start)]
     assert "pfm::hang_gather_lists(" in body and "HgEntry{(int32_t)(hc * 32" not in body

@@ -1,5 +1,5 @@
-"""The launches of the cartesian family, for comparing two builds of the library launch by launch (a change of the launchers
-or of plan_cart must leave this listing as it is):
+"""The launches of the cartesian family, for comparing two builds of the library launch by launch (a change of the launchers,
+of plan_cart or of the dispatch in pfm_dispatch.cpp must leave this listing as it is):
 
     rocprofv3 --kernel-trace --output-format csv -d DIR -o p -- python tools/launch_trace.py        # the run to trace
     python tools/launch_trace.py --list DIR > listing.txt                                            # its launches
