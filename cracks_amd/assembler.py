@@ -226,6 +226,22 @@ class Context:
         """``pfm_state_set_solution``: old / old_old keep the values of the last full scatter (line search)."""
         self._check(self.lib.pfm_state_set_solution(self._h, C.c_void_p(sol_ptr), 1), "pfm_state_set_solution")
 
+    def values_keep_uu_block(self, ptr: int):
+        """``pfm_values_keep_uu_block``: promises that nothing but the library writes the (u,u) block at device address
+        ``ptr``; assemblies into that pointer then leave it alone while old_solution, old_old_solution, the displacement
+        constraints and the parameters are what they were when it was written.  Nothing is cleared.  Blocked layout only."""
+        self._check(self.lib.pfm_values_keep_uu_block(self._h, C.c_void_p(ptr)), "pfm_values_keep_uu_block")
+
+    def values_release_uu_block(self):
+        """withdraws the promise of ``values_keep_uu_block`` (harmless without one)"""
+        self._check(self.lib.pfm_values_keep_uu_block(self._h, None), "pfm_values_keep_uu_block")
+
+    def values_uu_block_kept(self) -> int:
+        """``pfm_values_uu_block_kept``: the device address of the kept (u,u) block, 0 if there is none."""
+        p = C.c_void_p()
+        self._check(self.lib.pfm_values_uu_block_kept(self._h, C.byref(p)), "pfm_values_uu_block_kept")
+        return p.value or 0
+
     def state_set_host(self, sol: np.ndarray, old: np.ndarray, oldold: np.ndarray):
         a = [np.ascontiguousarray(x, np.float64) for x in (sol, old, oldold)]
         self._check(self.lib.pfm_state_set(self._h, capi.np_ptr(a[0], np.float64), capi.np_ptr(a[1], np.float64),
@@ -734,11 +750,17 @@ class Assembler:
         if (self._system_pde_matrix and self._keeps_up_block()
                 and self.ctx.values_up_block_kept() == self._system_pde_matrix[1].data_ptr() != 0):
             self.ctx.values_release_up_block()
+        if (self._system_pde_matrix and self._keeps_uu_block()
+                and self.ctx.values_uu_block_kept() == self._system_pde_matrix[0].data_ptr() != 0):
+            self.ctx.values_release_uu_block()
         self._system_pde_matrix = list(blocks) if blocks else []
 
     def _keeps_up_block(self) -> bool:
         # (PFM_LIB may name an older build in an A/B run)
         return self.ctx.n_blocks == 4 and hasattr(self.ctx.lib, "pfm_values_keep_up_block") and bool(getattr(self.ctx, "_h", None))
+
+    def _keeps_uu_block(self) -> bool:
+        return self.ctx.n_blocks == 4 and hasattr(self.ctx.lib, "pfm_values_keep_uu_block") and bool(getattr(self.ctx, "_h", None))
 
     @property
     def split_model(self) -> int:
@@ -794,6 +816,11 @@ class Assembler:
             if (keep_up_block and self._keeps_up_block() and self._system_pde_matrix[1].numel() > 0
                     and self.ctx.values_up_block_kept() == 0):
                 self.ctx.values_keep_up_block(self._system_pde_matrix[1].data_ptr())
+            # ... and the (u,u) block is kept while the lagged phase field, the displacement constraints and the parameters
+            # stay what they were (Context.values_keep_uu_block): given exactly where the other promise is
+            if (keep_up_block and self._keeps_uu_block() and self._system_pde_matrix[0].numel() > 0
+                    and self.ctx.values_uu_block_kept() == 0):
+                self.ctx.values_keep_uu_block(self._system_pde_matrix[0].data_ptr())
 
     def set_params(self, prm):
         self.ctx.set_params(prm)

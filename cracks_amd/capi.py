@@ -35,7 +35,7 @@ EXPORTS = [
     "pfm_check_finite",
     "pfm_halo_register", "pfm_halo_pack", "pfm_halo_unpack", "pfm_halo_pack_all", "pfm_halo_unpack_all",
     "pfm_assemble_device", "pfm_assemble_nl_residual_device",
-    "pfm_sync_status", "pfm_assemble", "pfm_host_register", "pfm_host_unregister", "pfm_values_to_host", "pfm_values_keep_up_block", "pfm_values_up_block_kept", "pfm_values_to_host_delta", "pfm_values_delta_reset", "pfm_values_delta_config", "pfm_values_delta_info", "pfm_ctx_kernel_path", "pfm_ctx_force_path", "pfm_ctx_overlay_info", "pfm_ctx_force_phase",
+    "pfm_sync_status", "pfm_assemble", "pfm_host_register", "pfm_host_unregister", "pfm_values_to_host", "pfm_values_keep_up_block", "pfm_values_up_block_kept", "pfm_values_keep_uu_block", "pfm_values_uu_block_kept", "pfm_values_to_host_delta", "pfm_values_delta_reset", "pfm_values_delta_config", "pfm_values_delta_info", "pfm_ctx_kernel_path", "pfm_ctx_force_path", "pfm_ctx_overlay_info", "pfm_ctx_force_phase",
     "pfm_ctx_force_zchunk", "pfm_ctx_zchunk", "pfm_ctx_device_bytes", "pfm_timing_enable", "pfm_kernel_time_ms", "pfm_kernel_times_ms",
     # include/pfm_newton.h
     "pfm_diag_mass_device", "pfm_active_set_device", "pfm_get_constraints", "pfm_functionals",
@@ -161,6 +161,9 @@ def load():
     if hasattr(lib, "pfm_values_keep_up_block"):  # (PFM_LIB may name an older build in an A/B run)
         lib.pfm_values_keep_up_block.argtypes = [vp, vp]
         lib.pfm_values_up_block_kept.argtypes = [vp, C.POINTER(vp)]
+    if hasattr(lib, "pfm_values_keep_uu_block"):
+        lib.pfm_values_keep_uu_block.argtypes = [vp, vp]
+        lib.pfm_values_uu_block_kept.argtypes = [vp, C.POINTER(vp)]
     lib.pfm_values_to_host_delta.argtypes = [vp, vp, vp, C.POINTER(i64)]
     lib.pfm_values_delta_reset.argtypes = [vp]
     lib.pfm_values_delta_config.argtypes = [vp, i64, i64]

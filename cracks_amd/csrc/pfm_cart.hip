@@ -1253,8 +1253,10 @@ namespace pfm
                   const double r = -s_P[4 + c][t] - s_P[c][t + RTX];
                   const bool con = (fl >> c) & 1u;
                   const long long di = dof_index_c<3>(v, row, c);
+                  if (c == 3 && (write_total & 2)) // the displacement rows alone (launch_assemble_cart, CartPlan::keep_uu)
+                    continue;
                   res_pde[di] = con ? 0.0 : r; // constrained scatter = masked store (cracks.cc:2440-2456)
-                  if (write_total)
+                  if (write_total & 1)
                     res_tot[di] = (con && S.total_via_update) ? 0.0 : r;
                 }
             }
@@ -1442,8 +1444,10 @@ namespace pfm
                   const double r = -s.P[par][4 + c][t] - s.P[par][c][t + RTX];
                   const bool con = (fl >> c) & 1u;
                   const long long di = dof_index_c<3>(v, (int)row, c);
+                  if (c == 3 && (write_total & 2)) // the displacement rows alone (launch_assemble_cart, CartPlan::keep_uu)
+                    continue;
                   res_pde[di] = con ? 0.0 : r; // constrained scatter = masked store (cracks.cc:2440-2456)
-                  if (write_total)
+                  if (write_total & 1)
                     res_tot[di] = (con && S.total_via_update) ? 0.0 : r;
                 }
             }
@@ -1655,8 +1659,10 @@ namespace pfm
                   const double r = -s.P[par][4 + c][t] - s.P[par][c][t + RTX];
                   const bool con = (fl >> c) & 1u;
                   const long long di = dof_index_c<3>(v, (int)row, c);
+                  if (c == 3 && (write_total & 2)) // the displacement rows alone (launch_assemble_cart, CartPlan::keep_uu)
+                    continue;
                   res_pde[di] = con ? 0.0 : r; // constrained scatter = masked store (cracks.cc:2440-2456)
-                  if (write_total)
+                  if (write_total & 1)
                     res_tot[di] = (con && S.total_via_update) ? 0.0 : r;
                 }
             }
@@ -1710,7 +1716,7 @@ namespace pfm
   // phase-field kernel of the pair, or under PFM_SIDE_STREAM for the residual kernel: both only read the node state), else s.
   int launch_assemble_cart(const CartPlan &pl, const DevView &v, const CartView &cv_in, const pfm_params &p, double *const *d_values,
                            double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock,
-                           int *n_compressed, const SplitSparse *sparse)
+                           int *n_compressed, const SplitSparse *sparse, const UuKeep *keep)
   {
     using ResidualKernel = void (*)(DevView, CartView, Scal, double *, double *, int, int);
     static const ResidualKernel residual_kernel[5][2] = {{nullptr, nullptr}, // by CartResidual and its flag: every instantiation there is
@@ -1773,7 +1779,30 @@ namespace pfm
     double *const res_rows = pl.rows_residual ? res_pde : nullptr;
     cv.tile_sel = pl.tile_sel(PFM_ZC_UU3);
     int rc = PFM_OK;
-    if (pl.uu3())
+    if (pl.keep_uu)
+      {
+        // CartPlan::keep_uu, all on s: k_cart_uu3 without the residual rows (returns at once when the block is current), the
+        // mark and the restore of the patched entries, the displacement rows of the residual from the quadrature kernel
+        if (!keep || !pl.pair || !pl.uu3() || (pl.u_rows != PFM_RES_3D && pl.u_rows != PFM_RES_3))
+          return PFM_ERR_INTERNAL;
+        CartPlan un = pl;
+        un.rows_residual = false; // (the form and its LDS alone; the plan stays a pair)
+        CartView cvu = cv;
+        cvu.uu_stale = keep->words;
+        rc = launch_cart_uu3(un, v, cvu, p, d_values[0], s, nullptr, clock);
+        if (rc == PFM_OK)
+          rc = launch_uu_mark_restore(*keep, d_values[0], s);
+        const TileGrid &g = pl.grid[PFM_ZC_RES3];
+        if (rc == PFM_OK && g.n_tiles != 0)
+          {
+            cv.tile_sel = 0;
+            hipLaunchKernelGGL(residual_kernel[pl.u_rows][pl.u_rows == PFM_RES_3 ? 1 : 0], dim3(xcd_grid(g.n_tiles)), dim3(RTX * RTY), 0, s, v, cv,
+                               make_scal(p, cv, v.dim), res_pde, res_tot, 2 /* no total residual, no phase-field row */, g.zc);
+            if (hipGetLastError() != hipSuccess)
+              rc = PFM_ERR_HIP;
+          }
+      }
+    else if (pl.uu3())
       rc = launch_cart_uu3(pl, v, cv, p, d_values[0], s, res_rows, clock);
     cv.tile_sel = 0;
     if (rc == PFM_OK && pl.phi4())

@@ -1838,14 +1838,65 @@ namespace pfm
       for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
         vals_uu[idx[i]] += val[i]; // one entry per matrix value at most: no two threads share an address
     }
+
+    // The same into a kept (u,u) block (CartPlan::keep_uu).  The patches depend on `solution`, the block under them does not:
+    // the assembly that wrote the block (keep.words[1]) records every patched entry and its value before the patch; one
+    // that kept the block has had those values put back (k_uu_restore) and adds to them -- the same addition on the same
+    // operands as in the block just written.
+    __global__ void k_cart_apply_patches_kept(double *__restrict__ vals_uu, const long long *__restrict__ idx, const double *__restrict__ val,
+                                              const int *__restrict__ count, int cap, int *__restrict__ status, UuKeep keep)
+    {
+      if (*count > cap && blockIdx.x == 0 && threadIdx.x == 0)
+        atomicMax(status, (int)PFM_ERR_INTERNAL);
+      const int n = min(*count, cap);
+      const bool written = keep.words[1] != 0;
+      for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        {
+          const long long at = idx[i];
+          if (written)
+            {
+              keep.saved_idx[i] = at;
+              keep.saved_val[i] = vals_uu[at];
+            }
+          vals_uu[at] += val[i];
+        }
+      if (written && blockIdx.x == 0 && threadIdx.x == 0)
+        *keep.saved_count = n;
+    }
+
+    __global__ void k_uu_mark(UuKeep keep)
+    {
+      keep.words[1] = keep.words[0];
+      keep.words[0] = 0;
+    }
+
+    __global__ void k_uu_restore(double *__restrict__ vals_uu, UuKeep keep)
+    {
+      if (keep.words[1] != 0)
+        return; // k_cart_uu3 has just written the block
+      const int n = *keep.saved_count;
+      for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        vals_uu[keep.saved_idx[i]] = keep.saved_val[i];
+    }
   } // namespace
 
-  int launch_cart_apply_patches(const CartView &cv, double *vals_uu, hipStream_t s, int *status)
+  int launch_cart_apply_patches(const CartView &cv, double *vals_uu, hipStream_t s, int *status, const UuKeep *keep)
   {
     if (!cv.patch_count)
       return PFM_OK;
-    hipLaunchKernelGGL(k_cart_apply_patches, dim3(64), dim3(256), 0, s, vals_uu, cv.patch_idx, cv.patch_val, cv.patch_count, cv.patch_cap,
-                       status);
+    if (keep)
+      hipLaunchKernelGGL(k_cart_apply_patches_kept, dim3(64), dim3(256), 0, s, vals_uu, cv.patch_idx, cv.patch_val, cv.patch_count, cv.patch_cap,
+                         status, *keep);
+    else
+      hipLaunchKernelGGL(k_cart_apply_patches, dim3(64), dim3(256), 0, s, vals_uu, cv.patch_idx, cv.patch_val, cv.patch_count, cv.patch_cap,
+                         status);
+    return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
+  }
+
+  int launch_uu_mark_restore(const UuKeep &keep, double *vals_uu, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_uu_mark, dim3(1), dim3(1), 0, s, keep);
+    hipLaunchKernelGGL(k_uu_restore, dim3(64), dim3(256), 0, s, vals_uu, keep);
     return hipGetLastError() == hipSuccess ? PFM_OK : PFM_ERR_HIP;
   }
 } // namespace pfm

@@ -127,6 +127,13 @@ namespace pfm
     // ... side by side on two streams: the caller forks, joins and applies the deferred patches (CartView::patch_*), the (u,u)
     // kernel takes the LDS allocation of the other.  Not in a half, not on a level lattice, not in another mode.
     bool pair = false;
+    // ... of a pair into a kept (u,u) block (pfm_values_keep_uu_block; plan_keep_uu): k_cart_uu3 in its form without the
+    // residual rows, which returns at once when the block is current (CartView::uu_stale), and behind it on the same stream
+    // the quadrature kernel `u_rows` (PFM_RES_3D or PFM_RES_3, what `residual` would be without rows_residual) storing the
+    // displacement rows of residual_pde alone: those rows have the same bits whether the block was written or kept.
+    // k_cart_phi4 writes the phase-field rows as in every pair.
+    bool keep_uu = false;
+    CartResidual u_rows = PFM_RES_NONE;
     CartResidual residual = PFM_RES_NONE; // the residual kernel that runs
     bool one_launch = false;              // k_cart2d_cells<2> instead of <0> + <1>
     // phase clocks (profiling) exist for the blocked layout, homogeneous material and k_cart_phi4<!OLDF>: nothing else is clocked
@@ -192,5 +199,20 @@ namespace pfm
           pl.grid[k] = cart_tile_grid(sel, k, n_cu);
         }
     return pl;
+  }
+
+  // CartPlan::keep_uu on the plan of a pair (plan_assembly decides whether the promise applies)
+  inline void plan_keep_uu(CartPlan &pl, const DevView &v, const CartView &cv, int n_cu)
+  {
+    if (!pl.pair)
+      return;
+    const bool whole_lex = cv.owned_lex && cv.o0[0] == 0 && cv.o0[1] == 0 && cv.o0[2] == 0 && cv.o1[0] == cv.NX - 1 &&
+                           cv.o1[1] == cv.NY - 1 && cv.o1[2] == cv.NZ - 1 && (long long)v.n_nodes == (long long)cv.NX * cv.NY * cv.NZ &&
+                           v.n_owned == v.n_nodes && (long long)v.n_nodes * 32 < (1LL << 32) && !Switches::res_no_transfers();
+    pl.keep_uu = true;
+    pl.u_rows = whole_lex ? PFM_RES_3D : PFM_RES_3; // (PFM_RES_3X reads the caller's vector in place: not in a full assembly)
+    CartView sel = cv;
+    sel.tile_sel = 0;
+    pl.grid[PFM_ZC_RES3] = cart_tile_grid(sel, PFM_ZC_RES3, n_cu);
   }
 } // namespace pfm

@@ -459,6 +459,9 @@ namespace pfm
       const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wave-uniform: scalar branches between the slot sets
       {
         UU_ENV();
+        // a kept (u,u) block that holds the current values (CartView::uu_stale): nothing to do.  Kernel-uniform
+        if (cv.uu_stale != nullptr && __builtin_amdgcn_readfirstlane(*cv.uu_stale) == 0)
+          return;
         const int OWX = cv.o1[0] - cv.o0[0] + 1, OWY = cv.o1[1] - cv.o0[1] + 1, OWZ = cv.o1[2] - cv.o0[2] + 1;
         const int ntx = (OWX + T3X - 1) / T3X, nty = (OWY + T3Y - 1) / T3Y;
         const int zc = A.zc, nch = (OWZ + zc - 1) / zc;

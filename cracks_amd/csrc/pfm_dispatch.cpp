@@ -128,6 +128,7 @@ namespace
     bool residual_only = false, split = false, cart = false, patches = false, overlay3 = false, overlay_uu = false, nothing = false;
     bool pair = false, fork = false, levels_concurrent = false, fill_up_block = false, up_block_cleared = false;
     bool keep_up_block = false; // d_values[1] is a kept (u,phi) block: nothing of this call writes it
+    bool keep_uu = false;       // d_values[0] is a kept (u,u) block and the promise applies: written only when stale (CartPlan::keep_uu)
     bool gather = false, fork_general = false, atomic_stream = false; // final behind the lazy tables: after_tables
     CartPlan box;   // cart: what the launchers of the cartesian family do (plan_cart)
     CartPlan level; // overlay3: the same for the first level lattice (every level shares its scheme, law and kernels)
@@ -192,6 +193,15 @@ namespace
     const bool blocked2 = p.cart && c->v.dim == 2 && !residual_only && c->v.layout == PFM_LAYOUT_BLOCKED;
     p.fill_up_block = blocked2 && phase <= 1 && c->n_blocks == 4 && d_values[1] && Switches::cart2d_fill() && !p.keep_up_block;
     p.up_block_cleared = p.keep_up_block || p.fill_up_block || (blocked2 && phase == 2 && Switches::cart2d_fill());
+    // A kept (u,u) block (pfm_values_keep_uu_block) is left alone while it provably holds the current values.  Only where the
+    // block cannot depend on `solution` and the library is the only writer of the node state: the pair of a 3-D box (blocked
+    // layout, linear scheme, kappa < 0.5, homogeneous material, the whole assembly, no level lattice -- CartPlan::pair) on a
+    // context without ghost nodes or peers.  Everywhere else the promise is ignored and the block is written; that assembly
+    // leaves the block stale for the next one that would keep it (assemble_impl).  PFM_NO_KEEP_UU_BLOCK=1: ignored everywhere.
+    const double *uu = (!residual_only && c->n_blocks == 4 && d_values) ? d_values[0] : nullptr;
+    p.keep_uu = uu && uu == c->kept_uu_block && Switches::keep_uu_block() && p.pair && c->peers.empty() && c->v.n_owned == c->v.n_nodes;
+    if (p.keep_uu)
+      plan_keep_uu(p.box, c->v, c->cv, cart_n_cu());
     return p;
   }
 
@@ -277,6 +287,41 @@ namespace
         c->device_bytes += (int64_t)c->cv.patch_cap * 16 + 4;
       }
     return hipMemsetAsync(c->cv.patch_count, 0, sizeof(int), c->stream) == hipSuccess ? PFM_OK : fail(c, PFM_ERR_HIP, "patch list reset");
+  }
+
+  // AssemblyPlan::keep_uu: the saved patch list of the kept (u,u) block, as long as the patch list (behind ensure_patch_list).
+  // A new one is empty and the block counts as stale.  uu_stale_pending: the word is raised here, on the assembly's stream.
+  int ensure_uu_keep(pfm_ctx *c, pfm::UuKeep &keep)
+  {
+    if (!c->uu_words)
+      return fail(c, PFM_ERR_INTERNAL, "kept (u,u) block without its device words");
+    if (c->uu_saved_cap < c->cv.patch_cap || !c->uu_saved_count)
+      {
+        (void)hipStreamSynchronize(c->stream); // (off the hot path: a kernel in flight may still read the old list)
+        for (void *q : {(void *)c->uu_saved_idx, (void *)c->uu_saved_val, (void *)c->uu_saved_count})
+          if (q)
+            (void)hipFree(q);
+        c->device_bytes -= (int64_t)c->uu_saved_cap * 16 + (c->uu_saved_count ? 4 : 0);
+        c->uu_saved_idx = nullptr, c->uu_saved_val = nullptr, c->uu_saved_count = nullptr, c->uu_saved_cap = 0;
+        const size_t cap = (size_t)std::max(c->cv.patch_cap, 1);
+        if (hipMalloc((void **)&c->uu_saved_idx, cap * sizeof(long long)) != hipSuccess ||
+            hipMalloc((void **)&c->uu_saved_val, cap * sizeof(double)) != hipSuccess ||
+            hipMalloc((void **)&c->uu_saved_count, sizeof(int)) != hipSuccess)
+          return fail(c, PFM_ERR_NOMEM, "saved patch list of the kept (u,u) block");
+        c->uu_saved_cap = (int)cap;
+        c->device_bytes += (int64_t)c->uu_saved_cap * 16 + 4;
+        if (hipMemsetAsync(c->uu_saved_count, 0, sizeof(int), c->stream) != hipSuccess)
+          return fail(c, PFM_ERR_HIP, "saved patch list reset");
+        c->uu_stale_pending = true;
+      }
+    if (c->uu_stale_pending)
+      {
+        if (hipMemsetD32Async((hipDeviceptr_t)c->uu_words, 1, 1, c->stream) != hipSuccess)
+          return fail(c, PFM_ERR_HIP, "raise the stale word of the kept (u,u) block");
+        c->uu_stale_pending = false;
+      }
+    keep = {c->uu_words, c->uu_saved_idx, c->uu_saved_val, c->uu_saved_count};
+    return PFM_OK;
   }
 
   // the lazy tables of the plan's family; gather_ready: the gather has its tables (false: the atomic class stays)
@@ -401,8 +446,12 @@ namespace
         if (const int rcs = sparse_buffers(c, c->cv, p.box, c->buf_sparse_cells, c->buf_sparse_flags, c->sparse_tiles, c->stream, sparse))
           return rcs;
       }
+    pfm::UuKeep keep{};
+    if (p.keep_uu)
+      if (const int rck = ensure_uu_keep(c, keep))
+        return rck;
     rc = launch_assemble_cart(p.box, c->v, cv, c->prm, d_values, d_res_pde, d_res_tot, c->stream, p.fork ? c->side_stream : c->stream,
-                              c->d_scal, &c->clock, n_compressed, run_sparse ? &sparse : nullptr);
+                              c->d_scal, &c->clock, n_compressed, run_sparse ? &sparse : nullptr, p.keep_uu ? &keep : nullptr);
     if (p.box.split3_jac())
       c->compressed_valid = rc == PFM_OK;
     if (run_sparse)
@@ -411,7 +460,7 @@ namespace
       if (const int rcj = join_from(c, c->side_stream, c->stream, c->ev_join, "join"))
         return rcj;
     if (p.pair && rc == PFM_OK)
-      rc = launch_cart_apply_patches(c->cv, d_values[0], c->stream, c->v.status);
+      rc = launch_cart_apply_patches(c->cv, d_values[0], c->stream, c->v.status, p.keep_uu ? &keep : nullptr);
     return PFM_OK;
   }
 
@@ -593,6 +642,8 @@ namespace
       c->compressed_valid = false; // pfm_ctx_split_route_info: the count belongs to the last full assembly
     if (!residual_only && phase != 1 && !(plan.cart && plan.box.voldev_sparse) && !(plan.overlay3 && plan.level.voldev_sparse))
       c->sparse_valid = false; // pfm_ctx_split_sparse_info: likewise
+    if (!residual_only && d_values && c->kept_uu_block && d_values[0] == c->kept_uu_block && !plan.keep_uu)
+      c->uu_stale_pending = true; // written by a path that does not record what the kept form needs (its patches stay added)
     bool gather_ready = false;
     if (const int rct = ensure_tables(c, plan, gather_ready))
       return rct;
@@ -678,6 +729,7 @@ extern "C"
     if (!c || kernel < 0 || kernel >= PFM_ZC_KERNELS || planes < 0)
       return PFM_ERR_BAD_ARG;
     c->cv.zc_force[kernel] = planes;
+    c->uu_stale_pending = true; // (a kept (u,u) block: written again by the tiles of the new length)
     for (auto &lv : c->levels3)
       lv.cv.zc_force[kernel] = planes;
     if (kernel == PFM_ZC_RES3 && c->overlap_lists_ready)
@@ -915,6 +967,8 @@ extern "C"
 
   int pfm_ctx_force_path(pfm_ctx *c, int path)
   {
+    if (c)
+      c->uu_stale_pending = true; // a kept (u,u) block is written again by whatever runs next
     if (path == 3 && c && !c->cart_ok && (c->n_patch_blocks > 0 || !c->levels3.empty()))
       {
         c->kernel_path = 3;

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstring>
 #include <vector>
 
 using namespace pfm;
@@ -49,6 +50,7 @@ namespace
       return PFM_ERR_BAD_ARG;
     (void)hipSetDevice(c->device);
     c->delta.valid = false; // the values move to other slots: what the host holds is not what the shadow describes
+    c->uu_stale_pending = true; // ... and a kept (u,u) block is written again
     const int dim = c->v.dim;
     int ncr, ncc;
     if (c->v.layout == PFM_LAYOUT_INTERLEAVED)
@@ -189,7 +191,7 @@ namespace pfm
             d[k] = c->d_stage_vec[k];
           }
       }
-    int rc = launch_state_set(c->v, d[0], d[1], d[2], c->stream);
+    int rc = launch_state_set(c->v, d[0], d[1], d[2], c->stream, c->uu_words);
     if (rc)
       return fail(c, rc, "state_set launch failed");
     if (!on_device)
@@ -261,7 +263,8 @@ extern "C"
       }
     for (void *q : {(void *)c->d_send_all, (void *)c->d_recv_all, (void *)c->d_send_ptr, (void *)c->d_recv_ptr,
                     (void *)c->d_halo_send, (void *)c->d_halo_recv, (void *)c->cv.patch_idx, (void *)c->cv.patch_val,
-                    (void *)c->cv.patch_count})
+                    (void *)c->cv.patch_count, (void *)c->uu_words, (void *)c->uu_saved_idx, (void *)c->uu_saved_val,
+                    (void *)c->uu_saved_count})
       if (q)
         (void)hipFree(q);
     if (c->atomic_stream)
@@ -350,6 +353,42 @@ extern "C"
     return PFM_OK;
   }
 
+  // The kept (u,u) block (include/pfm_assemble.h; plan_assembly decides per call whether d_values[0] is it and whether the
+  // promise applies).  Nothing is cleared: the block counts as stale until an assembly has written it.
+  int pfm_values_keep_uu_block(pfm_ctx *c, double *d_values_uu)
+  {
+    if (!c)
+      return PFM_ERR_BAD_ARG;
+    if (c->n_blocks != 4)
+      return fail(c, PFM_ERR_BAD_ARG, "pfm_values_keep_uu_block: the interleaved layout has no (u,u) block of its own");
+    c->kept_uu_block = nullptr;
+    c->uu_stale_pending = true;
+    if (!d_values_uu)
+      return PFM_OK;
+    if (c->block_nnz(0) <= 0)
+      return fail(c, PFM_ERR_BAD_ARG, "pfm_values_keep_uu_block: the (u,u) block is empty");
+    if (!c->uu_words)
+      {
+        (void)hipSetDevice(c->device);
+        if (hipMalloc((void **)&c->uu_words, 2 * sizeof(int)) != hipSuccess)
+          return fail(c, PFM_ERR_NOMEM, "hipMalloc device words of the kept (u,u) block");
+        c->device_bytes += 2 * (int64_t)sizeof(int);
+        const int init[2] = {1, 0};
+        if (hipMemcpy(c->uu_words, init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess)
+          return fail(c, PFM_ERR_HIP, "pfm_values_keep_uu_block");
+      }
+    c->kept_uu_block = d_values_uu;
+    return PFM_OK;
+  }
+
+  int pfm_values_uu_block_kept(const pfm_ctx *c, const double **d_values_uu)
+  {
+    if (!c || !d_values_uu)
+      return PFM_ERR_BAD_ARG;
+    *d_values_uu = c->kept_uu_block;
+    return PFM_OK;
+  }
+
   int pfm_set_params(pfm_ctx *c, const pfm_params *p)
   {
     if (!c || !p)
@@ -360,6 +399,8 @@ extern "C"
     if (c->v.dim == 3 && c->split_model == PFM_SPLIT_REFERENCE && p->decompose_stress_matrix > 0 && p->timestep_number > 0)
       return fail(c, PFM_ERR_UNSUPPORTED,
                   "stress split is 2-D only in the reference (cracks.cc:1685-1690)");
+    if (!c->have_params || memcmp(&c->prm, p, sizeof(pfm_params)) != 0)
+      c->uu_stale_pending = true; // a kept (u,u) block (pfm_values_keep_uu_block) follows the parameters, byte by byte
     c->prm = *p;
     c->have_params = true;
     c->scal_dirty = true; // the per-launch scalar tables of the cartesian Jacobian kernels follow the parameters
@@ -377,6 +418,7 @@ extern "C"
     if (model == PFM_SPLIT_VOLDEV && c->v.dim != 3)
       return fail(c, PFM_ERR_UNSUPPORTED, "the volumetric-deviatoric split is a 3-D law; 2-D keeps the reference's closed form");
     c->split_model = model;
+    c->uu_stale_pending = true;
     return PFM_OK;
   }
 
@@ -391,6 +433,7 @@ extern "C"
     if (route != PFM_SPLIT_ROUTE_GENERAL && c->v.dim != 3)
       return fail(c, PFM_ERR_UNSUPPORTED, "the lattice routes carry the 3-D split laws");
     c->split_route = route;
+    c->uu_stale_pending = true;
     return PFM_OK;
   }
 
@@ -414,14 +457,34 @@ extern "C"
     if (c->cart_ok && c->v.dim == 3)
       {
         std::atomic<int64_t> nf{0};
-        parallel_for(c->v.n_owned, [&](int64_t nb, int64_t ne) {
+        // a kept (u,u) block follows the displacement bits alone: the phase-field bit changes at every active-set update
+        // (k_active_set writes no other bit), so the bits of the last call are what the device holds
+        const bool first = c->h_flags_u.size() != (size_t)c->v.n_nodes;
+        if (first)
+          c->h_flags_u.assign((size_t)c->v.n_nodes, 0);
+        std::atomic<bool> changed{first};
+        uint8_t *const last = c->h_flags_u.data();
+        parallel_for(c->v.n_nodes, [&](int64_t nb, int64_t ne) {
           int64_t k = 0;
+          bool diff = false;
           for (int64_t n = nb; n < ne; ++n)
-            k += __builtin_popcount(node_flags[n] & 7u);
+            {
+              const uint8_t f = node_flags[n] & 7u;
+              if (n < c->v.n_owned)
+                k += __builtin_popcount(f);
+              diff |= f != last[n];
+              last[n] = f;
+            }
           nf += k;
+          if (diff)
+            changed = true;
         });
         c->n_flag_u = nf;
+        if (changed)
+          c->uu_stale_pending = true;
       }
+    else
+      c->uu_stale_pending = true;
     if (e == hipSuccess)
       e = hipStreamSynchronize(c->stream); // node_flags is a borrowed host buffer
     return e == hipSuccess ? PFM_OK : hipfail(c, e, "set_constraints copy");

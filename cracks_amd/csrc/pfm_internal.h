@@ -119,6 +119,10 @@ namespace pfm
                                       // import lands (cracks.cc:2147-2154 next to the cell loop instead of in front of it)
     int zc_force[4];                  // pfm_ctx_force_zchunk, per marching kernel (PFM_ZC_*): 0 = the default length
                                       // (tuning variable, else the dispatch model), > 0 = that many planes (host side only)
+    const int *uu_stale;              // k_cart_uu3 into a kept (u,u) block (pfm_values_keep_uu_block): the device word that says
+                                      // whether the block must be written.  Every workgroup reads it once, before its first
+                                      // barrier, and returns when it is 0 (about 3 ns per skipped workgroup, as the early exits
+                                      // of the overlapped assembly).  nullptr: the launch writes.
   };
   // the marching kernels of the cartesian family, indices of CartView::zc_force (pfm_ctx_force_zchunk)
   enum
@@ -150,8 +154,10 @@ namespace pfm
   };
 
   // launchers implemented in pfm_kernels.hip
+  // uu_stale: the word of a kept (u,u) block (pfm_ctx::uu_words) or nullptr -- set to 1 when a phi_old or phi_oldold
+  // of an owned node changes its bit pattern
   int launch_state_set(const DevView &v, const double *d_sol, const double *d_old,
-                       const double *d_oldold, hipStream_t s);
+                       const double *d_oldold, hipStream_t s, int *uu_stale = nullptr);
   // fills v.cslot from the current order of the node-graph rows (context creation, pfm_pattern_bind)
   int launch_build_cslot(const DevView &v, hipStream_t s);
   // d_out[a * n + i] = d_in[i * w + a] (mesh tables: host AoS -> device SoA)
@@ -182,10 +188,19 @@ namespace pfm
     int *tile_flag;     // [ntx nty nch of grid[PFM_ZC_UU3]] 1 = the tile-chunk owns a vertex of such a cell
     int *n_rows;        // nodes whose rows the sparse form of k_cart_split3_jac recomputed
   };
+  // CartPlan::keep_uu: the device words and the saved patch list of the context's kept (u,u) block (pfm_ctx::uu_*)
+  struct UuKeep
+  {
+    int *words;           // [0] stale: the block must be written; [1] written: the assembly in flight wrote it (k_uu_mark)
+    long long *saved_idx; // entries the deferred patches of the writing assembly went to, and their values before the patch
+    double *saved_val;
+    int *saved_count;
+  };
   int launch_assemble_cart(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
                            double *res_pde, double *res_tot, hipStream_t s, hipStream_t s_side, void *d_scal, KernelClock *clock,
                            int *n_compressed = nullptr /* CartPlan::voldev_jac: device counter, zeroed by the caller */,
-                           const SplitSparse *sparse = nullptr /* CartPlan::voldev_sparse */);
+                           const SplitSparse *sparse = nullptr /* CartPlan::voldev_sparse */,
+                           const UuKeep *keep = nullptr /* CartPlan::keep_uu */);
   // pfm_cart_split3.hip: the matrix values of a CartPlan::voldev_jac assembly (sparse: its rows at compressed cells alone,
   // behind launch_cart_split3_mark and the unsplit kernels)
   int launch_cart_split3_jac(const CartPlan &pl, const DevView &v, const CartView &cv, const pfm_params &p, double *const *d_values,
@@ -198,7 +213,12 @@ namespace pfm
                       double *res_pde, KernelClock *clock);
   int launch_cart_phi4(const CartPlan &pl, const DevView &v, const CartView &cv, double *const *d_values, hipStream_t s,
                        const void *d_scal, double *res_pde, KernelClock *clock);
-  int launch_cart_apply_patches(const CartView &cv, double *vals_uu, hipStream_t s, int *status);
+  // keep (CartPlan::keep_uu): an assembly that wrote the block records the values under its patches, one that kept it
+  // finds them put back (launch_uu_mark_restore) and adds as ever
+  int launch_cart_apply_patches(const CartView &cv, double *vals_uu, hipStream_t s, int *status, const UuKeep *keep = nullptr);
+  // behind k_cart_uu3 on its stream: written := stale, stale := 0; then, in an assembly that kept the block, the recorded
+  // values go back under the patches of the last one
+  int launch_uu_mark_restore(const UuKeep &keep, double *vals_uu, hipStream_t s);
   int cart_n_cu();                                 // CUs of the device (asked once)
   int cart_zchunk(CartView cv, int kernel);        // chunk length of a whole assembly of cv by marching kernel PFM_ZC_*
   // XCD-aware launch: workgroup i runs on XCD i % 8.  The kernels are launched with a grid rounded up to a multiple
@@ -338,6 +358,19 @@ struct pfm_ctx
   // (nullptr: no promise).  stage_up_kept: d_stage_val[1] was cleared when it was allocated; only pfm_assemble writes it
   double *kept_up_block = nullptr;
   bool stage_up_kept = false;
+  // pfm_values_keep_uu_block: the caller's (u,u) block that nobody but the library writes (nullptr: no promise), the two
+  // device words of pfm::UuKeep and the saved patch list (capacity CartView::patch_cap).  uu_stale_pending: an input of K_uu
+  // changed on the host side, or something else wrote the block -- the next assembly that would keep it raises the word
+  // first, on its stream.  prm_uu: the parameter bytes of the last pfm_set_params.  h_flags_u: the displacement bits of the
+  // last pfm_set_constraints.
+  double *kept_uu_block = nullptr;
+  int *uu_words = nullptr;
+  long long *uu_saved_idx = nullptr;
+  double *uu_saved_val = nullptr;
+  int *uu_saved_count = nullptr;
+  int uu_saved_cap = 0;
+  bool uu_stale_pending = true;
+  std::vector<uint8_t> h_flags_u;
   // host arrays the caller page-locked through pfm_host_register (DMA at the link rate instead of the pageable path);
   // zeroed: the array is the (u,phi) block of a matrix and has been cleared once (pfm_values_to_host never copies it)
   struct HostPin

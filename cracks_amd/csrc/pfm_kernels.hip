@@ -2272,7 +2272,7 @@ namespace pfm
     // ------------------------------------------------------------ small kernels
     template <int dim>
     __global__ void k_state_set(DevView v, const double *__restrict__ sol, const double *__restrict__ old,
-                                const double *__restrict__ oldold)
+                                const double *__restrict__ oldold, int *__restrict__ uu_stale)
     {
       const int n = blockIdx.x * blockDim.x + threadIdx.x;
       if (n >= v.n_owned)
@@ -2284,8 +2284,14 @@ namespace pfm
       v.phi[n] = sol[dp];
       if (old) // nullptr: pfm_state_set_solution, the old fields keep their values (kernel argument: uniform branch)
         {
-          v.phi_old[n] = old[dp];
-          v.phi_oldold[n] = oldold[dp];
+          const double po = old[dp], poo = oldold[dp];
+          // a kept (u,u) block (pfm_values_keep_uu_block) is a function of these two fields: compared as bit patterns, so
+          // that a NaN equals itself and -0.0 differs from +0.0
+          if (uu_stale && (__double_as_longlong(v.phi_old[n]) != __double_as_longlong(po) ||
+                           __double_as_longlong(v.phi_oldold[n]) != __double_as_longlong(poo)))
+            *uu_stale = 1;
+          v.phi_old[n] = po;
+          v.phi_oldold[n] = poo;
         }
     }
 
@@ -2533,15 +2539,15 @@ namespace pfm
   } // namespace
 
   int launch_state_set(const DevView &v, const double *sol, const double *old, const double *oldold,
-                       hipStream_t s)
+                       hipStream_t s, int *uu_stale)
   {
     if (v.n_owned == 0)
       return PFM_OK;
     const int bs = 256, nb = (v.n_owned + bs - 1) / bs;
     if (v.dim == 2)
-      hipLaunchKernelGGL(k_state_set<2>, dim3(nb), dim3(bs), 0, s, v, sol, old, oldold);
+      hipLaunchKernelGGL(k_state_set<2>, dim3(nb), dim3(bs), 0, s, v, sol, old, oldold, uu_stale);
     else
-      hipLaunchKernelGGL(k_state_set<3>, dim3(nb), dim3(bs), 0, s, v, sol, old, oldold);
+      hipLaunchKernelGGL(k_state_set<3>, dim3(nb), dim3(bs), 0, s, v, sol, old, oldold, uu_stale);
     return check_launch();
   }
 

@@ -29,6 +29,8 @@ namespace pfm
     static bool cart2d_fill() { return !set("PFM_CART2D_NO_FILL") && !cart2d_one_launch(); }
     // a kept (u,phi) block (pfm_values_keep_up_block) is left alone (PFM_NO_KEEP_UP_BLOCK: the promise is ignored, every path writes it)
     static bool keep_up_block() { return !set("PFM_NO_KEEP_UP_BLOCK"); }
+    // a kept (u,u) block (pfm_values_keep_uu_block) is left alone while it is current (PFM_NO_KEEP_UU_BLOCK: the promise is ignored, every assembly writes it)
+    static bool keep_uu_block() { return !set("PFM_NO_KEEP_UU_BLOCK"); }
     static bool fused_scatter() { return !set("PFM_NO_FUSED_SCATTER"); }     // line search: the residual kernel scatters the solution
     static bool levels_concurrent() { return set("PFM_OVERLAY3_CONCURRENT"); } // 3-D overlay: a stream per level lattice
     static bool res_no_transfers() { return set("PFM_RES_NO_TRANSFERS"); }   // k_cart_residual3 instead of 3x / 3d

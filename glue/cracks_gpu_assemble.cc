@@ -418,6 +418,9 @@ namespace pfm_glue_detail
             // and left alone by every assembly (withdrawn by pfm_ctx_destroy in release(), in front of the hipFree)
             if (blocked && block == 1 && nnz[block] > 0)
               PFM_CALL(ctx, pfm_values_keep_up_block(ctx, d_val[block]));
+            // the (u,u) block: likewise ours; the library rewrites it only when an input of it has changed
+            if (blocked && block == 0 && nnz[block] > 0)
+              PFM_CALL(ctx, pfm_values_keep_uu_block(ctx, d_val[block]));
             // Epetra's value array receives 35 GB per Jacobian at 1e7 cells: page-locked, the transfer is DMA at the link
             // rate (pageable memory: a fraction of it).  Best effort: if the pages cannot be locked the copy still works.
             // Opt-in (pin_host_matrix): the lock must be gone BEFORE the matrix is reinitialised in setup_system --

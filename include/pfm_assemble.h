@@ -502,6 +502,36 @@ int pfm_assemble(pfm_ctx *ctx, const double *sol, const double *old, const doubl
 int pfm_values_keep_up_block(pfm_ctx *ctx, double *d_values_up /* NULL: withdraw */);
 int pfm_values_up_block_kept(const pfm_ctx *ctx, const double **d_values_up);
 
+/* A kept (u,u) block (4-block layout only).  In the quasi-monolithic scheme without the penalty term and without a stress
+ * split (every Sneddon and Miehe parameter file of the reference) the (u,u) block is a function of old_solution,
+ * old_old_solution, the displacement constraints and the parameters -- not of `solution` (cracks.cc:2262-2277, 2353-2364,
+ * 4275) -- so every Newton iteration of a time step after the first rewrites the same values: 9/16 of the matrix.
+ *   pfm_values_keep_uu_block   remembers the pointer; nothing is cleared or written.  The caller promises that nothing but
+ *                              this library writes that array.  In turn a pfm_assemble_device / pfm_assemble_overlapped
+ *                              whose d_values[0] EQUALS that pointer leaves the block alone when it provably holds the
+ *                              current values: the library raises a device word whenever an input of the block changes
+ *                              (the promise itself, pfm_set_params with other bytes, pfm_set_constraints with another
+ *                              displacement bit, pfm_pattern_bind*, pfm_set_split_model / _route, pfm_ctx_force_path /
+ *                              _zchunk, pfm_state_set with another bit pattern of old or oldold at any owned node, any
+ *                              assembly that wrote the array on another path), the (u,u) kernel reads it on the device and
+ *                              the call stays asynchronous.  The promise takes effect only on the two-stream pair of a
+ *                              3-D box: linear scheme, kappa < 0.5, homogeneous material, whole assembly, no level lattice, a
+ *                              context without ghost nodes or peers, none of PFM_RES_KERNEL / PFM_JAC_SEQUENTIAL / the phase
+ *                              clocks.  Everywhere else it is accepted and ignored and the block is written at every
+ *                              assembly.  Under the promise, where it takes effect, the displacement rows of residual_pde
+ *                              come from the quadrature kernel in EVERY assembly, written or kept: they are the rows
+ *                              PFM_RES_KERNEL=1 gives, bit for bit, equal from one assembly to the next, within the parity
+ *                              bar of the reference, and not bit-equal to the rows the Jacobian kernel derives from its
+ *                              matrix rows without the promise.  The four value blocks keep their bits.  A call with any
+ *                              other d_values[0] behaves as without a promise and leaves it in place.  One promise per
+ *                              context; NULL withdraws it (pfm_ctx_destroy does it too) and must do so BEFORE the array is
+ *                              freed or reallocated.  PFM_ERR_BAD_ARG for the interleaved layout and for a non-NULL pointer
+ *                              when block_nnz(0) == 0.  PFM_NO_KEEP_UU_BLOCK=1 (read per call): ignored everywhere.
+ *   pfm_values_uu_block_kept   the kept pointer, NULL if there is none.
+ * pfm_assemble (host pointers) is unchanged: its cost is the copy to the host. */
+int pfm_values_keep_uu_block(pfm_ctx *ctx, double *d_values_uu /* NULL: withdraw */);
+int pfm_values_uu_block_kept(const pfm_ctx *ctx, const double **d_values_uu);
+
 /* Delta transfer of the matrix values ("Delta transfer"): within a time step most of the Jacobian does not
  * change between Newton iterations (without the stress split the displacement rows depend on the lagged phase field
  * only), and the library finds out itself which values did.
